@@ -1,23 +1,31 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: rendered rays/s (RGB + depth + 29-class semantics, 800x800) and train-step ms.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  N > 1 without a torch.distributed environment starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process (before anything here touches the GPU)
 and relays its output; under torch.distributed.run it is one rank per GPU over RCCL.
 
-Output.  Rank 0 prints ONE JSON line of < 4 KB on stdout (`headline_line`: metric, value, config.workload, dtype, `roofline`,
-`cpu_baseline`, scalar summaries of the other legs) and writes everything else — every leg's full record — to
-`bench_detail.json` next to this file (`--detail-file`); progress goes to stderr.
+Output.  Rank 0 prints ONE JSON line of < 4 KB on stdout (`headline_line`: metric, value, unit, higher_is_better, dtype,
+ms_per_step, config.workload; with `--full` also `roofline`, `cpu_baseline` and scalar summaries of the other legs) and writes
+the run's full record to `bench_detail.json` next to this file (`--detail-file`); progress goes to stderr.
 
-Legs of the default run (`--workload all`):
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the headline's last timed step computed, as DIR/<name>.npy in
+float32 / float64 (< 64 MB in all; `dump_rows`: a fixed, seeded sample of the rays of a larger render).  The inputs (stand-in
+weights, poses, rays) depend only on the arguments, so two builds can be compared output for output.
+
+A plain run (`--workload all` or `render800`) is only the headline: set-up (the stand-in scene is trained once per library build
+and cached), `--warmup` steps, `--steps` timed steps, the outputs, the line:
 
   value / ms_per_step   BASELINE config 3: a step = `--views` (default 4) full-resolution 800x800 views of the trained
                         stand-in of Habitat scene 102344529 rendered in ONE batched call of the reference's test-time renderer
                         semantics (perception/models/utils.py:555-779) — rays, weights and occupancy grid resident in HBM.
                         With N GPUs every rank renders its own views (independent units, no data-path collective: weak
                         scaling); value = whole-job rays/s.
+
+`--full` adds every other leg:
+
   roofline              the dominant kernel (fused hash gather + MLPs + compositing): algorithmic bytes / hipEvent time of its
                         launches in a second pass of the same steps with ONE render job in flight (the timed pass runs two
                         jobs side by side, whose launches overlap: a per-launch duration is only meaningful for the serial form)
@@ -34,13 +42,13 @@ Legs of the default run (`--workload all`):
   cpu_baseline          the oracle (CPU port of the same path) on this box's host cores, on a bounded sample of the headline workload
                         (24x24 rays of one benchmark view, <= ~12 s), and `bench_parity`: the HIP render of the same rays against it.
                         The run FAILS (exit code 3) above the north-star tolerance.
-
-`--full` adds the legs of tools/bench_extra.py (the drop-in surface as the reference calls it, ensemble steps, presampled and
-dynamic-schedule train steps, random-weight / fp16-blend renders, the BL-1 and per-shape CPU baselines).
+  tools/bench_extra.py  the drop-in surface as the reference calls it, ensemble steps, presampled and dynamic-schedule train
+                        steps, random-weight / fp16-blend renders, the BL-1 and per-shape CPU baselines.
 
 Weights: trained stand-ins (`apnrf_amd.standin`): the product's own `train_step` for 2000 iterations on an
 analytic target built from the procedural occupancy grid — bitwise reproducible (seeded draws, deterministic gradient
-accumulation), so the scenes are the same on every box.  `--workload` restricts the run to one part.
+accumulation), so the scenes are the same on every box.  `--workload train | config2 | score256` runs that one leg, which
+then gives the headline (its secondary passes included; the tools/bench_extra.py part of it with `--full`).
 """
 import argparse
 import gc
@@ -80,7 +88,11 @@ def parse(argv=None):
     ap.add_argument("--standin-steps", type=int, default=2000, help="training iterations of the stand-in scenes (SURVEY 8d: 2000)")
     ap.add_argument("--weights", default="trained", choices=["trained", "random"],
                     help="random = round 1's random-init weights with an engineered density gain (continuity only)")
-    ap.add_argument("--full", action="store_true", help="also run the legs of tools/bench_extra.py (detail file only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline and one-view passes, the train / config 2 / scoring legs (--workload all), "
+                         "the CPU baseline with the bench parity check, and the legs of tools/bench_extra.py")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     ap.add_argument("--detail-file", default=os.path.join(REPO, "bench_detail.json"))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the second, hipEvent-instrumented passes")
@@ -91,7 +103,10 @@ def parse(argv=None):
     ap.add_argument("--train-dtypes", default="f16,bf16", help="matrix-core operand types of the train leg")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of an N > 1 job (nccl = RCCL; gloo: test rigs)")
     ap.add_argument("--one-device", action="store_true", help="test rigs: every rank uses cuda:0 (two ranks on a one-GPU box; RCCL refuses that, so with --dist-backend gloo)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(args):
@@ -166,6 +181,42 @@ def _dig(d, ks):
             return None
         d = d[k]
     return d
+
+
+# ------------------------------------------------------------------ --dump-outputs: what the headline's last timed step computed
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS = 1 << 18                   # rays of a render kept in the dump: 262 144 x (3 + 1 + 1 + 29) floats = 36 MB
+
+
+def dump_rows(n, k=DUMP_ROWS, seed=0):
+    """A fixed, seeded, ascending sample of k of the n rows of an output (all of them when n <= k): the same rows in every run with the same arguments."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def render_outputs(r):
+    """The dict `render_views` returned -> host arrays: rgb / acc / depth / sem of the `dump_rows` sample, `rows` (their indices in the step's rays)
+    and `total_samples` ([kept, evaluated] of the whole step)."""
+    import torch
+    rows = dump_rows(r["rgb"].shape[0])
+    idx = torch.from_numpy(rows).to(r["rgb"].device)
+    out = {k: r[k].index_select(0, idx).float().cpu().numpy() for k in ("rgb", "acc", "depth", "sem")}
+    out["rows"] = rows.astype(np.float64)
+    out["total_samples"] = r["total"].cpu().numpy().astype(np.float64)
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    """arrays (name -> array) -> out_dir/<name>.npy, float32 stays float32 and everything else becomes float64; at most DUMP_MAX_BYTES in all"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
 
 
 # ------------------------------------------------------------------ counter traffic from committed profiles
@@ -360,13 +411,19 @@ class Ctx:
         self.L = L
         self.lib = L.load_library()
         self.standin_info, self.opt_states, self._scenes = {}, {}, {}
+        self.outputs = None           # host arrays of the headline's last timed step (rank 0, --dump-outputs)
 
     def log(self, msg):
         if self.rank == 0:
             log(msg)
 
     def want(self, w):
-        return self.args.workload in ("all", w)
+        """--workload all: the headline leg (render800), every leg with --full"""
+        a = self.args
+        return a.workload == w or (a.workload == "all" and (a.full or w == "render800"))
+
+    def dumping(self):
+        return self.args.dump_outputs is not None and self.rank == 0
 
     def scene_model(self, name, seed=9, steps=None, keep_optimizer=False, neurons=128, layers=2):
         """(scene dict, field, estimator): the trained stand-in.  Rank 0 trains or loads the cache; the other ranks load the cache it
@@ -448,6 +505,7 @@ class RenderLeg:
         self.n_views, self.n_per_view = len(poses), width * height
         self.bk = torch.zeros(3)
         self.process_samples = torch.zeros((), dtype=torch.int64, device=cx.dev)      # every evaluated sample of this process (PMC sums cover all launches)
+        self.last = None              # what the last timed step of the latest `run` returned (taken by --dump-outputs, then dropped)
 
     def run(self, V, steps, warmup, with_events, n_split=2):
         from apnrf_amd import render as RD
@@ -456,6 +514,7 @@ class RenderLeg:
         batches = [(self.rays.origins[k:k + V].reshape(-1, 3).contiguous(), self.rays.viewdirs[k:k + V].reshape(-1, 3).contiguous())
                    for k in range(0, self.n_views, V)]
         evaluated = torch.zeros((), dtype=torch.int64, device=cx.dev)
+        self.last = None
 
         def step(i):
             o, d = batches[i % len(batches)]
@@ -465,8 +524,14 @@ class RenderLeg:
 
         def collect(r):
             evaluated.add_(r["total"][1])
+            self.last = r
         dt = cx.timed(step, steps, warmup, with_events, collect)
         return dt, int(evaluated.item())
+
+    def take_last(self):
+        """host arrays of the last timed step's outputs when this rank dumps them; the device tensors are released either way"""
+        r, self.last = self.last, None
+        return render_outputs(r) if self.cx.dumping() else None
 
     def roofline(self, V, steps, kernel_name, traffic_key="field_kernel"):
         """second pass of the same K steps, ONE job in flight, hipEvent pairs around every field-kernel launch (hipEventRecord between dependent launches
@@ -496,6 +561,7 @@ def leg_render800(cx, line):
     V, n_per_view = args.views, width * height
     cx.log("render800: timed pass")
     dt, samples = leg.run(V, args.steps, args.warmup, False, n_split=args.render_jobs)      # the reported value: no instrumentation
+    cx.outputs = leg.take_last()
     cx.log(f"render800: {1e3 * dt / args.steps:.2f} ms/step, {samples / (n_per_view * V * args.steps):.1f} samples/ray")
     line["value"] = n_per_view * V * world * args.steps / dt
     line["ms_per_step"] = 1e3 * dt / args.steps
@@ -505,12 +571,12 @@ def leg_render800(cx, line):
                            "ms_per_view": 1e3 * dt / args.steps / V, "samples_per_ray": samples / (n_per_view * V * args.steps),
                            "samples_per_s": samples * world / dt, "render_jobs_in_flight": min(args.render_jobs, V),
                            "march_order": "8x8 pixel blocks inside every view (mnf_render_opts.view_order); per-ray results do not depend on it"})
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         r = leg.roofline(V, args.steps, "mnf::field_kernel<128,2,2,false> (hash gather + MLPs + fused compositing)")
         if r:
             line["roofline"] = r
             cx.log(f"render800 field kernel: {r['avg_launch_ms']:.4f} ms per {r['samples_per_launch'] / 1e6:.2f} M samples = {r['frac']:.3f} of {HBM_PEAK_GBS:.0f} GB/s")
-    if V != 1 and not args.no_views1:
+    if args.full and V != 1 and not args.no_views1:
         dt1, s1 = leg.run(1, args.steps, 2, False)
         line["render_views1"] = {"value": n_per_view * world * args.steps / dt1, "unit": "rays/s", "ms_per_view": 1e3 * dt1 / args.steps,
                                  "samples_per_ray": s1 / (n_per_view * args.steps)}
@@ -597,6 +663,7 @@ class TrainLeg:
                 return RD.train_step(tf, te, opt, r, pix, dep_, lab, bkd, step=1000 + i, sync=sync, occ_thre=1e-2, **SC.RENDER_KW)
         warm = max(args.warmup, 6)
         dt_t = cx.timed(tstep, steps, warm, False, outs.append)      # (the first asynchronous steps also size the sample bounds)
+        self.last = outs[-1]
         kept = float(np.mean([int(o["n_rendering_samples"]) for o in outs]))
         marched = float(int(te.last_sampling["n_marched"]))
         res = {"ms_per_step": 1e3 * dt_t / steps, "steps": steps, "rays_per_step": R_, "dtype": dtype, "model": self.model,
@@ -644,10 +711,13 @@ def leg_train(cx, line):
     train = {"workload": "BASELINE config 5: scene 102344280 (trained stand-in, training continued from the same state in every leg), 8192-ray batches "
                          "of one 640x640 view, occupancy sampling + density pre-pass + differentiable render + loss (pipeline.py:506-511) + backward "
                          "+ NaN guard + FusedAdam; occupancy refresh every 16th step; asynchronous steps (sync=False)"}
+    first_out = None
     for dt_ in dtypes:
         cx.log(f"train {dt_}: timed passes")
         leg = tl.run(dt_, args.train_rays, False, tsteps, True)
         train[dt_] = leg
+        if first_out is None:
+            first_out = tl.last           # what train_step returned in the headline pass's last timed step
         cx.log(f"train {dt_}: {leg['ms_per_step']:.2f} ms/step at {leg['rendering_samples_per_step']:.0f} samples")
     first = train[dtypes[0]]
     train.update({k: first[k] for k in ("ms_per_step", "rays_per_step", "rendering_samples_per_step", "marched_samples_per_step", "roofline")})
@@ -669,6 +739,8 @@ def leg_train(cx, line):
         line.update({"metric": "train-step ms", "value": train["ms_per_step"], "unit": "ms", "higher_is_better": False,
                      "ms_per_step": train["ms_per_step"], "dtype": dtypes[0]})
         line["config"]["workload"] = train["workload"]
+        if cx.dumping():
+            cx.outputs = {k: np.array([float(v)]) for k, v in first_out.items() if v is not None}
 
 
 def leg_config2(cx, line):
@@ -681,6 +753,7 @@ def leg_config2(cx, line):
     leg = RenderLeg(cx, tl.field0, tl.est0, tl.scene["poses"][[(5 * k + cx.rank) % 40 for k in range(8)]], w, h, focal)
     V = 8
     dt, samples = leg.run(V, args.steps, args.warmup, False, n_split=2)
+    c2_outputs = leg.take_last()
     c2 = {"workload": "BASELINE config 2: scene 102344250 (trained stand-in), hash-grid 16x4 T=2^19 + base MLP 64x4 + 64x2 heads, 256x256 RGB+depth+29-class views"}
     c2["render"] = {"ms_per_step": 1e3 * dt / args.steps, "views_per_step": V, "ms_per_view": 1e3 * dt / args.steps / V, "rays_per_s": w * h * V * cx.world * args.steps / dt,
                     "samples_per_ray": samples / (w * h * V * args.steps), "samples_per_s": samples * cx.world / dt}
@@ -701,6 +774,7 @@ def leg_config2(cx, line):
     if not (cx.want("render800") or cx.want("train")):
         line.update({"value": c2["render"]["rays_per_s"], "ms_per_step": c2["render"]["ms_per_step"], "metric": "rendered rays/sec (RGB+depth+semantic, 256x256)"})
         line["config"]["workload"] = c2["workload"]
+        cx.outputs = c2_outputs
         if "roofline" in c2["render"]:
             line["roofline"] = c2["render"]["roofline"]
 
@@ -740,7 +814,9 @@ def leg_score256(cx, line):
         t_parts["compute"] += t1 - t0; t_parts["gather"] += t2 - t1; t_parts["n"] += 1
     ssteps = max(3, min(args.steps, 5))
     cx.log("score256: timed pass")
-    dt_s = cx.timed(sstep, ssteps, 1, False)
+    last = {}
+    dt_s = cx.timed(sstep, ssteps, 1, False, lambda r: last.update(r=r))
+    last_terms, last_score = last.pop("r")
     cx.log(f"score256: {1e3 * dt_s / ssteps:.2f} ms/pass")
     terms, score = sstep(0)
     evaluated = float(sum(int(t[1]) for t in RD.LAST_SCORE_TOTALS))          # this rank's share of the views, all members
@@ -793,6 +869,8 @@ def leg_score256(cx, line):
     if not (cx.want("render800") or cx.want("train") or cx.want("config2")):
         line.update({"metric": "candidate-view scoring rays/s", "value": sc["rays_per_s"], "ms_per_step": sc["ms_per_pass"], "scaling": "strong"})
         line["config"]["workload"] = sc["workload"]
+        if cx.dumping():
+            cx.outputs = {"terms": last_terms.cpu().numpy(), "score": np.array([float(last_score)])}
 
 
 def trained_scene(scene, f, e):
@@ -832,17 +910,23 @@ def main():
     if cx.rank == 0:
         if cx.standin_info:
             line["config"]["standin_training"] = cx.standin_info
-        if cx.world == 1 and not args.no_cpu_baseline and headline_scene is not None and args.weights == "trained":
+        if args.dump_outputs is not None:
+            if cx.outputs is None:
+                raise SystemExit("--dump-outputs: the headline leg kept no outputs")
+            nbytes = write_outputs(args.dump_outputs, cx.outputs)
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": nbytes, "arrays": {k: list(np.shape(v)) for k, v in cx.outputs.items()}}
+            cx.log(f"outputs of the last timed step: {len(cx.outputs)} arrays, {nbytes / 1e6:.1f} MB -> {args.dump_outputs}")
+            cx.outputs = None
+        if args.full and cx.world == 1 and not args.no_cpu_baseline and headline_scene is not None and args.weights == "trained":
             scene529, field, est, poses, (width, height, focal) = headline_scene
             cx.log("cpu baseline + bench parity")
             line["cpu_baseline"], line["bench_parity"] = cpu_baseline_and_parity(trained_scene(scene529, field, est), poses[0], width, height, focal, field, est, cx.dev)
             cx.log(f"cpu baseline {line['cpu_baseline']['value']:.0f} rays/s; bench parity ok = {line['bench_parity']['ok']}")
             if not line["bench_parity"]["ok"]:
                 rc = 3
-            if args.full:
-                sys.path.insert(0, os.path.join(REPO, "tools"))
-                import bench_extra as X
-                X.cpu_extras(cx, line, trained_scene(scene529, field, est), poses[0], width, height, focal)
+            sys.path.insert(0, os.path.join(REPO, "tools"))
+            import bench_extra as X
+            X.cpu_extras(cx, line, trained_scene(scene529, field, est), poses[0], width, height, focal)
         line["bench_seconds"] = time.perf_counter() - T0
         detail_file = args.detail_file
         try:

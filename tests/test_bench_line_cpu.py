@@ -58,3 +58,30 @@ def test_cli_defaults_finish_within_minutes_and_flags_exist():
     assert a.gpus == 1 and a.steps == 10 and a.warmup == 3 and a.workload == "all" and not a.full
     a = bench.parse(["--gpus", "8", "--steps", "5", "--warmup", "2", "--workload", "config2", "--full"])
     assert (a.gpus, a.steps, a.warmup, a.workload, a.full) == (8, 5, 2, "config2", True)
+
+
+def test_dump_outputs_are_a_fixed_sample_within_the_size_limit(tmp_path):
+    """--dump-outputs: the same rays in every run with the same arguments, float32 / float64 files only, < 64 MB for the largest render (8 views of 800x800)."""
+    import numpy as np
+    import torch
+    n = 8 * 800 * 800
+    rows = bench.dump_rows(n)
+    assert np.array_equal(rows, bench.dump_rows(n)) and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(bench.dump_rows(1000), np.arange(1000))
+    r = {"rgb": torch.rand(n, 3), "acc": torch.rand(n, 1), "depth": torch.rand(n, 1), "sem": torch.rand(n, 29), "total": torch.tensor([3, 5])}
+    out = bench.render_outputs(r)
+    nbytes = bench.write_outputs(str(tmp_path), out)
+    assert nbytes <= bench.DUMP_MAX_BYTES
+    for k in ("rgb", "acc", "depth", "sem", "rows", "total_samples"):
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+    np.testing.assert_array_equal(np.load(tmp_path / "sem.npy"), r["sem"].numpy()[rows])
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+
+
+def test_dump_outputs_flag():
+    assert bench.parse([]).dump_outputs is None
+    assert bench.parse(["--dump-outputs", "out", "--full"]).dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

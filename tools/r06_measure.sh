@@ -6,7 +6,7 @@ out=gpurun_out/r06; mkdir -p $out
 what="${*:-tests bench prof}"
 has() { [[ " $what " == *" $1 "* ]]; }
 if has tests; then timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -3 > $out/pytest_gpu.txt; cat $out/pytest_gpu.txt; fi
-if has bench; then timeout 900 python bench.py --detail-file $out/bench_detail.json 2> $out/bench.err > $out/bench_stdout.txt; echo "bench rc $?"; tail -1 $out/bench_stdout.txt > $out/bench_line.json; wc -c $out/bench_line.json; grep "^\[bench" $out/bench.err | tail -25; fi
+if has bench; then timeout 900 python bench.py --full --detail-file $out/bench_detail.json 2> $out/bench.err > $out/bench_stdout.txt; echo "bench rc $?"; tail -1 $out/bench_stdout.txt > $out/bench_line.json; wc -c $out/bench_line.json; grep "^\[bench" $out/bench.err | tail -25; fi
 if has benchfull; then timeout 1500 python bench.py --full --detail-file $out/bench_detail_full.json 2> $out/bench_full.err > $out/bench_full_stdout.txt; echo "bench --full rc $?"; fi
 stats() {   # stats <tag> <bench args...>: rocprofv3 kernel stats of one workload
   tag=$1; shift

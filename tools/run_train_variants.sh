@@ -1,8 +1,8 @@
 #!/bin/bash
-# tools/run_train_variants.sh <name>...  train workload per-kernel times with each gpurun_exp/lib_<name>.so (128x2-only builds)
+# tools/run_train_variants.sh <name>...  train workload per-kernel times with each build/variants/lib_<name>.so (128x2-only builds)
 cd "$(dirname "$0")/.."
 for name in "$@"; do
-  MNF_LIB_PATH=$PWD/gpurun_exp/lib_$name.so timeout 300 python bench.py --workload train --no-cpu-baseline --steps 20 --train-dtypes f16 --detail-file /tmp/detail_$name.json > /dev/null 2>&1
+  MNF_LIB_PATH=$PWD/build/variants/lib_$name.so timeout 300 python bench.py --workload train --no-cpu-baseline --steps 20 --train-dtypes f16 --detail-file /tmp/detail_$name.json > /dev/null 2>&1
   python - $name <<'PY'
 import json, sys
 d = json.load(open(f"/tmp/detail_{sys.argv[1]}.json")); t = d["train"]["f16"]; y = d["train_refyaml"]

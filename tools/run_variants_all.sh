@@ -1,10 +1,11 @@
 #!/bin/bash
-# tools/run_variants_all.sh <name>...: headline legs (render800, train, score256) with each gpurun_exp/lib_<name>.so (128x2 only builds), two alternations; one line per run
+# tools/run_variants_all.sh <name>...: headline legs (render800, train, score256) with each build/variants/lib_<name>.so (128x2 only builds), two alternations; one line per run
 cd "$(dirname "$0")/.."
 for rep in 1 2; do
 for name in "$@"; do
   for wl in render800 train score256; do
-  MNF_LIB_PATH=$PWD/gpurun_exp/lib_$name.so timeout 600 python bench.py --workload $wl --no-cpu-baseline --no-kernel-timing --train-dtypes f16 --detail-file /tmp/detail_$name.json 2>/dev/null | tail -1 \
+  full=; [ $wl = render800 ] && full=--full      # the one-view pass of the render leg (views1) runs with --full
+  MNF_LIB_PATH=$PWD/build/variants/lib_$name.so timeout 600 python bench.py --workload $wl $full --no-cpu-baseline --no-kernel-timing --train-dtypes f16 --detail-file /tmp/detail_$name.json 2>/dev/null | tail -1 \
    | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for rep in 1 2; do
 for name in "$@"; do
-  MNF_LIB_PATH=$PWD/gpurun_exp/lib_$name.so timeout 300 python bench.py --workload render800 --no-cpu-baseline 2>/dev/null \
+  MNF_LIB_PATH=$PWD/build/variants/lib_$name.so timeout 300 python bench.py --workload render800 --no-cpu-baseline --full 2>/dev/null \
    | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d.get('roofline',{})

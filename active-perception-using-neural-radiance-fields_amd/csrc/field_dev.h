@@ -231,12 +231,13 @@ __device__ __forceinline__ void dense_out(const half8 *__restrict__ w_lds, int l
     }
 }
 
-// tcnn-faithful hand-over: the three networks' outputs rounded to fp16 and widened again (`.to(x)` in ngp.py:181-220)
+// tcnn-faithful hand-over: the three networks' outputs rounded to fp16 and widened again (`.to(x)` in ngp.py:181-220).  fp16 in
+// both builds: through tab_t, not half_t (which is bf16 under MNF_BF16 and would keep only 8 significand bits)
 __device__ __forceinline__ void round_outputs_fp16(f32x16 (&o)[CT]) {
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) o[ct][i] = (float)(half_t)o[ct][i];
+        for (int i = 0; i < 16; ++i) o[ct][i] = (float)(tab_t)o[ct][i];
 }
 
 // Lane l (sample A = column l of tile 0) and lane l+32 (sample B = column l of tile 1) each hold all 16

@@ -31,7 +31,9 @@ what tiny-cuda-nn hands back (the product's `tcnn_output_rounding=True` / `mnf_f
 ``precision="bf16"`` is the product's `mfma_bf16` mode (BASELINE config 5): weights, MLP inputs and hidden
 activations rounded to bfloat16 instead of fp16, hash table still fp16, fp32 accumulation and outputs.
 tcnn's fp16 ACCUMULATION inside a layer is not emulated (its summation order is not part of any published
-contract).  ``precision="f32"`` does no rounding.
+contract).  ``precision="f32"`` does no rounding.  ``output_rounding`` decouples the fp16 hand-over from the operand precision:
+``None`` (default) rounds the outputs only under ``precision="tcnn"``; ``True`` rounds them to fp16 under any precision (``"bf16"`` +
+``True`` is the product's `mfma_bf16=1, output_fp16=1`), ``False`` never.
 """
 import math
 from dataclasses import dataclass, field as dc_field
@@ -148,7 +150,7 @@ class OracleField:
     """forward / query_density with the ngp.py call surface, torch CPU fp32."""
 
     def __init__(self, cfg: FieldConfig, params: Dict[str, np.ndarray], precision: str = "f16", requires_grad: bool = False,
-                 blend: str = "f32", accum: str = "whole"):
+                 blend: str = "f32", accum: str = "whole", output_rounding: Optional[bool] = None):
         """blend: precision of the 8-corner interpolation of a hash level.  "f32" (default): fp32 weight x fp16 entry summed in fp32 (one rounding
         when the feature enters the network).  "f16": tiny-cuda-nn's published kernel with T = __half (grid.h `kernel_grid`): the weight is cast to
         half and `result = fma((T)weight, value, result)` runs in half precision, corners in index order.  Which of the two the reference's
@@ -162,6 +164,8 @@ class OracleField:
         # (tests/test_oracle_noise_floor_cpu.py, bench_parity.noise_floor): what two faithful implementations may differ by.
         self.accum = accum
         self.precision = precision
+        # every network output rounded to fp16 (tcnn's hand-over): implied by "tcnn", or asked for explicitly with any operand precision
+        self.output_rounding = precision == "tcnn" if output_rounding is None else bool(output_rounding)
         self.num_semantic_classes = cfg.num_semantic_classes
         self.aabb = torch.tensor(cfg.aabb, dtype=torch.float32)
         self.levels, self.table_entries = grid_levels(cfg)
@@ -266,8 +270,9 @@ class OracleField:
         for w in ws[:-1]:
             h = _q(torch.relu(self._mm(h, w)), self.precision)
         out = self._mm(h, ws[-1])
-        # "tcnn": the network hands its outputs over in fp16 (ngp.py:181-200, :210-220 widen them with `.to(x)`)
-        return _q(out, "f16") if self.precision == "tcnn" else out
+        # output_rounding: the network hands its outputs over in fp16 (ngp.py:181-200, :210-220 widen them with `.to(x)`) -- fp16 whatever
+        # the operand precision
+        return _q(out, "f16") if self.output_rounding else out
 
     # ---- ngp.py call surface ---------------------------------------------------------
     def _base(self, positions: torch.Tensor):

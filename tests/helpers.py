@@ -8,11 +8,12 @@ from apnrf_amd import synthetic as S  # noqa: F401
 from apnrf_amd.scenes import RENDER_KW, hip_estimator, hip_field, make_scene  # noqa: F401
 
 
-def oracle_field(scene, precision="f16", requires_grad=False):
+def oracle_field(scene, precision="f16", requires_grad=False, **kw):
+    """kw: OracleField's mode switches (blend, accum, output_rounding)"""
     from oracle.field import FieldConfig, OracleField
     cfg = FieldConfig(aabb=tuple(float(x) for x in scene["aabb"]), neurons=scene["neurons"], layers=scene["layers"],
                       num_semantic_classes=scene["C"], log2_hashmap_size=scene["log2_hashmap_size"])
-    return OracleField(cfg, scene["params"], precision, requires_grad)
+    return OracleField(cfg, scene["params"], precision, requires_grad, **kw)
 
 
 def view_rays(scene, pose_idx, width=640, height=640, h=32, w=32):

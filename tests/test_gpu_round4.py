@@ -120,7 +120,9 @@ def test_config3_trained_scene_sparse_parity_at_1e3():
     """BASELINE config 3 as bench.py renders it: the 2000-iteration stand-in of scene 102344529, an 800x800 view, a 24x24
     linspace sub-sample of its rays rendered stand-alone on the GPU and through the oracle (same call shape, hence the same round schedule):
     rgb / acc / depth within 1e-3 absolute, class logits within 1e-3 x max(1, |logit|) — both forms reported — with the tie budget (<= 2 rays up
-    to 5e-2: a sample on the alpha-threshold edge), PSNR > 50 dB, evaluated-sample totals within 0.2 %."""
+    to 5e-2: a sample on the alpha-threshold edge), PSNR > 50 dB, evaluated-sample totals within 0.2 %.
+    The same checks run a second time with the trained state in the tcnn-faithful mode (`tcnn_output_rounding=True`: every network output handed
+    over in fp16) against the oracle's precision="tcnn", its noise floor taken from the "tcnn" oracle with permuted accumulation."""
     from apnrf_amd import render as RD
     from apnrf_amd import standin as SI
     from oracle import render as R
@@ -131,35 +133,44 @@ def test_config3_trained_scene_sparse_parity_at_1e3():
                       log2_hashmap_size=sc["log2_hashmap_size"])
     params = {"mlp_base": field.mlp_base.params.detach().cpu().numpy(), "mlp_head": field.mlp_head.params.detach().cpu().numpy(),
               "mlp_sem": field.mlp_sem.params.detach().cpu().numpy()}
-    orc = OracleField(cfg, params, "f16", False)
-    orc_perm = OracleField(cfg, params, "f16", False, accum="k16_reversed")       # same operands, another fp32 accumulation order: the noise floor
+    field_tcnn = H.hip_field(dict(sc, params=params), tcnn_output_rounding=True)       # the same trained state, fp16 hand-over
     occ = est.binaries.cpu().numpy()
     S_, width = 24, 800
     focal = 0.5 * width / np.tan(np.pi / 4)
     bk = torch.zeros(3)
     worst_all = []
-    for pose in (0, 15):
-        idx = R.subsample_indices(width * width, S_ * S_)
-        o, d = R.generate_image_rays(R.pose_to_c2w(sc["poses"][pose]), width, width, focal, idx)
-        ref = R.render_test(1024, orc, occ, sc["aabb"][None], o, d, render_bkgd=bk, **H.RENDER_KW)
-        got = RD.render_views(field, est, o.to(DEV), d.to(DEV), S_ * S_, 1024, render_bkgd=bk, **H.RENDER_KW)
-        errs, sem_scaled, sem_mag = _render_errors(got, ref, S_ * S_)
-        ref2 = R.render_test(1024, orc_perm, occ, sc["aabb"][None], o, d, render_bkgd=bk, **H.RENDER_KW)
-        floor = (ref2["sem"] - ref["sem"]).abs().max(dim=1).values.numpy()
-        print(f"config 3 pose {pose}: NOISE FLOOR of the composited logits (oracle vs oracle, permuted accumulation): abs {floor.max():.2e} "
-              f"({int((floor > 1e-3).sum())} rays above 1e-3), relative to the ray's largest |logit| {(floor / sem_mag).max():.2e}; "
-              f"HIP vs oracle: abs {errs['sem'].max():.2e}, relative {(errs['sem'] / sem_mag).max():.2e}")
-        assert (errs["sem"] / sem_mag).max() <= 3.0 * max((floor / sem_mag).max(), 1e-4)      # the product sits within 3x the oracle's own floor
-        worst = np.max(np.stack([errs["rgb"], errs["acc"], errs["depth"], sem_scaled]), axis=0)
-        tie = worst > 1e-3
-        mse = float(((got["rgb"].cpu() - ref["rgb"]) ** 2).mean())
-        print(f"config 3 pose {pose}: max abs rgb {errs['rgb'][~tie].max():.2e} acc {errs['acc'][~tie].max():.2e} depth {errs['depth'][~tie].max():.2e} | sem scaled "
-              f"{sem_scaled[~tie].max():.2e}, unscaled {errs['sem'].max():.2e} ({int((errs['sem'] > 1e-3).sum())} rays above 1e-3 absolute, largest |logit| {sem_mag.max():.1f}) | "
-              f"tie rays {int(tie.sum())} | PSNR {10 * np.log10(1.0 / max(mse, 1e-20)):.1f} dB | samples {int(got['total'][0])} vs {ref['total_samples']}")
-        assert worst[~tie].max() <= 1e-3 and tie.sum() <= 2 and (not tie.any() or worst[tie].max() <= 5e-2)
-        assert 10 * np.log10(1.0 / max(mse, 1e-20)) > 50
-        assert abs(int(got["total"][0]) - ref["total_samples"]) <= max(4, 2e-3 * ref["total_samples"])
-        worst_all.append(worst)
+    for mode, hip, prec in (("f16", field, "f16"), ("tcnn", field_tcnn, "tcnn")):
+        orc = OracleField(cfg, params, prec, False)
+        orc_perm = OracleField(cfg, params, prec, False, accum="k16_reversed")     # same operands, another fp32 accumulation order: the noise floor
+        outs = []
+        for pose in (0, 15):
+            idx = R.subsample_indices(width * width, S_ * S_)
+            o, d = R.generate_image_rays(R.pose_to_c2w(sc["poses"][pose]), width, width, focal, idx)
+            ref = R.render_test(1024, orc, occ, sc["aabb"][None], o, d, render_bkgd=bk, **H.RENDER_KW)
+            got = RD.render_views(hip, est, o.to(DEV), d.to(DEV), S_ * S_, 1024, render_bkgd=bk, **H.RENDER_KW)
+            outs.append(got["sem"])
+            errs, sem_scaled, sem_mag = _render_errors(got, ref, S_ * S_)
+            ref2 = R.render_test(1024, orc_perm, occ, sc["aabb"][None], o, d, render_bkgd=bk, **H.RENDER_KW)
+            floor = (ref2["sem"] - ref["sem"]).abs().max(dim=1).values.numpy()
+            print(f"config 3 [{mode}] pose {pose}: NOISE FLOOR of the composited logits (oracle vs oracle, permuted accumulation): abs {floor.max():.2e} "
+                  f"({int((floor > 1e-3).sum())} rays above 1e-3), relative to the ray's largest |logit| {(floor / sem_mag).max():.2e}; "
+                  f"HIP vs oracle: abs {errs['sem'].max():.2e}, relative {(errs['sem'] / sem_mag).max():.2e}")
+            assert (errs["sem"] / sem_mag).max() <= 3.0 * max((floor / sem_mag).max(), 1e-4)      # the product sits within 3x the oracle's own floor
+            worst = np.max(np.stack([errs["rgb"], errs["acc"], errs["depth"], sem_scaled]), axis=0)
+            tie = worst > 1e-3
+            mse = float(((got["rgb"].cpu() - ref["rgb"]) ** 2).mean())
+            print(f"config 3 [{mode}] pose {pose}: max abs rgb {errs['rgb'][~tie].max():.2e} acc {errs['acc'][~tie].max():.2e} depth {errs['depth'][~tie].max():.2e} | "
+                  f"sem scaled {sem_scaled[~tie].max():.2e}, unscaled {errs['sem'].max():.2e} ({int((errs['sem'] > 1e-3).sum())} rays above 1e-3 absolute, "
+                  f"largest |logit| {sem_mag.max():.1f}) | tie rays {int(tie.sum())} | PSNR {10 * np.log10(1.0 / max(mse, 1e-20)):.1f} dB | "
+                  f"samples {int(got['total'][0])} vs {ref['total_samples']}")
+            assert worst[~tie].max() <= 1e-3 and tie.sum() <= 2 and (not tie.any() or worst[tie].max() <= 5e-2)
+            assert 10 * np.log10(1.0 / max(mse, 1e-20)) > 50
+            assert abs(int(got["total"][0]) - ref["total_samples"]) <= max(4, 2e-3 * ref["total_samples"])
+            worst_all.append(worst)
+        if mode == "f16":
+            outs_f16 = outs
+        else:                                                                       # the fp16 hand-over is really on in the second pass
+            assert not all(torch.equal(a, b) for a, b in zip(outs, outs_f16))
 
 
 def test_config4_full_size_scoring_properties_and_oracle_views():

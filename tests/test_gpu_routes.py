@@ -19,12 +19,14 @@ def _cu(a):
 
 
 # ------------------------------------------------------------------ field backward (csrc/train.hip dgrad_kernel<W,NH>, wgrad, scatter)
-def _backward_vs_oracle(neurons, layers, C, lh, n, seed):
+def _backward_vs_oracle(neurons, layers, C, lh, n, seed, field_kw=None, oracle_kw=None, rel=2e-2, cos=0.9995, fwd_atol=1e-3, flip_kw=None):
     """test_field_backward_matches_oracle's comparison at one shape: train forward == inference forward, every gradient group within 2e-2 relative L2
-    and cosine > 0.9995, untouched table entries exactly zero.  Returns (hip, orc, n_mlp) for further checks."""
+    and cosine > 0.9995, untouched table entries exactly zero.  Returns (hip, orc, n_mlp) for further checks.
+    field_kw / oracle_kw: the field's precision mode (hip_field keywords) and the oracle of the same mode (oracle_field keywords); rel / cos / fwd_atol: that
+    mode's bars.  flip_kw: hip_field keywords of the same route with the mode switch flipped, whose gradients must differ (the switch is really on)."""
     sc = H.make_scene(neurons=neurons, layers=layers, C=C, log2_hashmap_size=lh, head_gain=2.0)
-    hip = H.hip_field(sc).train()
-    orc = H.oracle_field(sc, requires_grad=True)
+    hip = H.hip_field(sc, **(field_kw or {})).train()
+    orc = H.oracle_field(sc, requires_grad=True, **(oracle_kw or {}))
     rng = np.random.default_rng(seed)
     a = sc["aabb"]
     pos = (rng.random((n, 3)) * (a[3:] - a[:3]) * 0.98 + a[:3] + 0.01 * (a[3:] - a[:3])).astype(np.float32)
@@ -37,22 +39,28 @@ def _backward_vs_oracle(neurons, layers, C, lh, n, seed):
     assert rgb.requires_grad and sem.requires_grad and sem.shape == (n, C)
     torch.autograd.backward([rgb, sigma, sem], [_cu(g_rgb), _cu(g_sig), _cu(g_sem)])
     r_rgb, r_sigma, r_sem = orc(torch.from_numpy(pos), torch.from_numpy(d))
-    np.testing.assert_allclose(rgb.detach().cpu().numpy()[5:], r_rgb.detach().numpy()[5:], atol=1e-3)       # train forward == inference forward
+    np.testing.assert_allclose(rgb.detach().cpu().numpy()[5:], r_rgb.detach().numpy()[5:], atol=fwd_atol)  # train forward == inference forward
     torch.autograd.backward([r_rgb, r_sigma, r_sem], [torch.from_numpy(g_rgb), torch.from_numpy(g_sig), torch.from_numpy(g_sem)])
     n_mlp = sum(o * i for o, i in orc.shapes["base"])
-    _grad_close(hip.mlp_base.params.grad[:n_mlp], orc.p_base.grad[:n_mlp], "base mlp")
-    _grad_close(hip.mlp_base.params.grad[n_mlp:], orc.p_base.grad[n_mlp:], "hash table")
-    _grad_close(hip.mlp_head.params.grad, orc.p_head.grad, "rgb head")
-    _grad_close(hip.mlp_sem.params.grad, orc.p_sem.grad, "sem head")
+    _grad_close(hip.mlp_base.params.grad[:n_mlp], orc.p_base.grad[:n_mlp], "base mlp", rel=rel, cos=cos)
+    _grad_close(hip.mlp_base.params.grad[n_mlp:], orc.p_base.grad[n_mlp:], "hash table", rel=rel, cos=cos)
+    _grad_close(hip.mlp_head.params.grad, orc.p_head.grad, "rgb head", rel=rel, cos=cos)
+    _grad_close(hip.mlp_sem.params.grad, orc.p_sem.grad, "sem head", rel=rel, cos=cos)
     # the semantic output layer class by class (rows of [ceil16(C), neurons / 2]): a wrong row at the padding edge is diluted in the group
     # total; the padding rows get exactly zero
     pad, wh = orc.cfg.sem_out_pad, neurons // 2
     got_w, want_w = hip.mlp_sem.params.grad[-pad * wh:].view(pad, wh), orc.p_sem.grad[-pad * wh:].view(pad, wh)
     for c in range(C):
-        _grad_close(got_w[c], want_w[c], f"sem output row {c} of {C}")
+        _grad_close(got_w[c], want_w[c], f"sem output row {c} of {C}", rel=rel, cos=cos)
     assert bool((got_w[C:] == 0).all()) and bool((want_w[C:] == 0).all())
     untouched = (orc.p_base.grad[n_mlp:] == 0).numpy()
     assert (hip.mlp_base.params.grad[n_mlp:].cpu().numpy()[untouched] == 0).all()
+    if flip_kw is not None:
+        other = H.hip_field(sc, **flip_kw).train()
+        torch.autograd.backward(list(other(_cu(pos), _cu(d))), [_cu(g_rgb), _cu(g_sig), _cu(g_sem)])
+        for a, b in zip(hip.parameters(), other.parameters()):
+            if a.numel():
+                assert not torch.equal(a.grad, b.grad), "the mode switch does not change the backward"
     return hip, orc, n_mlp
 
 
@@ -81,14 +89,16 @@ def test_field_backward_scatter_routes(lh, n):
 
 
 # ------------------------------------------------------------------ fused train step (mnf_train_step) of every shape
-def _fused_step_vs_oracle(neurons, layers, C, lh, hw, min_samples):
+def _fused_step_vs_oracle(neurons, layers, C, lh, hw, min_samples, field_kw=None, oracle_kw=None, loss_rtol=1e-4, rel=3e-2, cos=0.999, flip_kw=None):
     """test_config2_fused_train_step_64x4_matches_oracle_autograd's comparison at one shape: one `train_step(fused=True)` against the oracle's
-    autograd on the same batch — sample count equal, loss to 1e-4 relative, every gradient group within the train-step tolerance."""
+    autograd on the same batch — sample count equal, loss to 1e-4 relative, every gradient group within the train-step tolerance.
+    field_kw / oracle_kw: the field's precision mode and the oracle of the same mode; loss_rtol / rel / cos: that mode's bars; flip_kw: hip_field keywords of
+    the same step with the mode switch flipped, whose gradients must differ (the switch is really on)."""
     from apnrf_amd import render as RD
     from apnrf_amd.optim import FusedAdam
     from oracle import render as R
     sc = H.make_scene("102344250", neurons=neurons, layers=layers, C=C, log2_hashmap_size=lh)
-    hip, orc, est = H.hip_field(sc), H.oracle_field(sc, requires_grad=True), H.hip_estimator(sc)
+    hip, orc, est = H.hip_field(sc, **(field_kw or {})), H.oracle_field(sc, requires_grad=True, **(oracle_kw or {})), H.hip_estimator(sc)
     o, d = H.view_rays(sc, 4, width=256, height=256, h=hw, w=hw)
     n = o.shape[0]
     pix, dep, lab = _targets(n, C)
@@ -101,18 +111,28 @@ def _fused_step_vs_oracle(neurons, layers, C, lh, hw, min_samples):
                          render_step_size=1e-3, cone_angle=0.004, alpha_thre=0.01)
     r_loss = _loss(ref[0], ref[2], ref[3], pix, dep, lab)
     r_loss.backward()
+    if field_kw:
+        print(f"fused step {neurons}x{layers} C={C} T=2^{lh} {field_kw}: samples {out['n_rendering_samples']} vs oracle {ref[4]}, "
+              f"loss rel err {abs(float(out['loss']) / float(r_loss.detach()) - 1.0):.2e}")
     assert ref[4] == out["n_rendering_samples"]
-    np.testing.assert_allclose(float(out["loss"]), float(r_loss.detach()), rtol=1e-4)
+    np.testing.assert_allclose(float(out["loss"]), float(r_loss.detach()), rtol=loss_rtol)
     if C > 1:
-        _check_grads(hip, orc)
+        _check_grads(hip, orc, rel=rel, cos=cos)
     else:
         # one class: the cross-entropy is identically zero, so is the semantic head's gradient (oracle: exactly) — the other groups as usual
         assert float(orc.p_sem.grad.abs().max()) == 0.0
         assert float(hip.mlp_sem.params.grad.abs().max()) <= 1e-6 * float(hip.mlp_head.params.grad.abs().max())
         n_mlp = sum(o_ * i_ for o_, i_ in orc.shapes["base"])
-        _grad_close(hip.mlp_base.params.grad[:n_mlp], orc.p_base.grad[:n_mlp], "base mlp", rel=3e-2, cos=0.999)
-        _grad_close(hip.mlp_base.params.grad[n_mlp:], orc.p_base.grad[n_mlp:], "hash table", rel=3e-2, cos=0.999)
-        _grad_close(hip.mlp_head.params.grad, orc.p_head.grad, "rgb head", rel=3e-2, cos=0.999)
+        _grad_close(hip.mlp_base.params.grad[:n_mlp], orc.p_base.grad[:n_mlp], "base mlp", rel=rel, cos=cos)
+        _grad_close(hip.mlp_base.params.grad[n_mlp:], orc.p_base.grad[n_mlp:], "hash table", rel=rel, cos=cos)
+        _grad_close(hip.mlp_head.params.grad, orc.p_head.grad, "rgb head", rel=rel, cos=cos)
+    if flip_kw is not None:
+        other = H.hip_field(sc, **flip_kw)
+        opt2 = FusedAdam(other.parameters(), lr=1e-3, eps=1e-15).bind_field(other)
+        out2 = RD.train_step(other, H.hip_estimator(sc), opt2, rays, pix.to(DEV), dep.to(DEV), lab.to(DEV), bk.to(DEV), step=1, fused=True, sync=True,
+                             stratified=False, **H.RENDER_KW)
+        assert not out2["skipped"]
+        assert not torch.equal(hip.mlp_base.params.grad, other.mlp_base.params.grad), "the mode switch does not change the fused step"
     return out
 
 

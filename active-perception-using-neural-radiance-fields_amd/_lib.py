@@ -160,6 +160,9 @@ SIGNATURES = {
     "mnf_profile_end": (c_int32, [POINTER(c_double), POINTER(c_int64)]),
     "mnf_profile_query": (c_int32, [c_char_p, POINTER(c_double), POINTER(c_int64)]),
     "mnf_score_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mnf_eval_views_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32]),
+    "mnf_eval_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

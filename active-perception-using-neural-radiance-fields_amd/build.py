@@ -33,6 +33,7 @@ SOURCES = {
     "occupancy.hip": ["-ffp-contract=off"],
     "vanilla.hip": [],
     "trainstep.hip": ["-ffp-contract=off"],
+    "eval.hip": [],
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
 }

@@ -1,0 +1,237 @@
+// Held-out view evaluation on the device (gfx950):
+//   mnf_eval_views  <- scripts/pipeline.py:550-613 (per test image: F.cross_entropy on the [H*W, C] logits, F.mse_loss on rgb and
+//                      depth, PSNR, each read back with .item(), every plane copied to the host) and :1011 (np.argmax over a float64
+//                      [H, W, C] host stack for the label image)
+//
+// One pass over the finished renders of V views of P pixels.  Ground truth is read straight from the dataset's storage (u8 images,
+// f32 / f16 depths, i64 / u8 labels: the two layouts of gather_pixels_kernel, march.hip); no fp32 ground-truth image is written.
+//
+// Work split: a view's pixels are cut into tiles of `tp` pixels, a view's tiles into `nb` contiguous runs, one workgroup per (run, view).
+// A tile's tp * C logits are one contiguous piece of `sem`: the workgroup copies it to LDS with 16-byte loads per lane (scalar loads up
+// to the first 16-byte boundary and after the last), then lane t works on pixel t out of LDS, whose row stride C | 1 is odd, so the 32
+// lanes of an LDS access hit 32 different banks.  Per pixel (3 + 1 + C) * 4 bytes of render and 15 (u8 / f32 / i64) or 6 (u8 / f16 / u8)
+// bytes of ground truth are read, once.
+//
+// Sums are carried in double: per lane over its pixels, then a shuffle tree per wave, then the four waves in order, then ONE row of
+// partial sums per workgroup in the caller's workspace; eval_finish_kernel adds a view's rows in a fixed order.  No floating-point
+// atomic anywhere: the same inputs give the same bits.  The confusion matrix is counted with integer atomics (an LDS histogram per
+// workgroup for C <= 64, flushed with one 64-bit global atomic per non-zero cell; straight to global above that).
+#include "common.h"
+
+namespace mnf {
+namespace {
+
+constexpr int kEvalThreads = 256;
+constexpr int kEvalMaxBlocksPerView = 512;    // depends on P and C only: a view's sums do not depend on how many views share the call
+constexpr int kEvalStageBytes = 40960;        // LDS for a tile's logits; + 16 KB histogram + the reduction scratch stays under 64 KB
+constexpr int kEvalHistClasses = 64;          // C <= 64: per-workgroup LDS histogram (64 * 64 * 4 B = 16 KB)
+constexpr int kEvalPartials = 6;              // rgb squared error, depth squared error, cross-entropy, correct, valid, invalid
+
+struct EvalPlan { int tp; int64_t tiles; int nb; };
+
+inline bool eval_plan(int64_t n_pix, int32_t C, EvalPlan *pl) {
+    const int64_t cs = C | 1;
+    int64_t tp = kEvalStageBytes / (cs * 4);
+    if (tp < 1) return false;
+    if (tp > kEvalThreads) tp = kEvalThreads;
+    if (tp >= 4) tp &= ~(int64_t)3;           // tiles of a multiple of four pixels keep every tile of an aligned view 16-byte aligned
+    pl->tp = (int)tp;
+    pl->tiles = ceil_div(n_pix, tp);
+    pl->nb = (int)(pl->tiles < kEvalMaxBlocksPerView ? pl->tiles : kEvalMaxBlocksPerView);
+    return true;
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
+
+__global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
+    const float *__restrict__ rgb, const float *__restrict__ depth, const float *__restrict__ sem, int64_t P, int C, int tp, int64_t tiles,
+    int vec_ok, const uint8_t *__restrict__ images, const void *__restrict__ depths, int depth_f16, const void *__restrict__ sems, int sem_u8,
+    int64_t pixels_per_image, const int64_t *__restrict__ image_ids, const int64_t *__restrict__ pix_idx, double *__restrict__ partials,
+    unsigned long long *__restrict__ confusion, uint8_t *__restrict__ pred_labels) {
+    extern __shared__ float stage[];                                 // [tp][C | 1]
+    __shared__ unsigned int hist[kEvalHistClasses * kEvalHistClasses];
+    __shared__ double red[kEvalThreads / 64][kEvalPartials];
+    const int tid = threadIdx.x, v = blockIdx.y, nb = gridDim.x, b = blockIdx.x;
+    const int Cs = C | 1;
+    const bool lds_hist = confusion && C <= kEvalHistClasses;
+    if (lds_hist) {
+        for (int i = tid; i < C * C; i += kEvalThreads) hist[i] = 0u;
+    }
+    const int64_t gt_base = image_ids[v] * pixels_per_image;
+    const int64_t t0 = tiles * b / nb, t1 = tiles * (b + 1) / nb;
+    double s_rgb = 0.0, s_dep = 0.0, s_ce = 0.0, n_ok = 0.0, n_valid = 0.0, n_bad = 0.0;
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t p0 = t * tp;
+        const int np = (int)(P - p0 < tp ? P - p0 : tp);
+        const int64_t e0 = ((int64_t)v * P + p0) * C;
+        const float *src = sem + e0;
+        const int n = np * C;
+        __syncthreads();                                             // the previous tile's rows are read; the histogram is zeroed
+        const int head = vec_ok ? min(n, (int)((4 - (e0 & 3)) & 3)) : n;
+        const int nvec = (n - head) >> 2;
+        if (Cs == C) {
+            for (int i = tid; i < head; i += kEvalThreads) stage[i] = src[i];
+            for (int q = tid; q < nvec; q += kEvalThreads) {
+                const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
+                float *dst = stage + head + 4 * q;
+                dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
+            }
+            for (int i = head + 4 * nvec + tid; i < n; i += kEvalThreads) stage[i] = src[i];
+        } else {
+            for (int i = tid; i < head; i += kEvalThreads) stage[(i / C) * Cs + i % C] = src[i];
+            for (int q = tid; q < nvec; q += kEvalThreads) {
+                const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
+                const float xs[4] = {x.x, x.y, x.z, x.w};
+                int e = head + 4 * q, p = e / C, c = e - p * C;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    stage[p * Cs + c] = xs[k];
+                    if (++c == C) { c = 0; ++p; }
+                }
+            }
+            for (int i = head + 4 * nvec + tid; i < n; i += kEvalThreads) stage[(i / C) * Cs + i % C] = src[i];
+        }
+        __syncthreads();
+        if (tid < np) {
+            const int64_t p = p0 + tid, i = (int64_t)v * P + p;
+            const int64_t g = gt_base + (pix_idx ? pix_idx[p] : p);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float gt = (float)images[3 * g + k] / 255.0f;  // gather_pixels_kernel's expression
+                const double d = (double)rgb[3 * i + k] - (double)gt;
+                s_rgb += d * d;
+            }
+            const float gd = depth_f16 ? (float)reinterpret_cast<const _Float16 *>(depths)[g] : reinterpret_cast<const float *>(depths)[g];
+            const double dd = (double)depth[i] - (double)gd;
+            s_dep += dd * dd;
+            const int64_t label = sem_u8 ? (int64_t)reinterpret_cast<const uint8_t *>(sems)[g] : reinterpret_cast<const int64_t *>(sems)[g];
+            // first maximal index; a NaN counts as the maximum (torch.argmax, np.argmax)
+            const float *row = stage + tid * Cs;
+            float best = row[0];
+            int arg = 0;
+            for (int c = 1; c < C; ++c) {
+                const float x = row[c];
+                if (x > best || (x != x && best == best)) { best = x; arg = c; }
+            }
+            if (pred_labels) pred_labels[i] = (uint8_t)arg;
+            if (label >= 0 && label < C) {
+                const double m = (double)best;
+                double se = 0.0;
+                for (int c = 0; c < C; ++c) se += exp((double)row[c] - m);
+                s_ce += (m + log(se)) - (double)row[label];
+                n_valid += 1.0;
+                n_ok += arg == (int)label ? 1.0 : 0.0;
+                if (lds_hist) atomicAdd(&hist[(int)label * C + arg], 1u);
+                else if (confusion) atomicAdd(&confusion[label * C + arg], 1ull);
+            } else {
+                n_bad += 1.0;
+            }
+        }
+    }
+    double part[kEvalPartials] = {s_rgb, s_dep, s_ce, n_ok, n_valid, n_bad};
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int k = 0; k < kEvalPartials; ++k) {
+        const double w = wave_sum(part[k]);
+        if (lane == 0) red[wave][k] = w;
+    }
+    __syncthreads();                                                 // also: every histogram count of this workgroup is in
+    if (tid < kEvalPartials) {
+        double s = red[0][tid];
+        for (int w = 1; w < kEvalThreads / 64; ++w) s += red[w][tid];
+        partials[((int64_t)v * nb + b) * kEvalPartials + tid] = s;
+    }
+    if (lds_hist) {
+        for (int i = tid; i < C * C; i += kEvalThreads) {
+            const unsigned int n = hist[i];
+            if (n) atomicAdd(&confusion[i], (unsigned long long)n);
+        }
+    }
+}
+
+// one wave per view: lane l adds rows l, l + 64, ... in order, then the shuffle tree
+__global__ void __launch_bounds__(64) eval_finish_kernel(const double *__restrict__ partials, int nb, int64_t P, double *__restrict__ metrics) {
+    const int v = blockIdx.x, lane = threadIdx.x;
+    double s[kEvalPartials];
+#pragma unroll
+    for (int k = 0; k < kEvalPartials; ++k) s[k] = 0.0;
+    for (int b = lane; b < nb; b += 64) {
+#pragma unroll
+        for (int k = 0; k < kEvalPartials; ++k) s[k] += partials[((int64_t)v * nb + b) * kEvalPartials + k];
+    }
+#pragma unroll
+    for (int k = 0; k < kEvalPartials; ++k) s[k] = wave_sum(s[k]);
+    if (lane == 0) {
+        double *m = metrics + (int64_t)v * 8;
+        const double mse = s[0] / (double)(3 * P);
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        m[0] = mse;
+        m[1] = -10.0 * log(mse) / log(10.0);                         // pipeline.py:601; +inf at mse 0
+        m[2] = s[1] / (double)P;
+        m[3] = s[4] > 0.0 ? s[2] / s[4] : nan;
+        m[4] = s[4] > 0.0 ? s[3] / s[4] : nan;
+        m[5] = s[4];
+        m[6] = s[5];
+        m[7] = 0.0;
+    }
+}
+
+}  // namespace
+}  // namespace mnf
+
+using namespace mnf;
+
+extern "C" int64_t mnf_eval_views_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes) {
+    EvalPlan pl;
+    if (n_views < 0 || n_pix <= 0 || n_classes <= 0 || !eval_plan(n_pix, n_classes, &pl)) return 0;
+    return (int64_t)n_views * pl.nb * kEvalPartials * (int64_t)sizeof(double);
+}
+
+extern "C" int mnf_eval_views(const float *rgb, const float *depth, const float *sem, int32_t n_views, int64_t n_pix, int32_t n_classes,
+                              const uint8_t *gt_images, const void *gt_depths, int32_t depth_is_f16, const void *gt_semantics, int32_t sem_is_u8,
+                              int64_t pixels_per_image, const int64_t *image_ids, const int64_t *pix_idx,
+                              double *metrics, int64_t *confusion, uint8_t *pred_labels,
+                              void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MNF_REQUIRE(n_views >= 0, "eval_views: n_views is negative (%d)", n_views);
+    MNF_REQUIRE(n_pix > 0, "eval_views: n_pix must be positive (got %lld)", (long long)n_pix);
+    MNF_REQUIRE(n_classes > 0, "eval_views: n_classes must be positive (got %d)", n_classes);
+    MNF_REQUIRE(!pred_labels || n_classes <= 256, "eval_views: pred_labels holds uint8 class ids and needs n_classes <= 256 (got %d)", n_classes);
+    MNF_REQUIRE(pixels_per_image > 0, "eval_views: pixels_per_image must be positive (got %lld)", (long long)pixels_per_image);
+    MNF_REQUIRE(pix_idx || n_pix <= pixels_per_image, "eval_views: n_pix (%lld) exceeds pixels_per_image (%lld) with no pix_idx", (long long)n_pix,
+                (long long)pixels_per_image);
+    if (n_views == 0) return MNF_OK;
+    MNF_REQUIRE(rgb, "eval_views: rgb is null");
+    MNF_REQUIRE(depth, "eval_views: depth is null");
+    MNF_REQUIRE(sem, "eval_views: sem is null");
+    MNF_REQUIRE(gt_images, "eval_views: gt_images is null");
+    MNF_REQUIRE(gt_depths, "eval_views: gt_depths is null");
+    MNF_REQUIRE(gt_semantics, "eval_views: gt_semantics is null");
+    MNF_REQUIRE(image_ids, "eval_views: image_ids is null");
+    MNF_REQUIRE(metrics, "eval_views: metrics is null");
+    MNF_REQUIRE(workspace, "eval_views: workspace is null");
+    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "eval_views: workspace must be 8-byte aligned");
+    EvalPlan pl;
+    if (!eval_plan(n_pix, n_classes, &pl)) {
+        set_error("eval_views: n_classes = %d is more than one LDS tile holds (%d)", n_classes, kEvalStageBytes / 4 - 1);
+        return MNF_ERR_UNSUPPORTED;
+    }
+    const int64_t need = (int64_t)n_views * pl.nb * kEvalPartials * (int64_t)sizeof(double);
+    MNF_REQUIRE(workspace_bytes >= need, "eval_views: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
+    MNF_REQUIRE(n_views <= 65535, "eval_views: at most 65535 views per call (got %d)", n_views);
+    hipStream_t s = as_stream(stream);
+    ProfScope prof("eval_views", s);
+    if (confusion) MNF_HIP(hipMemsetAsync(confusion, 0, (size_t)n_classes * n_classes * sizeof(int64_t), s));    // written, not accumulated into
+    const int vec_ok = (reinterpret_cast<uintptr_t>(sem) & 15) == 0;
+    const size_t lds = (size_t)pl.tp * (n_classes | 1) * sizeof(float);
+    hipLaunchKernelGGL(eval_views_kernel, dim3(pl.nb, n_views), dim3(kEvalThreads), lds, s, rgb, depth, sem, n_pix, n_classes, pl.tp, pl.tiles, vec_ok,
+                       gt_images, gt_depths, depth_is_f16, gt_semantics, sem_is_u8, pixels_per_image, image_ids, pix_idx,
+                       reinterpret_cast<double *>(workspace), reinterpret_cast<unsigned long long *>(confusion), pred_labels);
+    int rc = launch_status("eval_views_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(n_views), dim3(64), 0, s, reinterpret_cast<const double *>(workspace), pl.nb, n_pix, metrics);
+    return launch_status("eval_finish_kernel");
+}

@@ -1089,3 +1089,140 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
     L.launch(lib.mnf_score_poses, handles, bins, bits, M, res[0], res[1], res[2], (ctypes.c_float * len(grids[0][1]))(*grids[0][1]), L.ptr(c2w), V, width,
              height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(opts), L.ptr(terms), L.ptr(ws), nbytes)
     return terms, trajectory_score(terms)
+
+
+# ------------------------------------------------------------------ held-out view evaluation (pipeline.py:550-613, :650-656, :1011)
+EVAL_COLUMNS = ("rgb_mse", "psnr", "depth_mse", "sem_ce", "sem_acc", "n_valid", "n_invalid", "reserved")     # columns of mnf_eval_views' metrics rows
+
+
+def miou_from_confusion(confusion) -> float:
+    """Mean intersection over union of a [C,C] confusion matrix (rows: ground-truth class, columns: predicted class): the mean of
+    TP / (TP + FP + FN) over the classes that occur in the ground truth or in the prediction; a class absent from both does not enter
+    the mean.  NaN for an all-zero matrix.  Pure numpy / torch, no GPU."""
+    m = confusion.detach().cpu().numpy() if isinstance(confusion, torch.Tensor) else np.asarray(confusion)
+    m = m.astype(np.float64)
+    tp = np.diag(m)
+    union = m.sum(0) + m.sum(1) - tp            # TP + FP + FN
+    present = union > 0
+    if not present.any():
+        return float("nan")
+    return float(np.mean(tp[present] / union[present]))
+
+
+def _eval_index_tensor(idx, device, limit, what):
+    """int64 device tensor of `idx`; a host list / array / tensor is range-checked here (a device tensor is the caller's word: checking
+    it would take a synchronisation)."""
+    if isinstance(idx, torch.Tensor) and idx.is_cuda:
+        return L.contig(idx.reshape(-1), torch.int64)
+    host = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx).astype(np.int64).reshape(-1)
+    if host.size and (host.min() < 0 or host.max() >= limit):
+        raise IndexError(f"{what} out of range [0, {limit})")
+    return torch.from_numpy(host).to(device)
+
+
+@torch.no_grad()
+def eval_metrics(rgb, depth, sem, dataset, image_ids, pix_idx=None, confusion=True, labels=False):
+    """Error metrics of finished renders against the ground truth a `Dataset` holds (`mnf_eval_views`, csrc/eval.hip): rgb [V,P,3],
+    depth [V,P] / [V,P,1], sem [V,P,C] (or their [V,H,W,...] forms) for the images `image_ids` [V]; pixel p of a view is pixel
+    `pix_idx[p]` of its image (None: pixel p, row-major).  The ground truth is read from `dataset.images / depths / semantics` as they
+    are stored, `packed=True` or not; no fp32 ground-truth image is made.  Returns a dict of device tensors and does not synchronise:
+    `metrics` [V,8] float64 (columns: EVAL_COLUMNS), `confusion` [C,C] int64 summed over the V views (None unless `confusion`),
+    `pred_labels` [V,P] uint8 (None unless `labels`)."""
+    lib = L.load_library()
+    L.require_gpu(rgb, depth, sem, dataset.images, dataset.depths, dataset.semantics)
+    dev = sem.device
+    C = int(sem.shape[-1])
+    ids = _eval_index_tensor(image_ids, dev, len(dataset), "image_ids")
+    V = int(ids.shape[0])
+    ppi = int(dataset.height) * int(dataset.width)
+    if V == 0 or sem.numel() % (V * C):
+        raise ValueError(f"sem of shape {tuple(sem.shape)} does not hold {V} views of {C}-class pixels")
+    P = sem.numel() // (V * C)
+    if rgb.numel() != V * P * 3 or depth.numel() != V * P:
+        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} do not match {V} views of {P} pixels")
+    pix = None
+    if pix_idx is not None:
+        pix = _eval_index_tensor(pix_idx, dev, ppi, "pix_idx")
+        if int(pix.shape[0]) != P:
+            raise ValueError(f"pix_idx has {int(pix.shape[0])} entries for views of {P} pixels")
+    elif P > ppi:
+        raise ValueError(f"views of {P} pixels against images of {ppi} pixels need a pix_idx")
+    if labels and C > 256:
+        raise ValueError("pred_labels are uint8: labels=True needs at most 256 classes")
+    if dataset.depths.dtype not in (torch.float32, torch.float16) or dataset.semantics.dtype not in (torch.int64, torch.uint8) \
+            or dataset.images.dtype != torch.uint8:
+        raise TypeError("eval_metrics reads u8 images, f32 / f16 depths and i64 / u8 labels")
+    r, d, s = (L.contig(t, torch.float32) for t in (rgb, depth, sem))
+    gi, gd, gs = dataset.images.contiguous(), dataset.depths.contiguous(), dataset.semantics.contiguous()
+    metrics = torch.empty(V, 8, dtype=torch.float64, device=dev)
+    conf = torch.empty(C, C, dtype=torch.int64, device=dev) if confusion else None
+    pred = torch.empty(V, P, dtype=torch.uint8, device=dev) if labels else None
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mnf_eval_views_workspace_bytes(V, P, C))
+        ws = _workspace((dev, "eval"), max(nbytes, 8))
+        L.launch(lib.mnf_eval_views, L.ptr(r), L.ptr(d), L.ptr(s), V, P, C, L.ptr(gi), L.ptr(gd), int(gd.dtype == torch.float16), L.ptr(gs),
+                 int(gs.dtype == torch.uint8), ppi, L.ptr(ids), L.ptr(pix), L.ptr(metrics), L.ptr(conf), L.ptr(pred), L.ptr(ws), max(nbytes, 8))
+    return dict(metrics=metrics, confusion=conf, pred_labels=pred)
+
+
+@torch.no_grad()
+def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, render_step_size, cone_angle, alpha_thre, max_samples=1024,
+                   render_bkgd=None, views_per_call=4, return_images=False, labels=False):
+    """The evaluation block of `nerf_training` (pipeline.py:550-613) as one call: the held-out images `indices` of `dataset` are rendered
+    `views_per_call` at a time — one batched `mnf_generate_rays` (all pixels, row-major: the evaluation branch of `Dataset.fetch_data`),
+    one batched test render (a view's result is that of `render_image_with_occgrid_test` on `dataset[i]["rays"]`, bit for bit, whatever
+    the grouping) and one `mnf_eval_views` per group — and ONE device-to-host copy at the end brings the metrics and the confusion matrix.
+    `render_bkgd=None` is white, what `Dataset.preprocess` hands out when not training.
+    Returns a dict: per-view float64 arrays `rgb_mse`, `psnr`, `depth_mse`, `sem_ce`, `sem_acc`; `confusion` int64 [C,C] over all views
+    with `pixel_accuracy` and `miou` (`miou_from_confusion`); `mean` = {"psnr", "depth_mse", "sem_ce"}, the three numbers
+    pipeline.py:650-656 prints.  Raises ValueError when a view has labels outside [0, C) (so does torch's cross_entropy).
+    `return_images=True` adds the device tensors `rgb` [N,H,W,3], `acc` [N,H,W,1], `depth` [N,H,W,1], `sem` [N,H,W,C], and
+    `pred_labels` [N,H,W] uint8 with `labels=True` (the argmax image of pipeline.py:1011)."""
+    lib = L.load_library()
+    idx = [int(i) for i in (indices.tolist() if hasattr(indices, "tolist") else indices)]
+    if not idx:
+        raise ValueError("evaluate_views needs at least one image index")
+    if min(idx) < 0 or max(idx) >= len(dataset):
+        raise IndexError(f"image index out of range [0, {len(dataset)})")
+    H, W = int(dataset.height), int(dataset.width)
+    P, C = H * W, int(radiance_field.num_semantic_classes)
+    dev = dataset.images.device
+    L.require_gpu(dataset.images, dataset.camtoworlds)
+    bkgd = torch.ones(3) if render_bkgd is None else render_bkgd.detach().cpu()      # a host tensor: the render options take host floats
+    per = max(1, int(views_per_call))
+    rows, conf, imgs = [], None, dict(rgb=[], acc=[], depth=[], sem=[], pred_labels=[])
+    for g0 in range(0, len(idx), per):
+        ids = torch.tensor(idx[g0:g0 + per], dtype=torch.int64, device=dev)
+        V = int(ids.shape[0])
+        c2w = dataset.camtoworlds[ids][:, :3, :4].contiguous()
+        o = torch.empty(V * P, 3, device=dev)
+        d = torch.empty(V * P, 3, device=dev)
+        L.launch(lib.mnf_generate_rays, L.ptr(c2w), V, W, H, dataset._focal, None, P, L.ptr(o), L.ptr(d))
+        r = _render_jobs([(radiance_field, estimator, o, d)], P, max_samples, near_plane, 1e10, render_step_size, bkgd, cone_angle, alpha_thre,
+                         1e-4, False, 8, (H, W), None)[0]
+        m = eval_metrics(r["rgb"], r["depth"], r["sem"], dataset, ids, None, confusion=True, labels=labels and return_images)
+        rows.append(m["metrics"])
+        conf = m["confusion"] if conf is None else conf + m["confusion"]
+        if return_images:
+            for k in ("rgb", "acc", "depth", "sem"):
+                imgs[k].append(r[k].view(V, H, W, -1))
+            if labels:
+                imgs["pred_labels"].append(m["pred_labels"].view(V, H, W))
+    n = len(idx)
+    # the one device-to-host copy: the metric rows and the matrix (its int64 bits carried as float64 words) in one block
+    host = torch.cat([torch.cat(rows).reshape(-1), conf.view(torch.float64).reshape(-1)]).cpu()
+    met = host[:n * 8].numpy().reshape(n, 8)
+    confusion = host[n * 8:].view(torch.int64).numpy().reshape(C, C).copy()
+    if (met[:, 6] > 0).any():
+        bad = [idx[k] for k in np.nonzero(met[:, 6] > 0)[0]]
+        raise ValueError(f"ground-truth labels outside [0, {C}) in image(s) {bad}: {int(met[:, 6].sum())} pixels")
+    out = {name: met[:, k].copy() for k, name in enumerate(EVAL_COLUMNS[:5])}
+    total = confusion.sum()
+    out["confusion"] = confusion
+    out["pixel_accuracy"] = float(np.trace(confusion) / total) if total else float("nan")
+    out["miou"] = miou_from_confusion(confusion)
+    out["mean"] = {"psnr": float(np.mean(out["psnr"])), "depth_mse": float(np.mean(out["depth_mse"])), "sem_ce": float(np.mean(out["sem_ce"]))}
+    if return_images:
+        for k in ("rgb", "acc", "depth", "sem") + (("pred_labels",) if labels else ()):
+            out[k] = torch.cat(imgs[k])
+    return out

@@ -526,7 +526,7 @@ int mnf_planner_map(const uint8_t *binaries, int32_t n_members, int32_t res_x, i
 /* Optional in-library kernel timing for bench.py's roofline figures: between begin and end the library brackets its main
  * launches with hipEvent pairs on the launch stream, grouped by label: "field_render" (the fused field kernel of
  * mnf_render_test), "field_density", "field_forward", "field_train_forward", "dgrad", "wgrad", "hash_scatter",
- * "composite_train_forward", "composite_train_backward", "sample_rays".  mnf_profile_end synchronises the events, sums
+ * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views".  mnf_profile_end synchronises the events, sums
  * the milliseconds per label and returns the "field_render" totals; mnf_profile_query reads any label afterwards.
  * Process-wide (backward passes run on torch's autograd thread).  Not part of the reference surface. */
 int mnf_profile_begin(void);
@@ -553,6 +553,34 @@ int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binari
                     int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
                     int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
                     const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
+/* ---------------------------------------------------------------- held-out view evaluation */
+
+/* The error metrics of scripts/pipeline.py:550-613 (per test image: F.cross_entropy on the [H*W, C] logits, F.mse_loss on rgb and
+ * depth, PSNR, each behind a blocking .item(), every plane copied to the host) and the label image of :1011 (np.argmax over a float64
+ * [H, W, C] host stack), as one pass over the finished renders of n_views views of n_pix pixels: rgb [V,P,3], depth [V,P],
+ * sem [V,P,C] f32.  Ground truth is read from the dataset's own storage, either layout mnf_gather_pixels accepts (gt_images u8
+ * [N,pixels_per_image,3]; gt_depths f32, or f16 with depth_is_f16; gt_semantics int64, or u8 with sem_is_u8): pixel p of view v is
+ * pixel image_ids[v] * pixels_per_image + (pix_idx ? pix_idx[p] : p) of the storage (image_ids [V], pix_idx [P] or NULL, int64).
+ * Ground-truth rgb is (float)u8 / 255.0f as mnf_gather_pixels computes it; differences, squares, sums, the log-sum-exp (maximum
+ * subtracted) and the logarithms are double.  The predicted class is the first maximal logit (torch.argmax / np.argmax).
+ * metrics [V,8] f64, per view: [0] rgb MSE over P*3, [1] PSNR = -10 ln(mse) / ln(10) (+inf at mse 0), [2] depth MSE, [3] semantic
+ * cross-entropy and [4] pixel accuracy, both over the pixels whose label lies in [0, C), [5] the number of those pixels, [6] the
+ * number of pixels with a label outside [0, C) (left out of [3], [4] and the matrix), [7] 0 (reserved).  A view without a valid
+ * label has NaN in [3] and [4]; NaN / inf in a render propagate as they do in torch.
+ * Optional outputs (NULL = skip): confusion [C,C] int64, rows = ground-truth class, columns = predicted class, summed over the views
+ * of the call and WRITTEN, not accumulated into (counted in an LDS histogram per workgroup for C <= 64, with global integer atomics
+ * directly above that); pred_labels [V,P] u8, the argmax map (needs C <= 256).
+ * No floating-point atomics: the same inputs give the same bits, and a view's row does not depend on the other views of the call.
+ * workspace: mnf_eval_views_workspace_bytes(V, P, C) bytes, 8-byte aligned (per-workgroup partial sums).  Argument errors return
+ * MNF_ERR_INVALID (a workspace that is too small included) before anything is enqueued; C > 10239 returns MNF_ERR_UNSUPPORTED;
+ * n_views == 0 returns MNF_OK.  Enqueues on `stream` and does not synchronise. */
+int64_t mnf_eval_views_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes);
+int mnf_eval_views(const float *rgb, const float *depth, const float *sem, int32_t n_views, int64_t n_pix, int32_t n_classes,
+                   const uint8_t *gt_images, const void *gt_depths, int32_t depth_is_f16, const void *gt_semantics, int32_t sem_is_u8,
+                   int64_t pixels_per_image, const int64_t *image_ids, const int64_t *pix_idx,
+                   double *metrics, int64_t *confusion, uint8_t *pred_labels,
+                   void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
 #ifdef __cplusplus
 }

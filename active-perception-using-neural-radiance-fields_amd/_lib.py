@@ -214,17 +214,12 @@ def stream(device=None):
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def launch(fn, *args):
-    """Call a stream-taking entry point of the C ABI: the GPU that owns the tensors (first device pointer among
-    `args`) is made current for the duration of the call and the work goes onto torch's current stream OF THAT GPU —
-    a model on cuda:1 runs on GPU 1 whatever the caller's current device is (the reference's `DEVICE_GUARD`,
+def launch(fn, *args, device=None):
+    """Call a stream-taking entry point of the C ABI: the GPU that owns the tensors (`device=`, for a call whose device pointers sit inside a
+    host array, else that of the first device pointer among `args`) is made current for the duration of the call and the work goes onto torch's
+    current stream OF THAT GPU — a model on cuda:1 runs on GPU 1 whatever the caller's current device is (the reference's `DEVICE_GUARD`,
     utils_cuda.cuh:23-24).  Appends the stream argument and raises MnfError on a non-zero return code."""
-    dev = next((a.device for a in args if isinstance(a, DevPtr) and a.device is not None), None)
-    if dev is None:      # an anchor object (`.p` = DevPtr) names the GPU of a call whose device pointers sit inside a host array
-        anchor = next((a for a in args if hasattr(a, "p") and isinstance(getattr(a, "p"), DevPtr)), None)
-        if anchor is not None:
-            dev = anchor.p.device
-            args = tuple(a for a in args if a is not anchor)
+    dev = device if device is not None else next((a.device for a in args if isinstance(a, DevPtr) and a.device is not None), None)
     if dev is None:
         check(fn(*args, stream()))
         return

@@ -22,6 +22,7 @@ from . import _lib as L
 from . import nerfacc as NA
 
 Rays = collections.namedtuple("Rays", ("origins", "viewdirs"))
+_GridArgs = collections.namedtuple("_GridArgs", ("binaries", "bits", "occs", "res", "aabb", "n_levels"))       # `_grid_args`
 
 _WORKSPACES = collections.OrderedDict()
 MAX_CACHED_WORKSPACES = 12      # (device, slot, stream) entries kept; the least recently used one goes first.  Grows to the largest job count of a render call + 4
@@ -56,20 +57,32 @@ def release_workspaces(stream=None):
         del _WORKSPACES[k]
 
 
-def _grid_levels(estimator, max_levels=4):
-    """-> (binaries u8 [L,X,Y,Z] on device, the L aabbs as one flat list of 6 L host floats).  The host copy of the aabbs lives on the
-    estimator and is refreshed when the tensor changes (`OccGridEstimator.aabb_host`), so a render call does not synchronise."""
+def _grid_args(estimator, max_levels=4):
+    """The occupancy grid as the C entry points take it: the binaries as u8 [L,X,Y,Z], the estimator's packed bit grid (no per-call packing), its
+    occupancy values, the resolution (X, Y, Z) and the L aabbs as one `c_float` array of 6 L.  The host copy of the aabbs lives on the estimator
+    and is refreshed when the tensor changes (`OccGridEstimator.aabb_host`), so a call does not synchronise."""
     L_ = int(estimator.binaries.shape[0])
     if L_ > max_levels:
         raise NotImplementedError(f"the fused renderer supports up to {max_levels} occupancy levels (got {L_}); use nerfacc.traverse_grids")
     b = estimator.binaries
     b = b.contiguous().view(torch.uint8) if b.dtype == torch.bool else b.to(torch.uint8).contiguous()
-    aabb = []
-    for lvl in range(L_):
-        aabb += list(estimator.aabb_host(lvl))
-    return b, aabb
+    L.require_gpu(b)
+    aabb = [x for lvl in range(L_) for x in estimator.aabb_host(lvl)]
+    bits = estimator.bitgrid() if hasattr(estimator, "bitgrid") else None
+    return _GridArgs(b, bits, estimator.occs, tuple(b.shape[1:]), (ctypes.c_float * len(aabb))(*aabb), L_)
 
 
+def _render_opts(*, max_samples, near_plane, far_plane, render_step_size, cone_angle, alpha_thre, early_stop_eps, probabilistic, rays_per_view,
+                 sync_every=8, render_bkgd=None, view_order=None, n_levels=0):
+    """`mnf_render_opts` (include/mi355nerf.h).  `render_bkgd`: read on the host (None: black); `view_order`: `_view_order`'s (None: row-major)."""
+    opts = L.RenderOpts()
+    opts.near_plane, opts.far_plane, opts.render_step_size = near_plane, far_plane, render_step_size
+    opts.cone_angle, opts.alpha_thre, opts.early_stop_eps = cone_angle, alpha_thre, early_stop_eps
+    for i, x in enumerate(() if render_bkgd is None else render_bkgd.detach().cpu().reshape(-1)[:3]):
+        opts.render_bkgd[i] = float(x)
+    opts.max_samples, opts.probabilistic, opts.rays_per_view, opts.sync_every = int(max_samples), int(probabilistic), int(rays_per_view), sync_every
+    opts.view_order, opts.bitgrid, opts.n_levels = (None if view_order is None else view_order.data_ptr()), None, n_levels
+    return opts
 
 
 _VIEW_ORDERS = {}
@@ -90,7 +103,7 @@ def _view_order(h: int, w: int, device, block: int = 8) -> torch.Tensor:
     return t
 
 
-def _render_jobs(specs, rpv, max_samples, near_plane, far_plane, render_step_size, render_bkgd, cone_angle, alpha_thre, early_stop_eps,
+def _render_jobs(specs, rpv, *, max_samples, near_plane, far_plane, render_step_size, render_bkgd, cone_angle, alpha_thre, early_stop_eps,
                  probabilistic, sync_every=8, image_hw=None, n_split=2):
     """`specs`: list of (radiance_field, estimator, origins [n,3], viewdirs [n,3]) sharing rays_per_view `rpv` and every option (the
     members of an ensemble looking at the same poses, or one model).  Every spec is cut into up to `n_split` contiguous groups of
@@ -98,113 +111,73 @@ def _render_jobs(specs, rpv, max_samples, near_plane, far_plane, render_step_siz
     marcher or the tail of its field launch leaves compute units idle, the other jobs' kernels use them.  A view's result does not
     depend on the grouping (its round schedule and its sample tiles are its own).  Returns one dict of device tensors per spec."""
     lib = L.load_library()
-    opts = L.RenderOpts()
-    opts.near_plane, opts.far_plane, opts.render_step_size = near_plane, far_plane, render_step_size
-    opts.cone_angle, opts.alpha_thre, opts.early_stop_eps = cone_angle, alpha_thre, early_stop_eps
-    bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(x) for x in render_bkgd.detach().cpu().reshape(-1)[:3]]
-    for i in range(3):
-        opts.render_bkgd[i] = bk[i]
-    opts.max_samples, opts.probabilistic, opts.rays_per_view, opts.sync_every = int(max_samples), int(probabilistic), int(rpv), sync_every
-    dev = specs[0][2].device
-    order = None
-    if image_hw is not None and image_hw[0] * image_hw[1] == rpv and min(image_hw) >= 16:
-        order = _view_order(image_hw[0], image_hw[1], dev)
-    opts.view_order = None if order is None else order.data_ptr()
-    opts.bitgrid = None
-    jobs, keep, outs = [], [], []
-    grid0 = None
-    for radiance_field, estimator, o, d in specs:
+    dev = specs[0][2].device                         # the GPU that owns the rays: device guard + stream of the call
+    order = _view_order(*image_hw, dev) if image_hw is not None and image_hw[0] * image_hw[1] == rpv and min(image_hw) >= 16 else None
+    opts = _render_opts(max_samples=max_samples, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, cone_angle=cone_angle,
+                        alpha_thre=alpha_thre, early_stop_eps=early_stop_eps, probabilistic=probabilistic, rays_per_view=rpv, sync_every=sync_every,
+                        render_bkgd=render_bkgd, view_order=order)
+    # n_split=None: the measured optimum for the shape — small views (the scorer's 64 x 64 sub-samples: a round is latency-bound) advance as four jobs, full
+    # images as two (profiles/r03_hw_queues.txt: one member, 256 scoring views 54.3 -> 50.4 ms with four; 800 x 800 views: two and four tie)
+    want = (4 if rpv <= 16384 else 2) if n_split is None else int(n_split)
+    groups = [max(1, min(want, o.shape[0] // rpv)) for _, _, o, _ in specs]
+    global MAX_CACHED_WORKSPACES
+    MAX_CACHED_WORKSPACES = max(MAX_CACHED_WORKSPACES, sum(groups) + 4)      # a call never evicts the slots it is still filling (ADVICE r05): the cap follows the largest job count seen
+    jobs, keep, outs, grid0 = [], [], [], None
+    for (radiance_field, estimator, o, d), G in zip(specs, groups):
         L.require_gpu(o, d)
-        n = o.shape[0]
+        n, C = o.shape[0], radiance_field.num_semantic_classes
         if n % rpv:
             raise L.MnfError(f"n_rays ({n}) must be a positive multiple of rays_per_view ({rpv})")
-        C = radiance_field.num_semantic_classes
-        handle = radiance_field._ensure_handle()
-        binaries, aabb = _grid_levels(estimator)
-        L.require_gpu(binaries)
+        handle, grid = radiance_field._ensure_handle(), _grid_args(estimator)
         if grid0 is None:
-            grid0 = (tuple(binaries.shape[1:]), tuple(aabb))
-        elif grid0 != (tuple(binaries.shape[1:]), tuple(aabb)):
+            grid0 = grid
+        elif (grid0.res, tuple(grid0.aabb)) != (grid.res, tuple(grid.aabb)):
             raise L.MnfError("render jobs of one call must share the occupancy grid resolution and aabb")
-        bits = estimator.bitgrid() if hasattr(estimator, "bitgrid") else None     # the estimator's packed grid (no per-call packing)
         rgb = torch.empty(n, 3, device=dev); acc = torch.empty(n, 1, device=dev); depth = torch.empty(n, 1, device=dev)
         sem = torch.empty(n, C, device=dev)
-        rgb_var = torch.empty(n, 3, device=dev) if probabilistic else None
-        depth_var = torch.empty(n, 1, device=dev) if probabilistic else None
+        rgb_var, depth_var = (torch.empty(n, 3, device=dev), torch.empty(n, 1, device=dev)) if probabilistic else (None, None)
         V = n // rpv
-        # n_split=None: the measured optimum for the shape — small views (the scorer's 64 x 64 sub-samples: a round is latency-bound) advance as four jobs, full
-        # images as two (profiles/r03_hw_queues.txt: one member, 256 scoring views 54.3 -> 50.4 ms with four; 800 x 800 views: two and four tie)
-        want = (4 if rpv <= 16384 else 2) if n_split is None else int(n_split)
-        G = max(1, min(want, V))
         totals = torch.zeros(G, 2, dtype=torch.int64, device=dev)   # per job: [kept (reference total_samples), evaluated]
-        keep += [binaries, bits, o, d, totals]
+        keep += [grid, o, d, totals]
         for g in range(G):
             r0, r1 = (V * g // G) * rpv, (V * (g + 1) // G) * rpv
             if r1 == r0:
                 continue
             nbytes = lib.mnf_render_workspace_bytes(r1 - r0, rpv)
-            global MAX_CACHED_WORKSPACES
-            MAX_CACHED_WORKSPACES = max(MAX_CACHED_WORKSPACES, len(jobs) + 5)      # a call never evicts the slots it is still filling (ADVICE r05): the cap follows the largest job count seen
             ws = _workspace((dev, len(jobs)), nbytes)
             j = L.RenderJob()
-            j.field, j.binaries, j.bitgrid = handle, binaries.data_ptr(), (None if bits is None else bits.data_ptr())
+            j.field, j.binaries, j.bitgrid = handle, grid.binaries.data_ptr(), (None if grid.bits is None else grid.bits.data_ptr())
             j.rays_o, j.rays_d, j.n_rays = o[r0:].data_ptr(), d[r0:].data_ptr(), r1 - r0
             j.rgb, j.acc, j.depth, j.sem = rgb[r0:].data_ptr(), acc[r0:].data_ptr(), depth[r0:].data_ptr(), sem[r0:].data_ptr()
-            j.rgb_var = rgb_var[r0:].data_ptr() if probabilistic else None
-            j.depth_var = depth_var[r0:].data_ptr() if probabilistic else None
+            j.rgb_var, j.depth_var = (rgb_var[r0:].data_ptr(), depth_var[r0:].data_ptr()) if probabilistic else (None, None)
             j.total_samples = totals[g].data_ptr()
             j.workspace, j.workspace_bytes = ws.data_ptr(), nbytes
             jobs.append(j)
             keep.append(ws)
-        out = dict(rgb=rgb, acc=acc, depth=depth, sem=sem, _totals=totals)
-        if probabilistic:
-            out.update(rgb_var=rgb_var, depth_var=depth_var)
-        outs.append(out)
+        outs.append(dict(rgb=rgb, acc=acc, depth=depth, sem=sem, _totals=totals, **(dict(rgb_var=rgb_var, depth_var=depth_var) if probabilistic else {})))
     if jobs:
-        arr = (L.RenderJob * len(jobs))(*jobs)
-        res, aabb = grid0
-        opts.n_levels = len(aabb) // 6
-        anchor = L.ptr(specs[0][2])                  # device guard + stream of the GPU that owns the rays
-        L.launch(lib.mnf_render_jobs, arr, len(jobs), res[0], res[1], res[2], (ctypes.c_float * len(aabb))(*aabb), ctypes.byref(opts), _Anchor(anchor))
+        opts.n_levels = grid0.n_levels
+        L.launch(lib.mnf_render_jobs, (L.RenderJob * len(jobs))(*jobs), len(jobs), *grid0.res, grid0.aabb, ctypes.byref(opts), device=dev)
     for out in outs:
         out["total"] = out.pop("_totals").sum(0)
     return outs
 
 
-class _Anchor:
-    """Carries a DevPtr through `L.launch` without adding an argument to the C call: launch() derives the device guard and the
-    stream from the first DevPtr among its arguments; mnf_render_jobs takes its device pointers inside the job array."""
-
-    def __init__(self, p):
-        self.p = p
-
-
-def _render_test(max_samples, radiance_field, estimator, rays, near_plane, far_plane, render_step_size, render_bkgd,
-                 cone_angle, alpha_thre, early_stop_eps, probabilistic, rays_per_view=None, sync_every=8, image_hw=None, n_split=2):
+def _render_test(radiance_field, estimator, rays, rays_per_view=None, image_hw=None, **jobs_kw):
+    """One model's test render through `_render_jobs` (whose keywords `jobs_kw` are), reshaped to the rays' leading shape."""
     rays_shape = rays.origins.shape
     if image_hw is None and rays_per_view is None and len(rays_shape) == 3:
         image_hw = (int(rays_shape[0]), int(rays_shape[1]))      # [H,W,3] rays (utils.py:574-580): one image
     o = L.contig(rays.origins.reshape(-1, 3), torch.float32)
     d = L.contig(rays.viewdirs.reshape(-1, 3), torch.float32)
     L.require_gpu(o, d)
-    n = o.shape[0]
-    C = radiance_field.num_semantic_classes
-    dev = o.device
-    shp = tuple(rays_shape[:-1])
+    n, dev = o.shape[0], o.device
     if n == 0:
-        z = lambda *s_: torch.empty(*s_, device=dev)
-        out = dict(rgb=z(n, 3), acc=z(n, 1), depth=z(n, 1), sem=z(n, C), total=torch.zeros(2, dtype=torch.int64, device=dev))
-        if probabilistic:
-            out.update(rgb_var=z(n, 3), depth_var=z(n, 1))
+        widths = dict(rgb=3, acc=1, depth=1, sem=radiance_field.num_semantic_classes, **(dict(rgb_var=3, depth_var=1) if jobs_kw["probabilistic"] else {}))
+        out = dict({k: torch.empty(0, c, device=dev) for k, c in widths.items()}, total=torch.zeros(2, dtype=torch.int64, device=dev))
     else:
-        rpv = n if rays_per_view is None else int(rays_per_view)
-        out = _render_jobs([(radiance_field, estimator, o, d)], rpv, max_samples, near_plane, far_plane, render_step_size, render_bkgd,
-                           cone_angle, alpha_thre, early_stop_eps, probabilistic, sync_every, image_hw, n_split)[0]
-    res = dict(rgb=out["rgb"].view(*shp, -1), acc=out["acc"].view(*shp, -1), depth=out["depth"].view(*shp, -1), sem=out["sem"].view(*shp, -1),
-               total=out["total"])
-    if probabilistic:
-        res.update(rgb_var=out["rgb_var"].view(*shp, -1), depth_var=out["depth_var"].view(*shp, -1))
-    return res
+        out = _render_jobs([(radiance_field, estimator, o, d)], n if rays_per_view is None else int(rays_per_view), image_hw=image_hw, **jobs_kw)[0]
+    return {k: v if k == "total" else v.view(*rays_shape[:-1], -1) for k, v in out.items()}
 
 
 @torch.no_grad()
@@ -215,8 +188,8 @@ def render_image_with_occgrid_test(max_samples: int, radiance_field, estimator, 
     """utils.py:555-779 -> (rgb, acc, depth, sem, total_samples)."""
     if timestamps is not None:
         raise NotImplementedError("timestamps (D-NeRF) are not part of the hot path")
-    r = _render_test(max_samples, radiance_field, estimator, rays, near_plane, far_plane, render_step_size, render_bkgd,
-                     cone_angle, alpha_thre, early_stop_eps, False)
+    r = _render_test(radiance_field, estimator, rays, max_samples=max_samples, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
+                     render_bkgd=render_bkgd, cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=early_stop_eps, probabilistic=False)
     return r["rgb"], r["acc"], r["depth"], r["sem"], int(r["total"][0].item())
 
 
@@ -229,8 +202,8 @@ def render_probablistic_image_with_occgrid_test(max_samples: int, radiance_field
     """utils.py:782-1032 -> (rgb, rgb_var, acc, depth, depth_var, sem, total_samples)."""
     if timestamps is not None:
         raise NotImplementedError("timestamps (D-NeRF) are not part of the hot path")
-    r = _render_test(max_samples, radiance_field, estimator, rays, near_plane, far_plane, render_step_size, render_bkgd,
-                     cone_angle, alpha_thre, early_stop_eps, True)
+    r = _render_test(radiance_field, estimator, rays, max_samples=max_samples, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
+                     render_bkgd=render_bkgd, cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=early_stop_eps, probabilistic=True)
     return r["rgb"], r["rgb_var"], r["acc"], r["depth"], r["depth_var"], r["sem"], int(r["total"][0].item())
 
 
@@ -243,8 +216,9 @@ def render_views(radiance_field, estimator, rays_o, rays_d, rays_per_view, max_s
     pixels of an H x W image (a speed hint only: see `_view_order`).  `n_split`: the views are rendered as up to this many
     groups advancing side by side (`_render_jobs`; a speed choice only: results do not depend on it).
     Returns a dict of device tensors."""
-    return _render_test(max_samples, radiance_field, estimator, Rays(rays_o, rays_d), near_plane, far_plane, render_step_size,
-                        render_bkgd, cone_angle, alpha_thre, early_stop_eps, probabilistic, rays_per_view, sync_every, image_hw, n_split)
+    return _render_test(radiance_field, estimator, Rays(rays_o, rays_d), rays_per_view, image_hw, max_samples=max_samples, near_plane=near_plane,
+                        far_plane=far_plane, render_step_size=render_step_size, render_bkgd=render_bkgd, cone_angle=cone_angle, alpha_thre=alpha_thre,
+                        early_stop_eps=early_stop_eps, probabilistic=probabilistic, sync_every=sync_every, n_split=n_split)
 
 
 # ------------------------------------------------------------------ train-mode forward (utils.py:63-219, :362-461)
@@ -333,44 +307,65 @@ def allreduce_gradients(parameters, group=None, skip=None):
         dist.all_reduce(skip, op=dist.ReduceOp.SUM, group=group)
 
 
-_TRAIN_STATE = {}
-
 # status bits of mnf_train_step's counts_dev[3] (include/mi355nerf.h)
 _ST_MARCHED, _ST_ROW, _ST_KEPT, _ST_LABEL, _ST_EMPTY = 1, 2, 4, 8, 16
+_STEP_OK, _STEP_ROW, _STEP_GROW = "ok", "row overflow", "bounds overflow; grow"      # what `_step_verdict` says
 
 
-def _grow_caps(st, marched, kept, R, carry):
-    """Raise the sample bounds of a field's train state after a step that overflowed them.  The state is per FIELD, not per ray count (the
-    reference changes `num_rays` after every iteration, scripts/pipeline.py:494-504, to hold the sample count near `target_sample_batch_size`).
-      carry=False (synchronous steps: the overflowing step is repeated at once): only the bounds of this ray count grow — exactly the bounds
-                  rounds 1-3 used, which the deterministic mode's partial-sum grouping (and with it the bitwise identity of the stand-in
-                  scenes across rounds) depends on;
-      carry=True  (asynchronous steps, counts read late): an absolute bound (what the schedule holds constant) and a per-ray bound (what a
-                  fixed-size batch holds constant) grow, and every later call — whatever its ray count — uses at least the larger of the two."""
-    cm, ck = int(marched * 1.3) + 1024, int(max(kept, marched // 2) * 1.3) + 1024
-    if carry:
-        st["abs_m"], st["abs_k"] = max(st["abs_m"], cm), max(st["abs_k"], ck)
-        st["per_m"], st["per_k"] = max(st["per_m"], cm / max(R, 1)), max(st["per_k"], ck / max(R, 1))
-    else:
-        bm, bk = st["by_R"].get(R, (max(R * 384, 1 << 18), R * 192))
-        st["by_R"][R] = (max(bm, cm), max(bk, ck))
+class TrainState:
+    """What train steps keep per FIELD, not per ray count (the reference changes `num_rays` after every iteration, scripts/pipeline.py:494-504, to
+    hold the sample count near `target_sample_batch_size`): the sample bounds, the step reports in flight and the counters read from them."""
+
+    def __init__(self):
+        self.by_R = {}                          # ray count -> (max_marched, max_kept) raised by synchronous steps of that ray count
+        self.abs_m, self.abs_k = 0, 0           # absolute bounds: raised by asynchronous steps and by `reserve`
+        self.per_m, self.per_k = 0.0, 0.0       # per-ray bounds: raised by asynchronous steps
+        self.pending = []                       # (pinned int64[5], event, ray count) of asynchronous steps whose report has not been read
+        self.pinned = []                        # (pinned int64[5], event) pairs free for the next report: at most 3 are in flight
+        self.last_counts = None                 # (n_rays, marched, kept) of the latest report read: `latest_step_counts`
+        self.skipped_steps = 0                  # asynchronous steps whose final skip flag arrived raised
+        self.sched_debt = 0                     # scheduler steps those had been given and the next calls leave out
+        self.overflowed_steps = 0               # asynchronous steps that were beyond a sample bound
+
+    def _own(self, R):
+        # (the default marched bound has an absolute floor: small batches of the dynamic schedule march ~1000 samples per ray through empty-looking early
+        #  grids, and an asynchronous step cannot be repeated; the surviving bound keeps its per-ray form — the deterministic mode's grouping depends on it)
+        return self.by_R.get(R, (max(R * 384, 1 << 18), R * 192))
+
+    def caps(self, R):
+        """(max_marched, max_kept) of a call with R rays: generous per-ray defaults, raised by what earlier steps of this field overflowed."""
+        bm, bk = self._own(R)
+        return max(bm, self.abs_m, int(self.per_m * R)), max(bk, self.abs_k, int(self.per_k * R))
+
+    def grow(self, marched, kept, R, carry):
+        """Raise the bounds after a step of R rays that overflowed them with `marched` / `kept` samples.
+          carry=False (synchronous steps: the overflowing step is repeated at once): only the bounds of this ray count grow — exactly the bounds
+                      rounds 1-3 used, which the deterministic mode's partial-sum grouping (and with it the bitwise identity of the stand-in
+                      scenes across rounds) depends on;
+          carry=True  (asynchronous steps, counts read late): an absolute bound (what the schedule holds constant) and a per-ray bound (what a
+                      fixed-size batch holds constant) grow, and every later call — whatever its ray count — uses at least the larger of the two."""
+        cm, ck = int(marched * 1.3) + 1024, int(max(kept, marched // 2) * 1.3) + 1024
+        if carry:
+            self.reserve(cm, ck)
+            self.per_m, self.per_k = max(self.per_m, cm / max(R, 1)), max(self.per_k, ck / max(R, 1))
+        else:
+            bm, bk = self._own(R)
+            self.by_R[R] = (max(bm, cm), max(bk, ck))
+
+    def reserve(self, max_marched, max_kept):
+        """Every later call, whatever its ray count, is sized for at least these many samples."""
+        self.abs_m, self.abs_k = max(self.abs_m, int(max_marched)), max(self.abs_k, int(max_kept))
 
 
-def _caps_for(st, R):
-    """(max_marched, max_kept) of a call with R rays: generous per-ray defaults, raised by what earlier steps of this field overflowed."""
-    # (the default marched bound has an absolute floor: small batches of the dynamic schedule march ~1000 samples per ray through empty-looking early
-    #  grids, and an asynchronous step cannot be repeated; the surviving bound keeps its per-ray form — the deterministic mode's grouping depends on it)
-    bm, bk = st["by_R"].get(R, (max(R * 384, 1 << 18), R * 192))
-    return max(bm, st["abs_m"], int(st["per_m"] * R)), max(bk, st["abs_k"], int(st["per_k"] * R))
+_TRAIN_STATE = {}
 
 
-def _train_state(radiance_field):
-    """The field's train state (sample bounds, counts in flight, pinned buffers): one per field whatever the ray count of a call (VERDICT r03
-    weak 6: under the reference's schedule the ray count changes every step)."""
+def _train_state(radiance_field) -> TrainState:
+    """The field's train state: one per field whatever the ray count of a call (under the reference's schedule it changes every step)."""
     key = id(radiance_field)
     st = _TRAIN_STATE.get(key)
     if st is None:
-        st = _TRAIN_STATE[key] = dict(by_R={}, abs_m=0, abs_k=0, per_m=0.0, per_k=0.0, pending=[])
+        st = _TRAIN_STATE[key] = TrainState()
         weakref.finalize(radiance_field, _TRAIN_STATE.pop, key, None)      # (the key holds id(field): drop the entry with the field, or a later field could inherit it)
     return st
 
@@ -380,8 +375,7 @@ def reserve_sample_bounds(radiance_field, max_marched: int, max_kept: int):
     samples in front of the visibility filter and `max_kept` behind it, whatever its ray count.  For asynchronous training (sync=False), where a step
     beyond its bounds cannot be repeated but is skipped on the device: a caller that knows its budget (`target_sample_batch_size` and the sampler's
     marched / surviving ratio) loses no step to the default per-ray bounds."""
-    st = _train_state(radiance_field)
-    st["abs_m"], st["abs_k"] = max(st["abs_m"], int(max_marched)), max(st["abs_k"], int(max_kept))
+    _train_state(radiance_field).reserve(max_marched, max_kept)
 
 
 def latest_step_counts(radiance_field):
@@ -390,12 +384,59 @@ def latest_step_counts(radiance_field):
     reference's dynamic batch size (scripts/pipeline.py:494-504: num_rays *= target_sample_batch_size / n_rendering_samples) can use
     without waiting for the GPU: the schedule then runs one or two steps behind the counts, the sample bounds absorb the lag."""
     st = _TRAIN_STATE.get(id(radiance_field))
-    return None if st is None else st.get("last_counts")
+    return None if st is None else st.last_counts
 
 
-def _check_status(status):
+def _step_verdict(marched, kept, longest, status, skipped):
+    """What the five host words of a step (marched, kept, longest ray, status, final skip flag) say about it: raises for a label outside the classes,
+    else _STEP_ROW (a ray longer than a scratch row: the batch is not one for the fused path), _STEP_GROW (a sample bound was too small) or _STEP_OK."""
     if status & _ST_LABEL:
         raise L.MnfError("train_step: a semantic class id lies outside [0, num_semantic_classes) (F.cross_entropy's device assert)")
+    if status & _ST_ROW:
+        return _STEP_ROW
+    return _STEP_GROW if status & (_ST_MARCHED | _ST_KEPT) else _STEP_OK
+
+
+def _drain_reports(st, wait):
+    """Read the reports of earlier asynchronous steps (`_report_step`): adapt the bounds, surface their errors.  Everything that has arrived is read;
+    the step enqueued two calls ago is waited for (the host is at least a step ahead of the GPU: no stall), so a bound that is too small is
+    corrected at most two steps late.  `wait`: read them all."""
+    while st.pending and (wait or len(st.pending) > 1 or st.pending[0][1].query()):
+        host, ev, r_then = st.pending.pop(0)                    # (whatever ray count that step had: the bounds are the field's)
+        ev.synchronize()
+        c = host.tolist()
+        st.pinned.append((host, ev))
+        if c[4] > 0:                                            # that step was skipped on the device (no samples, a bound, non-finite gradients): train_step(sync=False)
+            st.skipped_steps += 1                               # had already advanced the LR scheduler for it — it owes one scheduler step (ADVICE r03)
+            st.sched_debt += 1
+        st.last_counts = (r_then, int(c[0]), int(c[1]))         # latest_step_counts(): the dynamic ray-count schedule without a host round trip
+        verdict = _step_verdict(*c)
+        if verdict == _STEP_ROW:
+            raise L.MnfError("train_step: a ray has more samples than a scratch row holds (use the autograd path: fused=False)")
+        if verdict == _STEP_GROW:
+            st.overflowed_steps += 1
+            st.grow(c[0], c[1], r_then, carry=True)
+
+
+def _report_step(st, out, optimizer=None, wait=False):
+    """The five words (`_step_verdict`) of a launched step `out` on their way to a pinned host buffer.  With `optimizer` (an `optim.FusedAdam`) its guarded step is enqueued
+    here and its step-count kernel writes them, the final skip flag included; an optimizer not bound to the field, or none, leaves them to copies on the
+    stream (no optimizer: the flag is not final, its word stays 0).  wait=True: the host waits and returns them; else `_drain_reports` reads them later."""
+    host, ev = st.pinned.pop() if st.pinned else (torch.zeros(5, dtype=torch.int64).pin_memory(), torch.cuda.Event())
+    host[4] = 0
+    counts, skip = out["counts"], out["skip"]
+    if optimizer is not None:
+        optimizer.step(skip=skip, count_nonfinite=True, report=(counts, host))
+    if optimizer is None or not optimizer.reported:
+        host[:4].copy_(counts, non_blocking=True)
+        if optimizer is not None:
+            host[4:5].copy_(skip.reshape(1).to(torch.int64), non_blocking=True)
+    ev.record(torch.cuda.current_stream(counts.device))
+    if not wait:
+        return st.pending.append((host, ev, out["_rays"]))
+    ev.synchronize()
+    st.pinned.append((host, ev))
+    return host.tolist()
 
 
 class Presample:
@@ -439,6 +480,34 @@ def _grid_version(estimator):
     return (b.data_ptr(), b._version, o.data_ptr(), o._version)
 
 
+def _step_seed(presampled, seed):
+    """The Philox key of a batch's near-plane jitter: the token's if the batch was presampled, else `seed`, else torch's CPU generator's next draw."""
+    if presampled is not None and presampled.keep is not None:
+        return presampled.seed
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+
+def _train_opts(radiance_field, grid, device, *, near_plane, far_plane, render_step_size, cone_angle, alpha_thre, stratified, seed, early_stop_eps=0.0,
+                loss_scale=0.0, deterministic=False, render_bkgd=None):
+    """-> (`mnf_train_opts` of a march or a step, the key under which a presampled march fits a step: the options the march depends on, the
+    device copy of `render_bkgd` the options point to, or None).  The march reads the options up to `seed`; `presampled` is left to the launch."""
+    opts = L.TrainOpts()
+    opts.near_plane, opts.far_plane, opts.render_step_size, opts.cone_angle = near_plane, far_plane, render_step_size, cone_angle
+    opts.alpha_thre, opts.early_stop_eps, opts.loss_scale = alpha_thre, early_stop_eps, loss_scale
+    opts.stratified = int(radiance_field.training if stratified is None else stratified)
+    opts.n_levels, opts.seed = grid.n_levels, seed
+    opts.deterministic = int(bool(deterministic))      # bitwise reproducible gradient accumulation (include/mi355nerf.h: mnf_train_opts)
+    bk_dev = None
+    if render_bkgd is not None and render_bkgd.is_cuda:          # pipeline.py:437 draws the colour on the GPU: hand over the pointer
+        bk_dev = L.contig(render_bkgd.detach().reshape(-1)[:3].to(device=device, dtype=torch.float32))
+        opts.render_bkgd_dev = bk_dev.data_ptr()
+    elif render_bkgd is not None:
+        for i, x in enumerate(render_bkgd.detach().reshape(-1)[:3]):
+            opts.render_bkgd[i] = float(x)
+    key = (float(near_plane), float(far_plane), float(render_step_size), float(cone_angle), float(alpha_thre), int(opts.stratified))
+    return opts, key, bk_dev
+
+
 @torch.no_grad()
 def presample(radiance_field, estimator, rays: Rays, near_plane=0.1, far_plane=1e10, render_step_size=1e-3, cone_angle=0.004, alpha_thre=0.01,
               stratified=None, handle: "Presample | None" = None, seed: "int | None" = None):
@@ -463,25 +532,17 @@ def presample(radiance_field, estimator, rays: Rays, near_plane=0.1, far_plane=1
     lib = L.load_library()
     o, d = L.contig(rays.origins.reshape(-1, 3), torch.float32), L.contig(rays.viewdirs.reshape(-1, 3), torch.float32)
     L.require_gpu(o, d)
-    R = o.shape[0]
-    binaries, aabb = _grid_levels(estimator)
-    bits = estimator.bitgrid()
-    res = binaries.shape[1:]
-    opts = L.TrainOpts()
-    opts.n_levels = len(aabb) // 6
-    opts.near_plane, opts.far_plane, opts.render_step_size, opts.cone_angle, opts.alpha_thre = near_plane, far_plane, render_step_size, cone_angle, alpha_thre
-    opts.stratified = int(radiance_field.training if stratified is None else stratified)
-    opts.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+    R, grid = o.shape[0], _grid_args(estimator)
+    opts, key, _ = _train_opts(radiance_field, grid, o.device, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
+                               cone_angle=cone_angle, alpha_thre=alpha_thre, stratified=stratified, seed=_step_seed(None, seed))
     tok = handle if handle is not None else Presample()
-    cap_m = _caps_for(_train_state(radiance_field), R)[0]      # the adopting step's bound on marched samples (the march's guard and compaction run here too)
+    cap_m = _train_state(radiance_field).caps(R)[0]      # the adopting step's bound on marched samples (the march's guard and compaction run here too)
     nbytes = int(lib.mnf_train_presample_workspace_bytes(R, cap_m))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=o.device)
-    L.launch(lib.mnf_train_presample, tok.handle, L.ptr(binaries), L.ptr(bits[0]), L.ptr(estimator.occs), res[0], res[1], res[2],
-             (ctypes.c_float * len(aabb))(*aabb), L.ptr(o), L.ptr(d), R, ctypes.byref(opts), cap_m, L.ptr(ws), nbytes)
-    tok.keep = (o, d, ws, binaries, bits)
-    tok.seed, tok.R, tok.version, tok.cap_m = int(opts.seed), R, _grid_version(estimator), cap_m
-    tok.key = (float(near_plane), float(far_plane), float(render_step_size), float(cone_angle), float(alpha_thre), int(opts.stratified))
-    tok.rays = (rays.origins, rays.viewdirs)
+    L.launch(lib.mnf_train_presample, tok.handle, L.ptr(grid.binaries), L.ptr(grid.bits), L.ptr(grid.occs), *grid.res, grid.aabb, L.ptr(o), L.ptr(d), R,
+             ctypes.byref(opts), cap_m, L.ptr(ws), nbytes)
+    tok.keep = (o, d, ws, grid.binaries, grid.bits)
+    tok.seed, tok.R, tok.version, tok.cap_m, tok.key, tok.rays = int(opts.seed), R, _grid_version(estimator), cap_m, key, (rays.origins, rays.viewdirs)
     return tok
 
 
@@ -522,9 +583,74 @@ def presampled_batches(batches, radiance_field, estimator, first_step: int = 0, 
 
 
 @torch.no_grad()
+def _launch_train_step(st, radiance_field, estimator, rays, pixels, dep, sem, render_bkgd, presampled, seed, wait_reports, **opts_kw):
+    """Exactly one `mnf_train_step` launch with the field's current sample bounds, behind the reading of earlier steps' reports (`_drain_reports(st,
+    wait_reports)`).  `presampled`: the batch's token or None; its march is adopted if it still fits this step (the token is consumed either way).
+    Returns `fused_forward_backward`'s dict with the counts as device tensors, which it also leaves in `estimator.last_sampling`."""
+    lib = L.load_library()
+    o, d = L.contig(rays.origins.reshape(-1, 3), torch.float32), L.contig(rays.viewdirs.reshape(-1, 3), torch.float32)
+    live = presampled is not None and presampled.keep is not None
+    if live and presampled.rays[0] is rays.origins and presampled.rays[1] is rays.viewdirs:
+        o, d = presampled.keep[0], presampled.keep[1]        # (the very tensors the march read: the C side compares pointers)
+    L.require_gpu(o, d, pixels, dep, sem)
+    R, dev = o.shape[0], o.device
+    handle, grid = radiance_field._ensure_handle(), _grid_args(estimator)
+    opts, key, bk_dev = _train_opts(radiance_field, grid, dev, seed=seed, loss_scale=float(radiance_field.loss_scale), render_bkgd=render_bkgd, **opts_kw)
+    params = [radiance_field.mlp_base.params, radiance_field.mlp_head.params, radiance_field.mlp_sem.params]
+    for p_ in params:
+        if p_.grad is None or p_.grad.shape != p_.shape or not p_.grad.is_contiguous():
+            p_.grad = torch.empty_like(p_)
+    tp, td, tl = L.contig(pixels, torch.float32), L.contig(dep, torch.float32), L.contig(sem, torch.int64)
+    _drain_reports(st, wait_reports)
+    losses, counts, skip = torch.empty(4, device=dev), torch.empty(4, dtype=torch.int64, device=dev), torch.empty((), dtype=torch.int32, device=dev)
+    cap_m, cap_k = st.caps(R)
+    nbytes = int(lib.mnf_train_step_workspace_bytes(handle, R, cap_m, cap_k))
+    ws = _workspace(dev, nbytes)
+    # the token's march only if it still fits this step: same rays, grid and options, and the bound on marched samples it was made for
+    adopt = (live and presampled.R == R and presampled.keep[0] is o and presampled.version == _grid_version(estimator) and presampled.key == key
+             and presampled.cap_m == cap_m)
+    if live and not adopt:
+        presampled.wait(dev)                                       # (its buffers are released below: not before the march has run)
+    opts.presampled = presampled.handle if adopt else None
+    L.launch(lib.mnf_train_step, handle, L.ptr(grid.binaries), L.ptr(grid.bits), L.ptr(grid.occs), *grid.res, grid.aabb, L.ptr(o), L.ptr(d), R,
+             L.ptr(tp), L.ptr(td), L.ptr(tl), ctypes.byref(opts), L.ptr(params[0].grad), L.ptr(params[1].grad), L.ptr(params[2].grad),
+             L.ptr(losses), L.ptr(counts), L.ptr(skip), cap_m, cap_k, L.ptr(ws), nbytes)
+    if presampled is not None:
+        presampled.adopted = adopt
+        presampled.keep = None                                      # consumed (or discarded): the step is enqueued, stream order protects the buffers
+    for p_ in params:
+        torch.autograd.graph.increment_version(p_.grad)
+    estimator.last_sampling = {"n_marched": counts[0]}
+    return dict(loss=losses[0], loss_rgb=losses[1], loss_dep=losses[2], loss_sem=losses[3], counts=counts, skip=skip, _keep=bk_dev, _rays=R,
+                n_rendering_samples=counts[1], n_marched=counts[0])
+
+
+def _run_step(batch, presampled, seed, opts_kw, wait_reports, read):
+    """A synchronous fused step: `mnf_train_step` is launched, `read(st, out)` enqueues what else belongs to an attempt and brings its five words to
+    the host; an attempt beyond its sample bounds changed nothing on the device and is repeated with larger ones (it marches itself: the guards cleared the
+    token's counts).  Returns (the launch's result, the words); (None, None) for more than four occupancy levels or a ray longer than a scratch row."""
+    st, seed = _train_state(batch[0]), _step_seed(presampled, seed)    # one draw per iteration, whatever the number of attempts
+    estimator = batch[1]
+    if estimator.levels > 4:
+        return None, None
+    for attempt in range(4):
+        out = _launch_train_step(st, *batch, presampled if attempt == 0 else None, seed, wait_reports, **opts_kw)
+        c = read(st, out)                                              # the step's one host round trip, after everything is enqueued
+        verdict = _step_verdict(*c)
+        if verdict == _STEP_ROW:
+            return None, None
+        if verdict == _STEP_OK:
+            estimator.last_sampling = {"n_marched": int(c[0])}
+            out.update(n_rendering_samples=int(c[1]), n_marched=int(c[0]))
+            return out, c
+        st.grow(c[0], c[1], out["_rays"], carry=False)
+    raise L.MnfError("train_step: sample bounds kept growing")
+
+
+@torch.no_grad()
 def fused_forward_backward(radiance_field, estimator, rays: Rays, pixels, dep, sem, render_bkgd=None, near_plane=0.1, far_plane=1e10,
                            render_step_size=1e-3, cone_angle=0.004, alpha_thre=0.01, early_stop_eps=1e-4, stratified=None, sync=True,
-                           deterministic=False, presampled: "Presample | None" = None, seed: "int | None" = None, _defer_report=False):
+                           deterministic=False, presampled: "Presample | None" = None, seed: "int | None" = None):
     """scripts/pipeline.py:472-518 for one model as ONE C call (`mnf_train_step`, csrc/trainstep.hip): train render (occupancy
     sampling + density pre-pass + visibility filter + sem_rendering), the three-term loss and its backward.  Fills `.grad` of
     the three flat parameter vectors.  The call itself never waits for the GPU: the sample counts stay on the device.
@@ -540,118 +666,119 @@ def fused_forward_backward(radiance_field, estimator, rays: Rays, pixels, dep, s
     single-pass scratch row): the caller then uses the autograd path, which is the same arithmetic in separate calls."""
     if estimator.levels > 4:
         return None
-    lib = L.load_library()
-    o, d = L.contig(rays.origins.reshape(-1, 3), torch.float32), L.contig(rays.viewdirs.reshape(-1, 3), torch.float32)
-    if presampled is not None and presampled.keep is not None and presampled.rays[0] is rays.origins and presampled.rays[1] is rays.viewdirs:
-        o, d = presampled.keep[0], presampled.keep[1]        # (the very tensors the march read: the C side compares pointers)
-    L.require_gpu(o, d, pixels, dep, sem)
-    R, dev = o.shape[0], o.device
-    handle = radiance_field._ensure_handle()
-    binaries, aabb = _grid_levels(estimator)
-    bits = estimator.bitgrid()
-    res = binaries.shape[1:]
-    opts = L.TrainOpts()
-    opts.n_levels = len(aabb) // 6
-    opts.near_plane, opts.far_plane, opts.render_step_size, opts.cone_angle = near_plane, far_plane, render_step_size, cone_angle
-    opts.alpha_thre, opts.early_stop_eps, opts.loss_scale = alpha_thre, early_stop_eps, float(radiance_field.loss_scale)
-    bk_dev = None
-    if render_bkgd is not None and render_bkgd.is_cuda:          # pipeline.py:437 draws the colour on the GPU: hand over the pointer
-        bk_dev = L.contig(render_bkgd.detach().reshape(-1)[:3].to(device=dev, dtype=torch.float32))
-        opts.render_bkgd_dev = bk_dev.data_ptr()
-    else:
-        bk = [0.0, 0.0, 0.0] if render_bkgd is None else [float(x) for x in render_bkgd.detach().reshape(-1)[:3]]
-        for i in range(3):
-            opts.render_bkgd[i] = bk[i]
-        opts.render_bkgd_dev = None
-    opts.stratified = int(radiance_field.training if stratified is None else stratified)
-    use_pre = False
-    if presampled is not None and presampled.keep is not None:
-        # the token's seed in any case (the batch's jitter was drawn when it was presampled); its march only if it still fits this step
-        opts.seed = presampled.seed
-        use_pre = (presampled.R == R and presampled.keep[0] is o and presampled.version == _grid_version(estimator)
-                   and presampled.key == (float(near_plane), float(far_plane), float(render_step_size), float(cone_angle), float(alpha_thre), int(opts.stratified)))
-        if not use_pre:
-            presampled.wait(dev)                                               # (its buffers are released below: not before the march has run)
-    else:
-        opts.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)      # (`seed`: the jitter's Philox key, for reproducible runs)
-    opts.deterministic = int(bool(deterministic))      # bitwise reproducible gradient accumulation (include/mi355nerf.h: mnf_train_opts)
-    params = [radiance_field.mlp_base.params, radiance_field.mlp_head.params, radiance_field.mlp_sem.params]
-    for p_ in params:
-        if p_.grad is None or p_.grad.shape != p_.shape or not p_.grad.is_contiguous():
-            p_.grad = torch.empty_like(p_)
-    tp, td, tl = L.contig(pixels, torch.float32), L.contig(dep, torch.float32), L.contig(sem, torch.int64)
-    st = _train_state(radiance_field)
-    # counts of earlier lazy steps (copied to pinned memory behind each step): adapt the bounds, surface their errors.  Everything that
-    # has arrived is read; the step enqueued two calls ago is waited for (the host is at least a step ahead of the GPU: no stall), so a
-    # bound that is too small is corrected at most two steps late.
-    pending = st["pending"]
-    while pending and (sync or len(pending) > 1 or pending[0][1].query()):
-        host, ev, r_then = pending.pop(0)                       # (whatever ray count that step had: the bounds are the field's)
-        ev.synchronize()
-        c = host.tolist()
-        if len(c) > 4 and c[4] > 0:                             # that step was skipped on the device (no samples, a bound, non-finite gradients): train_step(sync=False)
-            st["skipped_steps"] = st.get("skipped_steps", 0) + 1      # had already advanced the LR scheduler for it — it owes one scheduler step (ADVICE r03)
-            st["sched_debt"] = st.get("sched_debt", 0) + 1
-        c = c[:4]
-        st["last_counts"] = (r_then, int(c[0]), int(c[1]))       # latest_step_counts(): the dynamic ray-count schedule without a host round trip
-        st.setdefault("pinned", []).append((host, ev))
-        _check_status(c[3])
-        if c[3] & _ST_ROW:
-            raise L.MnfError("train_step: a ray has more samples than a scratch row holds (use the autograd path: fused=False)")
-        if c[3] & (_ST_MARCHED | _ST_KEPT):
-            st["overflowed_steps"] = st.get("overflowed_steps", 0) + 1
-            _grow_caps(st, c[0], c[1], r_then, carry=True)
-    for _attempt in range(4):
-        losses = torch.empty(4, device=dev)
-        counts = torch.empty(4, dtype=torch.int64, device=dev)
-        skip = torch.empty((), dtype=torch.int32, device=dev)
-        cap_m, cap_k = _caps_for(st, R)
-        nbytes = int(lib.mnf_train_step_workspace_bytes(handle, R, cap_m, cap_k))
-        ws = _workspace(dev, nbytes)
-        # (a repeated step marches itself: the guards cleared the token's counts; so does a step whose bound has grown since its token was made)
-        adopt = use_pre and _attempt == 0 and presampled.cap_m == cap_m
-        if use_pre and _attempt == 0 and not adopt:
-            use_pre = False
-            presampled.wait(dev)
-        opts.presampled = presampled.handle if adopt else None
-        L.launch(lib.mnf_train_step, handle, L.ptr(binaries), L.ptr(bits[0]), L.ptr(estimator.occs), res[0], res[1], res[2],
-                 (ctypes.c_float * len(aabb))(*aabb), L.ptr(o), L.ptr(d), R, L.ptr(tp), L.ptr(td), L.ptr(tl), ctypes.byref(opts),
-                 L.ptr(params[0].grad), L.ptr(params[1].grad), L.ptr(params[2].grad), L.ptr(losses), L.ptr(counts), L.ptr(skip),
-                 cap_m, cap_k, L.ptr(ws), nbytes)
-        if not sync:
-            break
-        c = counts.tolist()                                         # the step's one host round trip, after everything is enqueued
-        _check_status(c[3])
-        if c[3] & _ST_ROW:
-            return None
-        if c[3] & (_ST_MARCHED | _ST_KEPT):                         # a sample bound was too small: grow and redo
-            _grow_caps(st, c[0], c[1], R, carry=False)
-            continue
-        break
-    else:
-        raise L.MnfError("train_step: sample bounds kept growing")
-    if presampled is not None:
-        presampled.adopted = use_pre
-        presampled.keep = None                                      # consumed (or discarded): the step is enqueued, stream order protects the buffers
-    for p_ in params:
-        torch.autograd.graph.increment_version(p_.grad)
-    out = dict(loss=losses[0], loss_rgb=losses[1], loss_dep=losses[2], loss_sem=losses[3], counts=counts, skip=skip, _keep=bk_dev)
+    batch = (radiance_field, estimator, rays, pixels, dep, sem, render_bkgd)
+    opts_kw = dict(near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,
+                   early_stop_eps=early_stop_eps, stratified=stratified, deterministic=deterministic)
     if sync:
-        estimator.last_sampling = {"n_marched": int(c[0])}
-        out.update(n_rendering_samples=int(c[1]), n_marched=int(c[0]))
-    else:
-        pool = st.setdefault("pinned", [])                         # (pinned host buffer, event) pairs are recycled: at most 3 are in flight
-        host, ev = pool.pop() if pool else (torch.zeros(5, dtype=torch.int64).pin_memory(), torch.cuda.Event())
-        host[4] = 0                                                 # (slot 4: the step's final skip flag, filled by train_step behind the optimizer's guard)
-        if _defer_report:
-            out["_report"] = (host, ev, R)                          # train_step: the optimizer call writes counters + final skip flag into `host`, no copy on the stream
-        else:
-            host[:4].copy_(counts, non_blocking=True)
-            ev.record(torch.cuda.current_stream(dev))
-            st["pending"].append((host, ev, R))
-        estimator.last_sampling = {"n_marched": counts[0]}
-        out.update(n_rendering_samples=counts[1], n_marched=counts[0])
+        return _run_step(batch, presampled, seed, opts_kw, True, lambda st, out: out["counts"].tolist() + [0])[0]
+    st = _train_state(radiance_field)
+    out = _launch_train_step(st, *batch, presampled, _step_seed(presampled, seed), False, **opts_kw)
+    _report_step(st, out)
     return out
+
+
+def _step_result(fwd, skipped, sync):
+    """`train_step`'s result.  A synchronous step without a surviving sample is the reference's `continue` (pipeline.py:491): no loss."""
+    if sync and fwd["n_rendering_samples"] == 0:
+        return dict(loss=None, n_rendering_samples=0, skipped=True)
+    return dict(loss=fwd["loss"].detach(), loss_rgb=fwd["loss_rgb"].detach(), loss_dep=fwd["loss_dep"].detach(), loss_sem=fwd["loss_sem"].detach(),
+                n_rendering_samples=fwd["n_rendering_samples"], skipped=skipped)
+
+
+def _train_fused_one_trip(batch, optimizer, scheduler, presampled, seed, opts_kw):
+    """The reference's loop form (n_rendering_samples and the skip decision on the host after every iteration) with ONE host round trip and no bubble on
+    the GPU: render + loss + backward AND the guarded optimizer call are enqueued first, then the host waits once for the five words the optimizer's
+    step-count kernel wrote into pinned memory.  A step beyond its sample bounds has raised the flag on the device: its optimizer call changed
+    nothing, the bounds grow and the step is repeated.  None: the batch is not one for the fused path (the flagged optimizer call changed nothing)."""
+    out, c = _run_step(batch, presampled, seed, opts_kw, False, lambda st, out: _report_step(st, out, optimizer, wait=True))
+    if out is None:
+        return None
+    skipped = c[4] > 0
+    if not skipped and scheduler is not None:
+        scheduler.step()
+    return _step_result(out, skipped, True)
+
+
+def _apply_update(radiance_field, optimizer, scheduler, fwd, sync, data_parallel, data_parallel_group):
+    """pipeline.py:520-532 behind a forward + backward `fwd` (its losses, `skip` flag and `n_rendering_samples`): gradient all-reduce, non-finite
+    guard, optimizer and scheduler step; returns `train_step`'s result."""
+    from .optim import FusedAdam, count_nan_gradients
+    skip = fwd["skip"]
+    if data_parallel:
+        allreduce_gradients(radiance_field.parameters(), data_parallel_group, skip)
+    if not sync:
+        # the step's counters and its FINAL skip flag (the optimizer's non-finite guard included) travel to pinned host memory; when they arrive — one or two
+        # calls later — a skipped step takes back the scheduler step it is given here: the schedule counts optimizer updates, as pipeline.py:491 / :520-532 do
+        st = _train_state(radiance_field)
+        if "counts" in fwd:                                                    # a fused step: the optimizer call reports it
+            _report_step(st, fwd, optimizer)
+        else:
+            optimizer.step(skip=skip, count_nonfinite=True)
+        if scheduler is not None and st.sched_debt > 0:
+            st.sched_debt -= 1
+        elif scheduler is not None:
+            scheduler.step()
+        return _step_result(fwd, skip, False)
+    if isinstance(optimizer, FusedAdam):
+        # the non-finite count is added to the same flag and the update leaves everything untouched when it is raised — one C call for guard + three
+        # updates + handle refresh when the optimizer is bound to the field (`bind_field`)
+        optimizer.step(skip=skip, count_nonfinite=True)
+        skipped = bool(skip.item() > 0)                                        # one host round trip per iteration
+    else:
+        count_nan_gradients(radiance_field.parameters(), out=skip)             # pipeline.py:520-529
+        skipped = bool(skip.item() > 0)
+        optimizer.zero_grad() if skipped else optimizer.step()
+    if not skipped and scheduler is not None:
+        scheduler.step()
+    return _step_result(fwd, skipped, True)
+
+
+def _train_fused(batch, optimizer, scheduler, sync, data_parallel, data_parallel_group, presampled, seed, opts_kw):
+    """The fused forward + backward followed by `_apply_update`: synchronous steps of a data-parallel run or a host-stepped optimizer (two round
+    trips), and every asynchronous step (none).  None: the batch is not one for the fused path."""
+    if batch[1].levels > 4:
+        return None
+    if sync:
+        fwd = fused_forward_backward(*batch, presampled=presampled, seed=seed, **opts_kw)
+    else:
+        fwd = _launch_train_step(_train_state(batch[0]), *batch, presampled, _step_seed(presampled, seed), False, **opts_kw)
+    return None if fwd is None else _apply_update(batch[0], optimizer, scheduler, fwd, sync, data_parallel, data_parallel_group)
+
+
+def _train_autograd(batch, optimizer, scheduler, sync, data_parallel, data_parallel_group, stratified, **render_kw):
+    """The differentiable Python surface (`render_image_with_occgrid_with_depth_guide` + torch losses + autograd): fused=False, or a batch the fused call
+    handed over (more than four occupancy levels / a ray past the sampler's scratch row).  The reference's signature has no jitter switch (it follows
+    radiance_field.training, occ_grid.py:187-189): `stratified=False` is honoured by rendering in eval mode."""
+    import torch.nn.functional as F
+    radiance_field, estimator, rays, pixels, dep, sem, render_bkgd = batch
+    no_jitter = stratified is False and radiance_field.training
+    if no_jitter:
+        radiance_field.eval()
+    try:
+        rgb, acc, depth, semantic, n_rendering_samples = render_image_with_occgrid_with_depth_guide(
+            radiance_field, estimator, rays, render_bkgd=render_bkgd, depth=dep, **render_kw)
+    finally:
+        if no_jitter:
+            radiance_field.train()
+    dev = rays.origins.device
+    skip = torch.zeros((), dtype=torch.int32, device=dev)      # device flag: raised for a step without samples
+    optimizer.zero_grad()
+    if n_rendering_samples == 0:
+        # pipeline.py:491: `continue`.  With data_parallel the collective still has to be reached by this rank:
+        # it contributes zero gradients and a raised skip flag.
+        skip += 1
+        for p_ in radiance_field.parameters():
+            if p_.numel():
+                p_.grad = torch.zeros_like(p_)
+        loss = loss_rgb = loss_dep = loss_sem = torch.zeros((), device=dev)
+    else:
+        loss_rgb = F.smooth_l1_loss(rgb, pixels)
+        loss_dep = F.smooth_l1_loss(depth, dep.unsqueeze(1))
+        loss_sem = F.cross_entropy(semantic, sem)
+        loss = loss_rgb * 10 + loss_dep / 5 + loss_sem / 2
+        loss.backward()
+    fwd = dict(loss=loss, loss_rgb=loss_rgb, loss_dep=loss_dep, loss_sem=loss_sem, skip=skip, n_rendering_samples=n_rendering_samples)
+    return _apply_update(radiance_field, optimizer, scheduler, fwd, sync, data_parallel, data_parallel_group)
 
 
 def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, sem, render_bkgd, step: int,
@@ -681,8 +808,7 @@ def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, se
     `presampled` (fused path): the `presample()` token of THIS batch — its march ran beside the previous iteration; ignored (the step marches itself,
     with the token's jitter seed) if the occupancy refresh below or other options made it stale.
     Returns dict(loss, loss_rgb, loss_dep, loss_sem as device tensors, n_rendering_samples, skipped)."""
-    import torch.nn.functional as F
-    from .optim import FusedAdam, count_nan_gradients
+    from .optim import FusedAdam
     radiance_field.train()
     estimator.train()
     if presampled is not None and presampled.keep is not None and step % REFRESH_EVERY == 0:
@@ -695,135 +821,15 @@ def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, se
         raise ValueError("train_step(sync=False) needs fused=True and optim.FusedAdam (the skip decision is taken on the device)")
 
     occ_eval_fn = NA.FieldDensityOcc(radiance_field, render_step_size)     # pipeline.py:376-378; one fused C call per refresh
-
     estimator.update_every_n_steps(step=step, occ_eval_fn=occ_eval_fn, occ_thre=occ_thre, n=REFRESH_EVERY)
-    out = None
+    batch = (radiance_field, estimator, rays, pixels, dep, sem, render_bkgd)
+    render_kw = dict(near_plane=near_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre)
+    opts_kw = dict(render_kw, far_plane=1e10, early_stop_eps=1e-4, stratified=stratified, deterministic=deterministic)
     if fused and sync and device_guard and not data_parallel:
-        # The reference's loop form (n_rendering_samples and the skip decision on the host after every iteration) with ONE host round trip and no bubble on the GPU: render +
-        # loss + backward AND the guarded optimizer call are enqueued first, then the host waits once for the five words the optimizer's step-count kernel wrote into pinned
-        # memory.  (Rounds 1-3 read the counts between backward and optimizer — the GPU idled through a round trip and the optimizer's launch — and the flag after it.)
-        # A step beyond its sample bounds has raised the flag on the device: its optimizer call changed nothing, the bounds grow and the step is repeated.
-        st = _train_state(radiance_field)
-        dev = rays.origins.device
-        if seed is None and (presampled is None or presampled.keep is None):
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # one draw per iteration, whatever the number of attempts
-        c = None
-        for attempt in range(4):
-            out = fused_forward_backward(radiance_field, estimator, rays, pixels, dep, sem, render_bkgd, near_plane=near_plane,
-                                         render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre, sync=False,
-                                         stratified=stratified, deterministic=deterministic, presampled=presampled if attempt == 0 else None, seed=seed,
-                                         _defer_report=True)
-            if out is None:
-                break
-            if presampled is not None and attempt == 0:
-                seed = presampled.seed
-            host, ev, _ = out["_report"]
-            optimizer.step(skip=out["skip"], count_nonfinite=True, report=(out["counts"], host))
-            if not optimizer.reported:
-                host[:4].copy_(out["counts"], non_blocking=True)
-                host[4:5].copy_(out["skip"].reshape(1).to(torch.int64), non_blocking=True)
-            ev.record(torch.cuda.current_stream(dev))
-            ev.synchronize()                                            # the iteration's one host round trip
-            c = host.tolist()
-            st.setdefault("pinned", []).append((host, ev))
-            _check_status(c[3])
-            if c[3] & _ST_ROW:
-                out = None                                              # a ray longer than a scratch row: the autograd path below (the flagged optimizer call changed nothing)
-                break
-            if c[3] & (_ST_MARCHED | _ST_KEPT):
-                _grow_caps(st, c[0], c[1], rays.origins.reshape(-1, 3).shape[0], carry=False)
-                continue
-            break
-        else:
-            raise L.MnfError("train_step: sample bounds kept growing")
-        if out is not None:
-            skipped = c[4] > 0
-            estimator.last_sampling = {"n_marched": int(c[0])}
-            if not skipped and scheduler is not None:
-                scheduler.step()
-            if int(c[1]) == 0:
-                return dict(loss=None, n_rendering_samples=0, skipped=True)
-            return dict(loss=out["loss"].detach(), loss_rgb=out["loss_rgb"].detach(), loss_dep=out["loss_dep"].detach(), loss_sem=out["loss_sem"].detach(),
-                        n_rendering_samples=int(c[1]), skipped=skipped)
-        fused = False
-    if fused:
-        out = fused_forward_backward(radiance_field, estimator, rays, pixels, dep, sem, render_bkgd, near_plane=near_plane,
-                                     render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre, sync=sync,
-                                     stratified=stratified, deterministic=deterministic, presampled=presampled, seed=seed,
-                                     _defer_report=(not sync and device_guard))
-    if out is not None:
-        n_rendering_samples = out["n_rendering_samples"]
-        loss, loss_rgb, loss_dep, loss_sem = out["loss"], out["loss_rgb"], out["loss_dep"], out["loss_sem"]
-        skip = out["skip"]                         # device flag: raised by the C call for a step without samples
+        res = _train_fused_one_trip(batch, optimizer, scheduler, presampled, seed, opts_kw)
     else:
-        # the autograd route (fused=False, or the fused call handed the batch over: more than four occupancy levels / a ray past the sampler's scratch row).  The
-        # reference's signature has no jitter switch (it follows radiance_field.training, occ_grid.py:187-189): `stratified=False` is honoured by rendering in eval mode
-        no_jitter = stratified is False and radiance_field.training
-        if no_jitter:
-            radiance_field.eval()
-        try:
-            rgb, acc, depth, semantic, n_rendering_samples = render_image_with_occgrid_with_depth_guide(
-                radiance_field, estimator, rays, near_plane=near_plane, render_step_size=render_step_size, render_bkgd=render_bkgd,
-                cone_angle=cone_angle, alpha_thre=alpha_thre, depth=dep)
-        finally:
-            if no_jitter:
-                radiance_field.train()
-        dev = rays.origins.device
-        skip = torch.zeros((), dtype=torch.int32, device=dev)
-        optimizer.zero_grad()
-        if n_rendering_samples == 0:
-            # pipeline.py:491: `continue`.  With data_parallel the collective below still has to be reached by this rank:
-            # it contributes zero gradients and a raised skip flag.
-            skip += 1
-            for p_ in radiance_field.parameters():
-                if p_.numel():
-                    p_.grad = torch.zeros_like(p_)
-            loss = loss_rgb = loss_dep = loss_sem = torch.zeros((), device=dev)
-        else:
-            loss_rgb = F.smooth_l1_loss(rgb, pixels)
-            loss_dep = F.smooth_l1_loss(depth, dep.unsqueeze(1))
-            loss_sem = F.cross_entropy(semantic, sem)
-            loss = loss_rgb * 10 + loss_dep / 5 + loss_sem / 2
-            loss.backward()
-    if data_parallel:
-        allreduce_gradients(radiance_field.parameters(), data_parallel_group, skip)
-    if device_guard:
-        # pipeline.py:520-532: the non-finite count is added to the same flag and the update leaves everything untouched when it is
-        # raised — one C call for guard + three updates + handle refresh when the optimizer is bound to the field (`bind_field`)
-        rep_ = out.get("_report") if out is not None else None
-        optimizer.step(skip=skip, count_nonfinite=True, report=(out["counts"], rep_[0]) if rep_ is not None else None)
-        if not sync:
-            st = _train_state(radiance_field)
-            # the step's counters and its FINAL skip flag (the optimizer's non-finite guard included) travel to pinned host memory; when they arrive — one or two
-            # calls later — a skipped step takes back the scheduler step it was given here: the schedule counts optimizer updates, as pipeline.py:491 / :520-532 do
-            if rep_ is not None:
-                host, ev, r_ = rep_
-                if not optimizer.reported:                         # (an optimizer not bound to the field: the copies the bound one's step-count kernel replaces)
-                    host[:4].copy_(out["counts"], non_blocking=True)
-                    host[4:5].copy_(skip.reshape(1).to(torch.int64), non_blocking=True)
-                ev.record(torch.cuda.current_stream(rays.origins.device))
-                st["pending"].append((host, ev, r_))
-            if scheduler is not None:
-                if st.get("sched_debt", 0) > 0:
-                    st["sched_debt"] -= 1
-                else:
-                    scheduler.step()
-            return dict(loss=loss.detach(), loss_rgb=loss_rgb.detach(), loss_dep=loss_dep.detach(), loss_sem=loss_sem.detach(),
-                        n_rendering_samples=n_rendering_samples, skipped=skip)
-        skipped = bool(skip.item() > 0)                                        # one host round trip per iteration
-    else:
-        count_nan_gradients(radiance_field.parameters(), out=skip)             # pipeline.py:520-529
-        skipped = bool(skip.item() > 0)
-        if skipped:
-            optimizer.zero_grad()
-        else:
-            optimizer.step()
-    if not skipped and scheduler is not None:
-        scheduler.step()
-    if isinstance(n_rendering_samples, int) and n_rendering_samples == 0:
-        return dict(loss=None, n_rendering_samples=0, skipped=True)
-    return dict(loss=loss.detach(), loss_rgb=loss_rgb.detach(), loss_dep=loss_dep.detach(), loss_sem=loss_sem.detach(),
-                n_rendering_samples=n_rendering_samples, skipped=skipped)
+        res = _train_fused(batch, optimizer, scheduler, sync, data_parallel, data_parallel_group, presampled, seed, opts_kw) if fused else None
+    return res if res is not None else _train_autograd(batch, optimizer, scheduler, sync, data_parallel, data_parallel_group, stratified, **render_kw)
 
 
 _ENSEMBLE_STREAMS = {}
@@ -1048,8 +1054,9 @@ def score_views(radiance_fields, estimators, poses, width, height, focal, near_p
         # profiles/r03_hw_queues.txt: two members are cut into two groups of views each, one member into four; rays stay in row-major
         # march order — the 8x8-block order of full images buys nothing on 64x64 sub-sampled views: profiles/r03_split_experiment.txt)
         M = len(radiance_fields)
-        outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], h * w, 1024, near_plane, 1e10, render_step_size,
-                            torch.zeros(3), cone_angle, alpha_thre, 1e-4, True, 8, None, max(1, 4 // M))
+        outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], h * w, max_samples=1024, near_plane=near_plane, far_plane=1e10,
+                            render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=1e-4,
+                            probabilistic=True, n_split=max(1, 4 // M))
         totals = [r["total"] for r in outs]
         rv = [r["rgb_var"].reshape(n, h * w, 3) for r in outs]; dv = [r["depth_var"].reshape(n, h * w) for r in outs]
         ac = [r["acc"].reshape(n, h * w) for r in outs]; sm = [r["sem"].reshape(n, h * w, -1) for r in outs]
@@ -1064,7 +1071,6 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
                 alpha_thre, device="cuda:0"):
     """`score_views` on one rank as ONE C call (`mnf_score_poses`, csrc/trainstep.hip): poses -> the sub-sampled rays of every
     view -> probabilistic renders by every ensemble member -> per-view terms.  Returns (terms [V,4] float64, score)."""
-    import ctypes
     lib = L.load_library()
     poses = np.asarray(poses)
     V, M = poses.shape[0], len(radiance_fields)
@@ -1072,21 +1078,16 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
     h, w = int(height * scale), int(width * scale)
     idx = torch.from_numpy(subsample_indices(width * height, h * w)).to(device)
     handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in radiance_fields])
-    grids = [_grid_levels(e) for e in estimators]
-    bins = (ctypes.c_void_p * M)(*[g[0].data_ptr() for g in grids])
-    bits = (ctypes.c_void_p * M)(*[e.bitgrid()[0].data_ptr() for e in estimators])
-    opts = L.RenderOpts()
-    opts.near_plane, opts.far_plane, opts.render_step_size = near_plane, 1e10, render_step_size
-    opts.cone_angle, opts.alpha_thre, opts.early_stop_eps = cone_angle, alpha_thre, 1e-4
-    opts.max_samples, opts.probabilistic, opts.rays_per_view, opts.sync_every = 1024, 1, h * w, 8
-    opts.view_order = None                                # row-major march order, as `score_views`
-    opts.n_levels = len(grids[0][1]) // 6
+    grids = [_grid_args(e) for e in estimators]
+    bins = (ctypes.c_void_p * M)(*[g.binaries.data_ptr() for g in grids])
+    bits = (ctypes.c_void_p * M)(*[g.bits.data_ptr() for g in grids])
+    opts = _render_opts(max_samples=1024, near_plane=near_plane, far_plane=1e10, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,
+                        early_stop_eps=1e-4, probabilistic=True, rays_per_view=h * w, n_levels=grids[0].n_levels)      # row-major march order, as `score_views`
     C = radiance_fields[0].num_semantic_classes
     nbytes = int(lib.mnf_score_poses_workspace_bytes(M, V, h * w, C))
     ws = _workspace(torch.device(device), nbytes)
     terms = torch.empty(V, 4, dtype=torch.float64, device=device)
-    res = grids[0][0].shape[1:]
-    L.launch(lib.mnf_score_poses, handles, bins, bits, M, res[0], res[1], res[2], (ctypes.c_float * len(grids[0][1]))(*grids[0][1]), L.ptr(c2w), V, width,
+    L.launch(lib.mnf_score_poses, handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, width,
              height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(opts), L.ptr(terms), L.ptr(ws), nbytes)
     return terms, trajectory_score(terms)
 
@@ -1198,8 +1199,8 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
         o = torch.empty(V * P, 3, device=dev)
         d = torch.empty(V * P, 3, device=dev)
         L.launch(lib.mnf_generate_rays, L.ptr(c2w), V, W, H, dataset._focal, None, P, L.ptr(o), L.ptr(d))
-        r = _render_jobs([(radiance_field, estimator, o, d)], P, max_samples, near_plane, 1e10, render_step_size, bkgd, cone_angle, alpha_thre,
-                         1e-4, False, 8, (H, W), None)[0]
+        r = _render_jobs([(radiance_field, estimator, o, d)], P, max_samples=max_samples, near_plane=near_plane, far_plane=1e10, render_step_size=render_step_size,
+                         render_bkgd=bkgd, cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=1e-4, probabilistic=False, image_hw=(H, W), n_split=None)[0]
         m = eval_metrics(r["rgb"], r["depth"], r["sem"], dataset, ids, None, confusion=True, labels=labels and return_images)
         rows.append(m["metrics"])
         conf = m["confusion"] if conf is None else conf + m["confusion"]

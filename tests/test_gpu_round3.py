@@ -106,11 +106,11 @@ def test_train_step_flags_bad_labels_and_recovers_from_small_bounds():
     key = id(hip)
     R_ = o.shape[0]
     small = dict(by_R={R_: (2048, 1024)}, abs_m=0, abs_k=0, per_m=0.0, per_k=0.0)
-    RD._TRAIN_STATE[key].update(small)                            # far too small
+    vars(RD._TRAIN_STATE[key]).update(small)                            # far too small
     out = RD.fused_forward_backward(hip, est, RD.Rays(o, d), pix, dep, lab, None, stratified=False, **H.RENDER_KW)
-    assert out["n_rendering_samples"] == n_ok and RD._caps_for(RD._TRAIN_STATE[key], o.shape[0])[1] >= n_ok       # repeated with larger bounds
+    assert out["n_rendering_samples"] == n_ok and RD._TRAIN_STATE[key].caps(o.shape[0])[1] >= n_ok       # repeated with larger bounds
     np.testing.assert_allclose(hip.mlp_head.params.grad.cpu().numpy(), g_ok.cpu().numpy(), rtol=2e-2, atol=1e-6)
-    RD._TRAIN_STATE[key].update(dict(small, by_R={R_: (2048, 1024)}))
+    vars(RD._TRAIN_STATE[key]).update(dict(small, by_R={R_: (2048, 1024)}))
     lazy = RD.fused_forward_backward(hip, est, RD.Rays(o, d), pix, dep, lab, None, stratified=False, sync=False, **H.RENDER_KW)
     assert int(lazy["skip"]) > 0 and int(lazy["counts"][3]) & 1 and float(hip.mlp_head.params.grad.abs().max()) == 0.0
     # WITHOUT any synchronisation by the caller the bounds are corrected at most two calls late (per bound: marched, then surviving)

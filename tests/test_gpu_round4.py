@@ -89,7 +89,7 @@ def test_dynamic_ray_count_schedule_async_matches_sync():
     hip, rs2, loss_async, _ = run(False, rs)
     assert len(RD._TRAIN_STATE) <= n_states + 1                          # one more field, ONE state for its 40 different ray counts
     st = RD._TRAIN_STATE[id(hip)]
-    assert len(st["pending"]) + len(st.get("pinned", [])) <= 4 and st.get("overflowed_steps", 0) == 0
+    assert len(st.pending) + len(st.pinned) <= 4 and st.overflowed_steps == 0
     assert RD.latest_step_counts(hip) is not None and RD.latest_step_counts(hip)[0] in rs
     np.testing.assert_allclose(loss_async, loss_sync, rtol=5e-3)
     # a flagged step among changing ray counts is not lost: the error surfaces within the next two calls
@@ -368,7 +368,7 @@ def test_presampled_steps_are_bitwise_the_steps_that_march_themselves():
     tok = RD.presample(f, e, data[1][0], **kw)
     tok.rays = (data[2][0].origins, data[2][0].viewdirs)
     tok.R = data[2][0].origins.shape[0]
-    tok.cap_m = RD._caps_for(RD._train_state(f), tok.R)[0]
+    tok.cap_m = RD._train_state(f).caps(tok.R)[0]
     tok.keep = (L.contig(data[2][0].origins.reshape(-1, 3), torch.float32),) + tuple(tok.keep[1:])
     with pytest.raises(L.MnfError, match="presampled was made for other rays"):
         RD.train_step(f, e, opt, *data[2], step=3, deterministic=True, presampled=tok, **kw)
@@ -391,7 +391,7 @@ def test_async_scheduler_counts_optimizer_updates_not_calls():
     opt = FusedAdam(f.parameters(), lr=1e-3, eps=1e-15).bind_field(f)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=1, gamma=0.99)
     st = RD._train_state(f)
-    st["by_R"][n] = (1 << 18, 64)                                                  # a surviving-sample bound every early step overflows: skipped on the device, the bound grows late
+    st.by_R[n] = (1 << 18, 64)                                                  # a surviving-sample bound every early step overflows: skipped on the device, the bound grows late
     outs = [RD.train_step(f, e, opt, *batch, step=1 + k, sync=False, stratified=False, scheduler=sched, **H.RENDER_KW) for k in range(12)]
     torch.cuda.synchronize()
     skipped = sum(int(o_["skipped"]) > 0 for o_ in outs)
@@ -402,7 +402,7 @@ def test_async_scheduler_counts_optimizer_updates_not_calls():
         outs.append(RD.train_step(f, e, opt, *batch, step=20 + k, sync=False, stratified=False, scheduler=sched, **H.RENDER_KW))
     torch.cuda.synchronize()
     assert not any(int(o_["skipped"]) for o_ in outs[12:])
-    assert st.get("skipped_steps", 0) == skipped and st.get("sched_debt", 0) == 0
+    assert st.skipped_steps == skipped and st.sched_debt == 0
     assert sched.last_epoch == 15 - skipped                                        # one scheduler step per optimizer update
     np.testing.assert_allclose(opt.param_groups[0]["lr"], 1e-3 * 0.99 ** (15 - skipped), rtol=1e-6)
 
@@ -425,7 +425,7 @@ def test_presampled_step_beyond_its_marched_bound_is_skipped_like_a_step_that_ma
         f, e = H.hip_field(sc).train(), H.hip_estimator(sc)
         opt = FusedAdam(f.parameters(), lr=1e-3, eps=1e-15).bind_field(f)
         st = RD._train_state(f)
-        st["by_R"][n] = (4096, 1 << 20)                                            # far fewer marched samples than this batch has
+        st.by_R[n] = (4096, 1 << 20)                                            # far fewer marched samples than this batch has
         p0 = [p.detach().clone() for p in f.parameters() if p.numel()]
         tok = RD.presample(f, e, batch[0], seed=7, stratified=False, **H.RENDER_KW) if pre else None
         out = RD.fused_forward_backward(f, e, *batch[:4], render_bkgd=bk, sync=False, stratified=False, presampled=tok, seed=7, **H.RENDER_KW)

@@ -97,7 +97,7 @@ def _dynamic_factory(cx, R_cap, target):
         def finish(res, outs, n_all, tf_):
             seen = dyn["seen"][-res["steps"]:]
             res.update({"rays_per_step_mean": float(np.mean(seen)), "rays_per_step_min_max": [int(min(seen)), int(max(seen))], "distinct_ray_counts": len(set(seen)),
-                        "target_sample_batch_size": target, "overflowed_steps": RD._TRAIN_STATE[id(tf_)].get("overflowed_steps", 0)})
+                        "target_sample_batch_size": target, "overflowed_steps": RD._TRAIN_STATE[id(tf_)].overflowed_steps})
         return tstep, finish
     return factory
 

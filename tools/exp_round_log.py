@@ -22,7 +22,8 @@ if len(sys.argv) > 2 and sys.argv[2] == "score":      # one render job of a scor
     field.eval(); est.eval()
     poses = SI._free_space_poses(scene, 256, seed=9)[:V]
     o, d, h, w = RD._pose_rays(poses, 640, 640, 320.0, 0.1, dev)
-    outs = RD._render_jobs([(field, est, o, d)], h * w, 1024, 0.1, 1e10, 1e-3, torch.zeros(3), 0.004, 0.01, 1e-4, True, 8, None, 1)
+    outs = RD._render_jobs([(field, est, o, d)], h * w, max_samples=1024, near_plane=0.1, far_plane=1e10, render_step_size=1e-3, render_bkgd=torch.zeros(3),
+                           cone_angle=0.004, alpha_thre=0.01, early_stop_eps=1e-4, probabilistic=True, n_split=1)
     torch.cuda.synchronize()
     print(f"[exp_round_log] score job, {V} views of {h * w} rays: {float(outs[0]['total'][1]) / (V * h * w):.2f} evaluated samples per ray", flush=True)
     sys.exit(0)

@@ -18,7 +18,7 @@ views = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [256,
 passes = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 if len(sys.argv) > 3:
     _jobs, _n = RD._render_jobs, int(sys.argv[3])
-    RD._render_jobs = lambda *a, **k: _jobs(*a[:13], _n) if len(a) > 13 else _jobs(*a, **dict(k, n_split=_n))
+    RD._render_jobs = lambda *a, **k: _jobs(*a, **dict(k, n_split=_n))
 dev = "cuda:0"
 scene = SC.make_scene("102344250", n_poses=40)
 f0, e0, _ = SI.train_standin(scene, dev, seed=9)

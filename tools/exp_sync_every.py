@@ -26,7 +26,8 @@ def run(V, sync_every, n_split, reps=5):
     ts = []
     for _ in range(reps):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        RD._render_jobs([(f0, e0, o, d), (f1, e1, o, d)], h * w, 1024, 0.1, 1e10, 1e-3, torch.zeros(3), 0.004, 0.01, 1e-4, True, sync_every, None, n_split)
+        RD._render_jobs([(f0, e0, o, d), (f1, e1, o, d)], h * w, max_samples=1024, near_plane=0.1, far_plane=1e10, render_step_size=1e-3, render_bkgd=torch.zeros(3),
+                        cone_angle=0.004, alpha_thre=0.01, early_stop_eps=1e-4, probabilistic=True, sync_every=sync_every, n_split=n_split)
         torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
     return 1e3 * float(np.median(ts))
 

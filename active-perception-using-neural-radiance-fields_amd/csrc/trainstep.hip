@@ -6,6 +6,9 @@
 //                     loss (pipeline.py:506-511) and `loss.backward()` down to the three flat parameter-gradient vectors.
 //                     The optimizer step and the NaN guard stay with the caller (pipeline.py:520-532), as does the occupancy
 //                     refresh (mnf_update_occupancy).
+//   mnf_train_render_forward / mnf_train_render_backward
+//                     the same step cut at its loss: pipeline.py:472-489 now, `loss.backward()` (pipeline.py:518) later with whatever gradients the caller's own
+//                     loss produced for the four rendered planes.  Same kernels in the same order on either side of the cut (step_forward / step_backward).
 //   mnf_score_poses   pipeline.py:674-781 for one trajectory: poses -> sub-sampled rays -> probabilistic renders of every
 //                     ensemble member -> per-view predictive-information terms.
 //
@@ -272,6 +275,82 @@ __global__ void __launch_bounds__(256) guard_kept_kernel(int32_t n_rays, int64_t
 
 __global__ void set3_kernel(float *dst, float a, float b, float c) { dst[0] = a; dst[1] = b; dst[2] = c; }
 
+// mnf_train_render_forward's tail: the four per-ray planes from the workspace (where the backward reads the opacity and the depth again) into the caller's
+// buffers, the head kernel's block ticket back to 0, and the forward's verdict (a guard fired, or nothing survived) into the word behind the ticket: the backward's
+// head reads it there, a word no block of its own launch writes
+__global__ void __launch_bounds__(256) outputs_kernel(int64_t n_rays, int32_t C, const float *__restrict__ o_rgb, const float *__restrict__ o_acc,
+                                                      const float *__restrict__ o_dep, const float *__restrict__ o_sem, float *__restrict__ rgb,
+                                                      float *__restrict__ acc, float *__restrict__ dep, float *__restrict__ sem, const int32_t *__restrict__ skip,
+                                                      uint32_t *__restrict__ ticket) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) { ticket[0] = 0u; ticket[1] = *skip > 0 ? 1u : 0u; }
+    if (i < n_rays) { acc[i] = o_acc[i]; dep[i] = o_dep[i]; }
+    if (i < n_rays * 3) rgb[i] = o_rgb[i];
+    if (i < n_rays * C) sem[i] = o_sem[i];
+}
+
+// mnf_train_render_backward's head, in planes_kernel's manner (its fills ride on one launch): the three parameter-gradient vectors are zeroed and the caller's
+// four output gradients are read through their strides (autograd hands over expanded stride-0 tensors for `x.mean()` and transposed views for other losses)
+// into the workspace's dense per-ray arrays.  NULL = zero.  A non-finite incoming value — `loss.backward()` of a NaN loss — is stored as 0 and raises status
+// bit 32 and the skip flag; the last block to finish then clears the surviving-sample count the kernels behind it work on, so the step yields zero
+// gradients (pipeline.py:520-529 decided on the device).  With the forward's verdict raised (outputs_kernel's word) every array is zeroed (wave-uniform: one word, constant over the launch).
+struct GradIn { const float *p; int64_t rs, cs; };      // a [rows, cols] gradient: element (r, c) at p[r * rs + c * cs]
+struct GradFills { float *g_base, *g_head, *g_sem; int64_t n_base, n_head, n_sem; };
+__device__ __forceinline__ float finite_or_flag(float v, bool &bad) {
+    if ((__float_as_uint(v) & 0x7F800000u) != 0x7F800000u) return v;
+    bad = true;
+    return 0.f;
+}
+__device__ __forceinline__ bool read_gradient(float *dst, const GradIn g, int64_t rows, int32_t cols, bool dead, int64_t tid, int64_t threads) {
+    const int64_t n = rows * cols;
+    if (dead || !g.p) { fill_zero(dst, n, tid, threads); return false; }
+    bool bad = false;
+    const bool dense = cols == 1 ? g.rs == 1 : (g.cs == 1 && g.rs == cols);
+    if (dense) {      // 16-byte loads from the source's first 16-byte boundary on, scalar head and tail (fill_zero's shape); `dst` is 256-byte aligned
+        const int64_t head = ((16 - (reinterpret_cast<uintptr_t>(g.p) & 15)) & 15) / 4;
+        const int64_t h = head < n ? head : n;
+        for (int64_t i = tid; i < h; i += threads) dst[i] = finite_or_flag(g.p[i], bad);
+        const float4 *q = reinterpret_cast<const float4 *>(g.p + h);
+        const int64_t nq = (n - h) / 4;
+        for (int64_t i = tid; i < nq; i += threads) {
+            const float4 v = q[i];
+            const float4 o = float4{finite_or_flag(v.x, bad), finite_or_flag(v.y, bad), finite_or_flag(v.z, bad), finite_or_flag(v.w, bad)};
+            float *d = dst + h + i * 4;
+            if (h == 0) *reinterpret_cast<float4 *>(d) = o;
+            else { d[0] = o.x; d[1] = o.y; d[2] = o.z; d[3] = o.w; }
+        }
+        for (int64_t i = h + nq * 4 + tid; i < n; i += threads) dst[i] = finite_or_flag(g.p[i], bad);
+    } else {
+        for (int64_t i = tid; i < n; i += threads) {
+            const int64_t r = i / cols, c = i - r * cols;
+            dst[i] = finite_or_flag(g.p[r * g.rs + c * g.cs], bad);
+        }
+    }
+    return bad;
+}
+__global__ void __launch_bounds__(256) gradients_in_kernel(int32_t n_rays, int32_t C, const GradIn i_rgb, const GradIn i_acc, const GradIn i_dep, const GradIn i_sem,
+                                                           float *__restrict__ g_rgb, float *__restrict__ g_acc, float *__restrict__ g_dep,
+                                                           float *__restrict__ g_sem, const GradFills z, int64_t *counts_dev, int32_t *skip,
+                                                           int64_t *eff /* [1]: surviving samples the backward works on */, uint32_t *ticket) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, threads = (int64_t)gridDim.x * blockDim.x;
+    fill_zero(z.g_base, z.n_base, tid, threads); fill_zero(z.g_head, z.n_head, tid, threads); fill_zero(z.g_sem, z.n_sem, tid, threads);
+    const bool dead = ticket[1] != 0u;      // the forward found nothing to render (its verdict as outputs_kernel left it: not the flag blocks of this launch raise)
+    bool bad = read_gradient(g_rgb, i_rgb, n_rays, 3, dead, tid, threads);
+    bad |= read_gradient(g_acc, i_acc, n_rays, 1, dead, tid, threads);
+    bad |= read_gradient(g_dep, i_dep, n_rays, 1, dead, tid, threads);
+    bad |= read_gradient(g_sem, i_sem, n_rays, C, dead, tid, threads);
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    if (threadIdx.x == 0) {
+        // (the flag is raised, read and ordered by device-scope atomics only; the fence — a write-back of the L2 the fills have just dirtied — is paid by a
+        //  block that raised it, which orders its raise in front of its ticket, and by no other)
+        if (any_bad) { atomicOr(reinterpret_cast<unsigned long long *>(counts_dev + 3), 32ull); atomicAdd(skip, 1); __threadfence(); }
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {      // every other block has raised its flag, if it had to
+            if (atomicAdd(skip, 0) > 0) eff[1] = 0;
+            ticket[0] = 0u;
+        }
+    }
+}
+
 struct StepWs {
     float *nearp, *farp, *scratch_ts, *scratch_te, *alpha_thre;
     int64_t *counts, *starts, *kept_cnts, *kept_starts, *totals, *scan;
@@ -281,10 +360,15 @@ struct StepWs {
     int64_t *k_ray;
     void *rows; int64_t *k_src;        // the pre-pass's feature rows [max_marched][64] x 16 bit and every surviving sample's row (field_rows_supported)
     float *o_rgb, *o_acc, *o_dep, *o_sem, *g_rgb, *g_dep, *g_sem;   // per ray
+    float *g_acc;                      // per ray: the caller's opacity gradient (mnf_train_render_backward; the step's own loss has none)
     void *field_ws;
     int64_t field_ws_bytes, bytes;
 };
 
+// The two small blocks' words.  `alpha_thre` (64 floats): [0] the threshold, [8..10] a by-value background colour (set3_kernel), [16..19] the loss terms of a
+// mnf_train_render_forward (render_losses).  `totals` (256 int64): [0..2] marched, kept, longest ray, [4..5] `eff`, the counts the kernels behind the guards work
+// on, [7] the pre-pass's work counter, [8..135] the occupancy mean's partial sums, [160..163] a presample's report (kPreReport), [200] mnf_train_render_*'s
+// block ticket (low half) and forward verdict (high half) (render_ticket).  A new user takes words not listed here, and lists them.
 StepWs carve_step(char *base, mnf_field_t f, int64_t R, int32_t cap, int64_t max_marched, int64_t max_kept) {
     StepWs w;
     size_t off = 0;
@@ -305,6 +389,7 @@ StepWs carve_step(char *base, mnf_field_t f, int64_t R, int32_t cap, int64_t max
     if (field_rows_supported(f)) { w.rows = take((size_t)max_marched * 128); w.k_src = (int64_t *)take(max_kept * 8); }
     w.field_ws_bytes = mnf_field_train_workspace_bytes(f, max_kept);
     w.field_ws = take((size_t)w.field_ws_bytes);
+    w.g_acc = (float *)take(R * 4);      // (behind everything else: every other offset is what it was)
     w.bytes = (int64_t)off;
     return w;
 }
@@ -455,30 +540,24 @@ extern "C" int mnf_train_presample(mnf_presample_t p, const uint8_t *binaries, c
     return MNF_OK;
 }
 
-extern "C" int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
-                              int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
-                              const float *target_rgb, const float *target_depth, const int64_t *target_sem, const mnf_train_opts *opts,
-                              float *g_base, float *g_head, float *g_sem, float *losses, int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched,
-                              int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MNF_REQUIRE(f && f->params_loaded && opts && aabb_host && counts_dev && skip_dev, "train_step: bad handle or options");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_step: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
-    MNF_REQUIRE(binaries && occs && rays_o && rays_d && target_rgb && target_depth && target_sem && g_base && g_head && g_sem && losses && workspace,
-                "train_step: null pointer");
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->render_step_size > 0.f, "train_step: bad sizes");
+namespace mnf {
+namespace {
+// A step in front of its loss — planes and fills, alpha threshold, march, guards, compaction, ray-major density pre-pass leaving its feature rows, visibility filter,
+// forward_train reading the rows, compositing forward — and behind it.  mnf_train_step is the two with loss_kernel in between; mnf_train_render_forward /
+// _backward are the same two with the caller's own loss in between.  Whatever the second half reads of the first lies in the workspace `w` was carved from.
+int step_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y, int32_t res_z,
+                 const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays, const mnf_train_opts *opts, StepFills fills, float *losses,
+                 int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, StepWs &w, int64_t *&eff, const float *&bk, mnf_stream_t stream) {
     hipStream_t s = as_stream(stream);
     const int32_t cap = scratch_cap(n_rays);
-    StepWs w = carve_step((char *)workspace, f, n_rays, cap, max_marched, max_kept);
-    if (workspace_bytes < w.bytes) { set_error("train_step: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
     const int C = f->cfg.num_semantic_classes;
     const int rblocks = (n_rays + 255) / 256;
     // (losses, counters, skip flag, the three gradient vectors, the pre-pass's density array and work counter: zeroed by planes_kernel)
-    int64_t *eff = w.totals + 4;                                           // [0] marched, [1] kept samples the kernels behind the guards work on
+    eff = w.totals + 4;                                                    // [0] marched, [1] kept samples the kernels behind the guards work on
     // ---- occupancy sampling (occ_grid.py:80-238): march, density pre-pass, visibility filter
     const int n_levels = opts->n_levels > 1 ? opts->n_levels : 1;
     MNF_REQUIRE(n_levels <= 4, "train_step: at most 4 occupancy levels");
     int rc = 0;
-    StepFills fills = {g_base, g_head, g_sem, w.sigma, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem, max_marched, nullptr, nullptr};
     if (const mnf_presample_s *pre = opts->presampled) {
         // the march of THIS batch ran earlier, on a side stream beside the previous step (mnf_train_presample): adopt what it left, after its last kernel
         MNF_REQUIRE(pre->valid && pre->rays_o == rays_o && pre->rays_d == rays_d && pre->n_rays == n_rays && pre->binaries == binaries && pre->seed == opts->seed &&
@@ -550,29 +629,118 @@ extern "C" int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint
         rc = forward_train(f, io, w.field_ws, w.field_ws_bytes, s, opts->deterministic != 0);
         if (rc) return rc;
     }
-    const float *bk = opts->render_bkgd_dev;                               // the caller's device colour, or the by-value one
+    bk = opts->render_bkgd_dev;                                            // the caller's device colour, or the by-value one
     if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) {
         float *bkd = w.alpha_thre + 8;                                     // three floats of the small scalar block
         hipLaunchKernelGGL(set3_kernel, dim3(1), dim3(1), 0, s, bkd, opts->render_bkgd[0], opts->render_bkgd[1], opts->render_bkgd[2]);
         bk = bkd;
     }
-    rc = composite_train_forward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.o_rgb, w.o_acc,
-                                      w.o_dep, w.o_sem, w.k_w, w.k_tr, nullptr, stream);
-    if (rc) return rc;
-    // ---- loss (pipeline.py:506-511) and backward (pipeline.py:518)
-    hipLaunchKernelGGL(loss_kernel, dim3(rblocks), dim3(256), 0, s, n_rays, C, w.o_rgb, w.o_dep, w.o_sem, target_rgb, target_depth, target_sem,
-                       w.g_rgb, w.g_dep, w.g_sem, losses, counts_dev + 3, skip_dev);
-    rc = launch_status("loss_kernel");
-    if (rc) return rc;
+    return composite_train_forward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.o_rgb, w.o_acc,
+                                        w.o_dep, w.o_sem, w.k_w, w.k_tr, nullptr, stream);
+}
+
+// composite_train_backward (g_acc: the caller's opacity gradient, or NULL), the factored output gradient, the field's backward
+int step_backward(mnf_field_t f, const StepWs &w, int32_t n_rays, const mnf_train_opts *opts, const float *bk, const float *g_acc, int64_t *eff, int64_t max_kept,
+                  float *g_base, float *g_head, float *g_sem, mnf_stream_t stream) {
+    const int C = f->cfg.num_semantic_classes;
     // the rgb / semantic output gradients of a sample are its weight times its ray's loss gradient: the split backward forms them itself from (k_w, k_ray, g_rgb, g_sem)
     // — 12 bytes per sample and cached per-ray vectors instead of 128 bytes written here and read there; the fused backward (mode 2) reads the per-sample arrays
     const bool factored = C > 0;
-    rc = composite_train_backward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.k_w, w.k_tr, w.o_acc,
-                                       w.o_dep, w.g_rgb, nullptr, w.g_dep, w.g_sem, w.k_dsig, factored ? nullptr : w.k_drgb, factored ? nullptr : w.k_dsem, stream);
+    int rc = composite_train_backward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.k_w, w.k_tr, w.o_acc,
+                                           w.o_dep, w.g_rgb, g_acc, w.g_dep, w.g_sem, w.k_dsig, factored ? nullptr : w.k_drgb, factored ? nullptr : w.k_dsem, stream);
     if (rc) return rc;
     if (factored) set_factored_output_gradient(FactoredGrad{w.k_w, w.k_ray, w.g_rgb, w.g_sem});
     return backward(f, w.k_pos, max_kept, eff + 1, w.k_drgb, w.k_dsig, w.k_dsem, w.k_rgb, w.k_sigma, w.field_ws, w.field_ws_bytes, opts->loss_scale, g_base,
-                    g_head, g_sem, false, true, opts->deterministic != 0, s);
+                    g_head, g_sem, false, true, opts->deterministic != 0, as_stream(stream));
+}
+}  // namespace
+}  // namespace mnf
+
+extern "C" int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
+                              int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
+                              const float *target_rgb, const float *target_depth, const int64_t *target_sem, const mnf_train_opts *opts,
+                              float *g_base, float *g_head, float *g_sem, float *losses, int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched,
+                              int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MNF_REQUIRE(f && f->params_loaded && opts && aabb_host && counts_dev && skip_dev, "train_step: bad handle or options");
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_step: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
+                opts->struct_size, sizeof(mnf_train_opts));
+    MNF_REQUIRE(binaries && occs && rays_o && rays_d && target_rgb && target_depth && target_sem && g_base && g_head && g_sem && losses && workspace,
+                "train_step: null pointer");
+    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->render_step_size > 0.f, "train_step: bad sizes");
+    hipStream_t s = as_stream(stream);
+    StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
+    if (workspace_bytes < w.bytes) { set_error("train_step: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    const StepFills fills = {g_base, g_head, g_sem, w.sigma, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem, max_marched, nullptr, nullptr};
+    int64_t *eff = nullptr;
+    const float *bk = nullptr;
+    int rc = step_forward(f, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, fills, losses, counts_dev, skip_dev, max_marched, max_kept,
+                          w, eff, bk, stream);
+    if (rc) return rc;
+    // ---- loss (pipeline.py:506-511) and backward (pipeline.py:518)
+    hipLaunchKernelGGL(loss_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, s, n_rays, f->cfg.num_semantic_classes, w.o_rgb, w.o_dep, w.o_sem, target_rgb, target_depth,
+                       target_sem, w.g_rgb, w.g_dep, w.g_sem, losses, counts_dev + 3, skip_dev);
+    rc = launch_status("loss_kernel");
+    if (rc) return rc;
+    return step_backward(f, w, n_rays, opts, bk, nullptr, eff, max_kept, g_base, g_head, g_sem, stream);
+}
+
+// The step cut at its loss (include/mi355nerf.h): step_forward now, step_backward later with the caller's gradients.  The words of the workspace's small blocks that
+// only this pair uses (the blocks' map is at carve_step): four floats for the loss terms planes_kernel zeroes (nobody reads them), the head kernel's block ticket
+// and, in the 32 bits behind it, the forward's verdict.
+static inline float *render_losses(const StepWs &w) { return w.alpha_thre + 16; }
+static inline uint32_t *render_ticket(const StepWs &w) { return reinterpret_cast<uint32_t *>(w.totals + 200); }
+
+extern "C" int mnf_train_render_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
+                                        int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
+                                        const mnf_train_opts *opts, float *rgb, float *acc, float *depth, float *sem, int64_t *counts_dev, int32_t *skip_dev,
+                                        int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MNF_REQUIRE(f && f->params_loaded && opts && aabb_host && counts_dev && skip_dev, "train_render_forward: bad handle or options");
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_forward: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
+                opts->struct_size, sizeof(mnf_train_opts));
+    MNF_REQUIRE(!opts->presampled, "train_render_forward: opts->presampled must be NULL (a presampled march is adopted by mnf_train_step only)");
+    MNF_REQUIRE(binaries && occs && rays_o && rays_d && rgb && acc && depth && workspace, "train_render_forward: null pointer");
+    MNF_REQUIRE(sem || f->cfg.num_semantic_classes == 0, "train_render_forward: null pointer (sem may be NULL only for a field without semantic classes)");
+    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->render_step_size > 0.f, "train_render_forward: bad sizes");
+    MNF_REQUIRE(opts->n_levels <= 4, "train_render_forward: at most 4 occupancy levels");
+    StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
+    if (workspace_bytes < w.bytes) { set_error("train_render_forward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    const StepFills fills = {nullptr, nullptr, nullptr, w.sigma, 0, 0, 0, max_marched, nullptr, nullptr};      // (no gradient vector is touched here)
+    int64_t *eff = nullptr;
+    const float *bk = nullptr;
+    int rc = step_forward(f, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, fills, render_losses(w), counts_dev, skip_dev, max_marched,
+                          max_kept, w, eff, bk, stream);
+    if (rc) return rc;
+    // (a guard that fired has cleared every per-ray count: the compositing then wrote the background colour and zeros, never what the workspace held before)
+    const int C = f->cfg.num_semantic_classes;
+    const int64_t widest = (int64_t)n_rays * (C > 3 ? C : 3);
+    hipLaunchKernelGGL(outputs_kernel, dim3((unsigned)((widest + 255) / 256)), dim3(256), 0, as_stream(stream), (int64_t)n_rays, C, w.o_rgb, w.o_acc, w.o_dep, w.o_sem,
+                       rgb, acc, depth, sem, skip_dev, render_ticket(w));
+    return launch_status("outputs_kernel");
+}
+
+extern "C" int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *g_rgb, int64_t g_rgb_row_stride,
+                                         int64_t g_rgb_col_stride, const float *g_acc, int64_t g_acc_row_stride, const float *g_depth, int64_t g_depth_row_stride,
+                                         const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base, float *g_head, float *g_sem_params,
+                                         int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes,
+                                         mnf_stream_t stream) {
+    MNF_REQUIRE(f && f->params_loaded && opts && counts_dev && skip_dev, "train_render_backward: bad handle or options");
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_backward: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
+                opts->struct_size, sizeof(mnf_train_opts));
+    MNF_REQUIRE(!opts->presampled, "train_render_backward: opts->presampled must be NULL");
+    MNF_REQUIRE(g_base && g_head && g_sem_params && workspace, "train_render_backward: null pointer");
+    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0, "train_render_backward: bad sizes");
+    const StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
+    if (workspace_bytes < w.bytes) { set_error("train_render_backward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    int64_t *eff = w.totals + 4;
+    const float *bk = opts->render_bkgd_dev;      // as the forward chose it: the caller's device colour, or the by-value one the forward left in the workspace
+    if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) bk = w.alpha_thre + 8;
+    const GradFills z = {g_base, g_head, g_sem_params, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem};
+    hipLaunchKernelGGL(gradients_in_kernel, dim3(fill_blocks((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), n_rays, f->cfg.num_semantic_classes,
+                       GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
+                       GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, w.g_rgb, w.g_acc, w.g_dep, w.g_sem, z, counts_dev, skip_dev, eff, render_ticket(w));
+    int rc = launch_status("gradients_in_kernel");
+    if (rc) return rc;
+    return step_backward(f, w, n_rays, opts, bk, w.g_acc, eff, max_kept, g_base, g_head, g_sem_params, stream);
 }
 
 // view groups per member of a scoring call.  FOUR render jobs in flight (the caller's stream + the three shared side streams) is the measured optimum for

@@ -6,6 +6,7 @@ running on libmi355nerf.so.
   render_image_with_occgrid_test                  utils.py:555-779
   render_probablistic_image_with_occgrid_test     utils.py:782-1032
   render_image_with_occgrid_with_depth_guide      utils.py:63-219   (forward; see DESIGN.md §Scope for backward)
+  fused_train_render                              utils.py:63-219 on the one-call step's kernels, differentiable (any torch loss behind it)
   sem_rendering                                   utils.py:362-461
   generate_image_rays / render_*_from_pose        habitat_to_data.py:274-549
   probablistic_uncertainty -> score_views         pipeline.py:666-798
@@ -309,6 +310,7 @@ def allreduce_gradients(parameters, group=None, skip=None):
 
 # status bits of mnf_train_step's counts_dev[3] (include/mi355nerf.h)
 _ST_MARCHED, _ST_ROW, _ST_KEPT, _ST_LABEL, _ST_EMPTY = 1, 2, 4, 8, 16
+_ST_GRAD = 32      # mnf_train_render_backward: a non-finite incoming gradient
 _STEP_OK, _STEP_ROW, _STEP_GROW = "ok", "row overflow", "bounds overflow; grow"      # what `_step_verdict` says
 
 
@@ -677,11 +679,147 @@ def fused_forward_backward(radiance_field, estimator, rays: Rays, pixels, dep, s
     return out
 
 
+# ------------------------------------------------------------------ the fused step cut at its loss (mnf_train_render_forward / _backward)
+_LAST_RENDER = weakref.WeakKeyDictionary()      # field -> the device counters and skip flag of its latest `fused_train_render` (`latest_train_render`)
+
+
+def latest_train_render(radiance_field):
+    """dict(counts [device int64: marched, kept, longest ray, status], skip [device int32 scalar]) of the field's most recent `fused_train_render`, or None if that
+    call handed over to `render_image_with_occgrid_with_depth_guide` (or none was made).  The backward of that render adds to them: status bit 32 and a raised
+    flag for a non-finite incoming gradient.  `skip` is what a guarded optimizer step takes (`optim.FusedAdam.step(skip=...)`)."""
+    return _LAST_RENDER.get(radiance_field)
+
+
+def _param_versions(radiance_field):
+    ps = (radiance_field.mlp_base.params, radiance_field.mlp_head.params, radiance_field.mlp_sem.params)
+    return tuple(p._version for p in ps) + (ps[0].data_ptr(),)
+
+
+@torch.no_grad()
+def _launch_train_render(st, radiance_field, estimator, rays, render_bkgd, seed, own_workspace, **opts_kw):
+    """Exactly one `mnf_train_render_forward` launch with the field's current sample bounds.  `own_workspace`: the call's scratch is a tensor of its own (a
+    differentiable call: its backward reads it, whatever runs in between) instead of the cached slot the next call overwrites.  Returns the four planes, the
+    device counters and skip flag, and what the backward needs."""
+    lib = L.load_library()
+    o, d = L.contig(rays.origins.reshape(-1, 3), torch.float32), L.contig(rays.viewdirs.reshape(-1, 3), torch.float32)
+    L.require_gpu(o, d)
+    R, dev, C = o.shape[0], o.device, radiance_field.num_semantic_classes
+    handle, grid = radiance_field._ensure_handle(), _grid_args(estimator)
+    if own_workspace and render_bkgd is not None and render_bkgd.is_cuda:
+        render_bkgd = render_bkgd.detach().clone()      # the backward reads the colour again: the forward's three floats, whatever the caller draws into its tensor meanwhile
+    opts, _, bk_dev = _train_opts(radiance_field, grid, dev, seed=seed, loss_scale=float(radiance_field.loss_scale), render_bkgd=render_bkgd, **opts_kw)
+    counts, skip = torch.empty(4, dtype=torch.int64, device=dev), torch.empty((), dtype=torch.int32, device=dev)
+    rgb, acc, depth, sem = torch.empty(R, 3, device=dev), torch.empty(R, 1, device=dev), torch.empty(R, 1, device=dev), torch.empty(R, C, device=dev)
+    cap_m, cap_k = st.caps(R)
+    nbytes = int(lib.mnf_train_step_workspace_bytes(handle, R, cap_m, cap_k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if own_workspace else _workspace(dev, nbytes)
+    L.launch(lib.mnf_train_render_forward, handle, L.ptr(grid.binaries), L.ptr(grid.bits), L.ptr(grid.occs), *grid.res, grid.aabb, L.ptr(o), L.ptr(d), R,
+             ctypes.byref(opts), L.ptr(rgb), L.ptr(acc), L.ptr(depth), L.ptr(sem), L.ptr(counts), L.ptr(skip), cap_m, cap_k, L.ptr(ws), nbytes)
+    return dict(rgb=rgb, acc=acc, depth=depth, sem=sem, counts=counts, skip=skip, _rays=R, _field=radiance_field, _handle=handle, _opts=opts, _keep=bk_dev,
+                _caps=(cap_m, cap_k), _ws=ws if own_workspace else None, _nbytes=nbytes, _versions=radiance_field._loaded_versions)
+
+
+class _TrainRender(torch.autograd.Function):
+    """The autograd node of `fused_train_render`: inputs the three flat parameter vectors, outputs the four rendered planes of a launched
+    `mnf_train_render_forward` (`call`), backward `mnf_train_render_backward` with whatever gradients autograd delivers — None as NULL, strides passed
+    through, no `.contiguous()`."""
+
+    @staticmethod
+    def forward(ctx, call, p_base, p_head, p_sem):
+        planes = tuple(call.pop(k) for k in ("rgb", "acc", "depth", "sem"))      # (not kept: the planes own this node, the node must not own the planes)
+        ctx.call = call
+        ctx.set_materialize_grads(False)      # a plane the loss does not use arrives as None (-> NULL), not as a zero tensor
+        return planes
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb, g_acc, g_depth, g_sem):
+        call = ctx.call
+        field = call["_field"]
+        if call["_ws"] is None:
+            raise L.MnfError("fused_train_render: a second backward through the same render (its backward overwrites the workspace the first one read); "
+                             "render again")
+        if field._loaded_versions != call["_versions"] or _param_versions(field) != call["_versions"]:
+            raise L.MnfError("fused_train_render: the field's parameters changed between the render and its backward (an optimizer step, a load): the 16-bit "
+                             "weights in the handle are no longer the forward's")
+        params = (field.mlp_base.params, field.mlp_head.params, field.mlp_sem.params)
+        grads = [torch.empty_like(p_, memory_format=torch.contiguous_format) for p_ in params]
+        dev, R = call["counts"].device, call["_rays"]
+        gs = [None if g is None else g.to(device=dev, dtype=torch.float32) for g in (g_rgb, g_acc, g_depth, g_sem)]      # (no-ops: autograd delivers fp32 on the device)
+        st0 = lambda g: 0 if g is None else g.stride(0)
+        st1 = lambda g: 0 if g is None else g.stride(1)
+        ws, call["_ws"] = call["_ws"], None
+        L.launch(L.load_library().mnf_train_render_backward, call["_handle"], R, ctypes.byref(call["_opts"]), L.ptr(gs[0]), st0(gs[0]), st1(gs[0]),
+                 L.ptr(gs[1]), st0(gs[1]), L.ptr(gs[2]), st0(gs[2]), L.ptr(gs[3]), st0(gs[3]), st1(gs[3]), L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]),
+                 L.ptr(call["counts"]), L.ptr(call["skip"]), *call["_caps"], L.ptr(ws), call["_nbytes"])
+        return None, grads[0], grads[1], grads[2]
+
+
+def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float = 0.0, far_plane: float = 1e10, render_step_size: float = 1e-3,
+                       render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0, alpha_thre: float = 0.0, early_stop_eps: float = 1e-4,
+                       depth: Optional[torch.Tensor] = None, stratified=None, seed: "int | None" = None, deterministic: bool = False):
+    """`render_image_with_occgrid_with_depth_guide` (utils.py:63-219) on the kernels of the one-call train step, differentiable with respect to the field's
+    parameters: any torch loss on the returned planes, then `loss.backward()`, runs the step's own forward and backward (`mnf_train_render_forward` /
+    `mnf_train_render_backward`) around it.  Switching over is the import line
+
+        from apnrf_amd.render import fused_train_render as render_image_with_occgrid_with_depth_guide
+
+    Returns (rgb [..,3], acc [..,1], depth [..,1], sem [..,C], n_rendering_samples: int) as the drop-in does.  `depth` is accepted and ignored, as in the
+    reference; `stratified=None` follows `radiance_field.training`; `seed`: the Philox key of the near-plane jitter (None: torch's CPU generator's next draw);
+    `deterministic=True`: bitwise reproducible gradient accumulation.  One host round trip (the four counters: the `int` the reference returns demands it); a
+    render beyond its sample bounds is repeated with larger ones (it is pure).  More than four occupancy levels, or a ray past the sampler's scratch row, hand
+    over to `render_image_with_occgrid_with_depth_guide`; the hand-over follows `radiance_field.training` as the drop-in does: `stratified=False` is honoured
+    (the field is put into eval mode for the call), `stratified=True` on a field in eval mode is not, and the drop-in has no `early_stop_eps`, `seed` or
+    `deterministic` to pass on.
+    One backward per render, and the parameters must not change between the two (both raise `MnfError`).  Under `torch.no_grad()`, or with no parameter
+    requiring a gradient, nothing is kept for a backward.  `latest_train_render(radiance_field)` has the device counters and the skip flag."""
+    _LAST_RENDER.pop(radiance_field, None)
+
+    def hand_over():
+        no_jitter = stratified is False and radiance_field.training      # (the drop-in's jitter follows radiance_field.training: `_train_autograd`)
+        if no_jitter:
+            radiance_field.eval()
+        try:
+            return render_image_with_occgrid_with_depth_guide(radiance_field, estimator, rays, near_plane=near_plane, far_plane=far_plane,
+                                                              render_step_size=render_step_size, render_bkgd=render_bkgd, cone_angle=cone_angle,
+                                                              alpha_thre=alpha_thre, depth=depth)
+        finally:
+            if no_jitter:
+                radiance_field.train()
+
+    if estimator.levels > 4 or rays.origins.numel() == 0:
+        return hand_over()
+    st, seed = _train_state(radiance_field), _step_seed(None, seed)      # one draw per render, whatever the number of attempts
+    differentiable = torch.is_grad_enabled() and any(p_.requires_grad for p_ in radiance_field.parameters())
+    opts_kw = dict(near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,
+                   early_stop_eps=early_stop_eps, stratified=stratified, deterministic=deterministic)
+    for attempt in range(4):
+        out = _launch_train_render(st, radiance_field, estimator, rays, render_bkgd, seed, differentiable, **opts_kw)
+        c = out["counts"].tolist()                                        # the render's one host round trip
+        verdict = _step_verdict(*c, 0)
+        if verdict == _STEP_ROW:
+            return hand_over()
+        if verdict == _STEP_OK:
+            break
+        st.grow(c[0], c[1], out["_rays"], carry=False)
+    else:
+        raise L.MnfError("fused_train_render: sample bounds kept growing")
+    estimator.last_sampling = {"n_marched": int(c[0])}
+    _LAST_RENDER[radiance_field] = dict(counts=out["counts"], skip=out["skip"])
+    if differentiable:
+        planes = _TrainRender.apply(out, radiance_field.mlp_base.params, radiance_field.mlp_head.params, radiance_field.mlp_sem.params)
+    else:
+        planes = (out["rgb"], out["acc"], out["depth"], out["sem"])
+    shp = tuple(rays.origins.shape[:-1])
+    return tuple(x.view(*shp, -1) for x in planes) + (int(c[1]),)
+
+
 def _step_result(fwd, skipped, sync):
     """`train_step`'s result.  A synchronous step without a surviving sample is the reference's `continue` (pipeline.py:491): no loss."""
     if sync and fwd["n_rendering_samples"] == 0:
         return dict(loss=None, n_rendering_samples=0, skipped=True)
-    return dict(loss=fwd["loss"].detach(), loss_rgb=fwd["loss_rgb"].detach(), loss_dep=fwd["loss_dep"].detach(), loss_sem=fwd["loss_sem"].detach(),
+    det = lambda x: None if x is None else x.detach()      # (a caller's `loss_fn` has no terms to report)
+    return dict(loss=det(fwd["loss"]), loss_rgb=det(fwd["loss_rgb"]), loss_dep=det(fwd["loss_dep"]), loss_sem=det(fwd["loss_sem"]),
                 n_rendering_samples=fwd["n_rendering_samples"], skipped=skipped)
 
 
@@ -781,9 +919,34 @@ def _train_autograd(batch, optimizer, scheduler, sync, data_parallel, data_paral
     return _apply_update(radiance_field, optimizer, scheduler, fwd, sync, data_parallel, data_parallel_group)
 
 
+def _train_loss_fn(batch, optimizer, scheduler, loss_fn, data_parallel, data_parallel_group, stratified, seed, deterministic, **render_kw):
+    """`train_step(loss_fn=...)`: `fused_train_render` -> the caller's loss -> `backward()` -> `_apply_update`.  The render's device skip flag (no surviving sample;
+    after the backward also a non-finite incoming gradient) is the one the guarded optimizer call reads."""
+    radiance_field, estimator, rays, pixels, dep, sem, render_bkgd = batch
+    rgb, acc, depth, semantic, n_rendering_samples = fused_train_render(radiance_field, estimator, rays, render_bkgd=render_bkgd, depth=dep, stratified=stratified,
+                                                                        seed=seed, deterministic=deterministic, **render_kw)
+    dev = rays.origins.device
+    last = latest_train_render(radiance_field)      # (None: the render was handed over to the call-by-call surface)
+    skip = last["skip"] if last is not None else torch.zeros((), dtype=torch.int32, device=dev)
+    optimizer.zero_grad()
+    if n_rendering_samples == 0:                    # pipeline.py:491: `continue`; a data-parallel rank still reaches the collective, with zero gradients
+        if last is None:
+            skip += 1
+        for p_ in radiance_field.parameters():
+            if p_.numel():
+                p_.grad = torch.zeros_like(p_)
+        loss = torch.zeros((), device=dev)
+    else:
+        loss = loss_fn(rgb, acc, depth, semantic, pixels, dep, sem)
+        loss.backward()
+    fwd = dict(loss=loss, loss_rgb=None, loss_dep=None, loss_sem=None, skip=skip, n_rendering_samples=n_rendering_samples)
+    return _apply_update(radiance_field, optimizer, scheduler, fwd, True, data_parallel, data_parallel_group)
+
+
 def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, sem, render_bkgd, step: int,
                near_plane=0.1, render_step_size=1e-3, cone_angle=0.004, alpha_thre=0.01, occ_thre=1e-3, scheduler=None,
-               data_parallel_group=None, data_parallel=False, fused=True, sync=True, stratified=None, deterministic=False, presampled=None, seed=None):
+               data_parallel_group=None, data_parallel=False, fused=True, sync=True, stratified=None, deterministic=False, presampled=None, seed=None,
+               loss_fn=None):
     """One model's training iteration exactly as scripts/pipeline.py:447-532 sequences it: occupancy refresh every 16th
     step (:447-470), train render (:472-489), loss 10*smoothL1(rgb) + smoothL1(depth)/5 + CE(sem)/2 (:506-511),
     backward (:518), NaN-gradient guard (:520-529), optimizer and scheduler step (:531-532).  `data_parallel=True`
@@ -807,8 +970,12 @@ def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, se
     `seed` (fused path): the Philox key of the near-plane jitter (None: torch's CPU generator's next draw).
     `presampled` (fused path): the `presample()` token of THIS batch — its march ran beside the previous iteration; ignored (the step marches itself,
     with the token's jitter seed) if the occupancy refresh below or other options made it stale.
+    `loss_fn` (sync=True only): a callable `loss_fn(rgb, acc, depth, sem, pixels, dep, sem_gt) -> scalar` replaces the three-term loss; the iteration then runs
+    `fused_train_render` -> `loss_fn` -> `backward()` on the same kernels (the result's loss_rgb / loss_dep / loss_sem are None).  None: nothing changes.
     Returns dict(loss, loss_rgb, loss_dep, loss_sem as device tensors, n_rendering_samples, skipped)."""
     from .optim import FusedAdam
+    if loss_fn is not None and not sync:
+        raise ValueError("train_step(loss_fn=...) is synchronous: the render returns n_rendering_samples as an int (sync=False is the built-in loss's)")
     radiance_field.train()
     estimator.train()
     if presampled is not None and presampled.keep is not None and step % REFRESH_EVERY == 0:
@@ -825,6 +992,10 @@ def train_step(radiance_field, estimator, optimizer, rays: Rays, pixels, dep, se
     batch = (radiance_field, estimator, rays, pixels, dep, sem, render_bkgd)
     render_kw = dict(near_plane=near_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre)
     opts_kw = dict(render_kw, far_plane=1e10, early_stop_eps=1e-4, stratified=stratified, deterministic=deterministic)
+    if loss_fn is not None:
+        if presampled is not None:
+            presampled.wait(rays.origins.device)      # (presample adoption is the one-call step's: the token is left unused, its buffers behind its march)
+        return _train_loss_fn(batch, optimizer, scheduler, loss_fn, data_parallel, data_parallel_group, stratified, seed, deterministic, **render_kw)
     if fused and sync and device_guard and not data_parallel:
         res = _train_fused_one_trip(batch, optimizer, scheduler, presampled, seed, opts_kw)
     else:

@@ -399,7 +399,7 @@ int mnf_field_forward_train_samples(mnf_field_t f, const float *rays_o, const fl
  * NO stream synchronisation: the sample counts stay on the device.  counts_dev (DEVICE, 4 x int64): [0] marched samples, [1] surviving
  * samples (= the reference's n_rendering_samples), [2] samples of the longest ray, [3] status bits: 1 marched > max_marched, 2 a ray
  * longer than a scratch row (use the two-pass sampler), 4 surviving > max_kept, 8 a class id outside [0, C) (F.cross_entropy's device
- * assert), 16 no sample survived (the reference `continue`s, pipeline.py:491).  skip_dev (DEVICE int32): set to 0, then raised for
+ * assert), 16 no sample survived (the reference `continue`s, pipeline.py:491), 32 (mnf_train_render_backward only) a non-finite incoming gradient.  skip_dev (DEVICE int32): set to 0, then raised for
  * every status bit: with it non-zero the gradients are zero / must not be applied (mnf_adam_step_guarded reads it).  The caller
  * bounds the sample counts (max_marched, max_kept), provides mnf_train_step_workspace_bytes(), reads counts_dev when it wants
  * to and retries with larger bounds after bits 1 / 4.
@@ -447,6 +447,37 @@ int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgr
                    const float *target_rgb, const float *target_depth, const int64_t *target_sem, const mnf_train_opts *opts,
                    float *g_base, float *g_head, float *g_sem, float *losses, int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched,
                    int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
+/* The same iteration cut at its loss, for a caller whose loss is not the one mnf_train_step computes (the reference's own loss lines kept in torch, masked
+ * depth, other weights, a term on the opacity, label smoothing): mnf_train_render_forward is pipeline.py:472-489 — the train render
+ * `render_image_with_occgrid_with_depth_guide`, utils.py:63-219 — and mnf_train_render_backward is what `loss.backward()` (pipeline.py:518) does below the
+ * four rendered planes.  Both launch exactly the kernels mnf_train_step launches on its side of the loss, in the same order, so rendered values, sample
+ * counts and gradients are the step's.  Arguments as mnf_train_step's; opts->presampled must be NULL (MNF_ERR_INVALID otherwise).
+ *
+ * mnf_train_render_forward writes rgb [n_rays,3], acc [n_rays], depth [n_rays], sem [n_rays,C] (ray-major, dense) and fills counts_dev / skip_dev as the step
+ * does (status bits 1, 2, 4, 16).  It touches no gradient vector.  When a guard fires or no sample survives the outputs are still defined: the background
+ * colour, acc 0, depth 0, sem 0.  `sem` may be NULL for a field without semantic classes (C == 0), and only then.
+ *
+ * mnf_train_render_backward takes dL/d(rgb, acc, depth, sem) as the caller's autograd delivers them: each pointer may be NULL (= zero) and comes with its
+ * row stride (and, for rgb / sem, column stride) in ELEMENTS — element (r, c) is read at g[r * row_stride + c * col_stride]; stride 0 (an expanded scalar)
+ * and transposed views are fine, no dense copy is needed.  g_base / g_head / g_sem_params are OVERWRITTEN, not accumulated.  counts_dev / skip_dev are the
+ * forward's: with the skip flag already raised the gradients come out zero; a non-finite incoming value raises status bit 32 and the skip flag and the
+ * gradients come out zero as well (pipeline.py:520-529 decided on the device: mnf_adam_step_guarded then leaves the parameters alone).
+ *
+ * Contract: every bit of per-call state lives in `workspace` (mnf_train_step_workspace_bytes(f, n_rays, max_marched, max_kept) bytes, the same n_rays and
+ * bounds in both calls).  Between a forward and its backward the workspace, the field's loaded weights (no mnf_field_set_params / optimizer step on `f`), the
+ * options and — if used — the three floats behind opts->render_bkgd_dev must stay unchanged; the rays and the occupancy grid are not read again.  Other
+ * forwards and backwards of the same field with OTHER workspaces may run in between (the deterministic mode's scratch on the field handle is only touched
+ * inside a backward).  One backward per forward: the backward overwrites workspace state. */
+int mnf_train_render_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
+                             int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
+                             const mnf_train_opts *opts, float *rgb, float *acc, float *depth, float *sem, int64_t *counts_dev, int32_t *skip_dev,
+                             int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *g_rgb, int64_t g_rgb_row_stride,
+                              int64_t g_rgb_col_stride, const float *g_acc, int64_t g_acc_row_stride, const float *g_depth, int64_t g_depth_row_stride,
+                              const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base, float *g_head, float *g_sem_params,
+                              int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes,
+                              mnf_stream_t stream);
 
 /* ---------------------------------------------------------------- fused test-mode renderers */
 

@@ -34,6 +34,7 @@ SOURCES = {
     "vanilla.hip": [],
     "trainstep.hip": ["-ffp-contract=off"],
     "eval.hip": [],
+    "ensemble.hip": [],
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
 }

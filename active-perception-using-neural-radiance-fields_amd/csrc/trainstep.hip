@@ -764,35 +764,44 @@ extern "C" int64_t mnf_score_poses_workspace_bytes(int32_t n_members, int32_t n_
     return R * 24 + 512 + n_members * (per_member + render + 64 * G + 256) + 4096;
 }
 
-extern "C" int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
-                               int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
-                               int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
-                               const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MNF_REQUIRE(fields_host && binaries_host && aabb_host && c2w && opts && terms && workspace && pix_idx, "score_poses: null pointer");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_render_opts), "score_poses: opts->struct_size is %u, this library's mnf_render_opts has %zu bytes (MNF_INIT)",
+// What mnf_score_poses and mnf_score_trajectory share: c2w -> the sub-sampled rays of every view -> every member's render as jobs of ONE mnf_render_jobs call,
+// the outputs the scorer reads laid out member-major in the workspace.  probabilistic: rgb_var / depth_var / acc / sem are member-major and the plain rgb / depth
+// go to per-member scratch; otherwise rgb / depth / acc / sem are member-major and no variance is rendered.
+struct MemberStacks { float *rgb_var, *depth_var, *rgb, *depth, *acc, *sem; int C; char *tail; int64_t tail_bytes; };      // tail: the workspace past every job's
+
+static int render_members(const char *what, const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
+                          int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w, int32_t n_views,
+                          int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix, const mnf_render_opts *opts, bool probabilistic,
+                          const void *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream, MemberStacks *st) {
+    MNF_REQUIRE(fields_host && binaries_host && aabb_host && c2w && opts && terms && workspace && pix_idx, "%s: null pointer", what);
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_render_opts), "%s: opts->struct_size is %u, this library's mnf_render_opts has %zu bytes (MNF_INIT)", what,
                 opts->struct_size, sizeof(mnf_render_opts));
-    MNF_REQUIRE(n_members >= 1 && n_members <= 16 && n_views >= 1 && n_pix >= 1, "score_poses: bad sizes");
+    MNF_REQUIRE(n_members >= 1 && n_members <= 16 && n_views >= 1 && n_pix >= 1, "%s: bad sizes", what);
     const int C = fields_host[0]->cfg.num_semantic_classes;
-    for (int m = 1; m < n_members; ++m) MNF_REQUIRE(fields_host[m]->cfg.num_semantic_classes == C, "score_poses: members disagree on the class count");
-    const int64_t need = mnf_score_poses_workspace_bytes(n_members, n_views, (int32_t)n_pix, C);
-    if (workspace_bytes < need) { set_error("score_poses: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need); return MNF_ERR_WORKSPACE; }
+    for (int m = 1; m < n_members; ++m) MNF_REQUIRE(fields_host[m]->cfg.num_semantic_classes == C, "%s: members disagree on the class count", what);
+    const int64_t need = probabilistic ? mnf_score_poses_workspace_bytes(n_members, n_views, (int32_t)n_pix, C)
+                                       : mnf_score_trajectory_workspace_bytes(n_members, n_views, (int32_t)n_pix, C);
+    if (workspace_bytes < need) { set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)need); return MNF_ERR_WORKSPACE; }
     const int64_t R = (int64_t)n_views * n_pix;
     char *base = (char *)workspace;
     size_t off = 0;
     auto take = [&](size_t b) { char *p = base + off; off += (b + 255) & ~(size_t)255; return p; };
     float *o = (float *)take(R * 12), *d = (float *)take(R * 12);
-    // member-major stacks, exactly what mnf_score_views reads
-    float *rgb_var = (float *)take((size_t)n_members * R * 12), *depth_var = (float *)take((size_t)n_members * R * 4);
+    // member-major stacks, exactly what mnf_score_views / mnf_score_ensemble_views read
+    float *wide = (float *)take((size_t)n_members * R * 12), *narrow = (float *)take((size_t)n_members * R * 4);
     float *acc = (float *)take((size_t)n_members * R * 4), *sem = (float *)take((size_t)n_members * R * C * 4);
     int rc = mnf_generate_rays(c2w, n_views, width, height, focal, pix_idx, n_pix, o, d, stream);
     if (rc) return rc;
     mnf_render_opts ro = *opts;
-    ro.probabilistic = 1; ro.rays_per_view = (int32_t)n_pix; ro.bitgrid = nullptr;      // (the caller's view_order, if any, applies to every view)
+    ro.probabilistic = probabilistic ? 1 : 0; ro.rays_per_view = (int32_t)n_pix; ro.bitgrid = nullptr;      // (the caller's view_order, if any, applies to every view)
+    if (!probabilistic) ro.render_bkgd[0] = ro.render_bkgd[1] = ro.render_bkgd[2] = 0.f;
     // every (member, half of the pose list) is a render job of its own: they advance side by side (mnf_render_jobs)
     const int G = score_groups(n_views, n_members);
     std::vector<mnf_render_job> jobs;
     for (int m = 0; m < n_members; ++m) {
-        float *rgb = (float *)take(R * 12), *depth = (float *)take(R * 4);          // outputs the scorer does not read
+        float *rgb = nullptr, *depth = nullptr;
+        if (probabilistic) { rgb = (float *)take(R * 12); depth = (float *)take(R * 4); }          // outputs the scorer does not read
+        else { rgb = wide + (size_t)m * R * 3; depth = narrow + (size_t)m * R; }
         for (int g = 0; g < G; ++g) {
             const int64_t r0 = (int64_t)group_lo(n_views, g, G) * n_pix, r1 = (int64_t)group_lo(n_views, g + 1, G) * n_pix;
             mnf_render_job j = {};
@@ -801,15 +810,47 @@ extern "C" int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *co
             j.rays_o = o + 3 * r0; j.rays_d = d + 3 * r0; j.n_rays = r1 - r0;
             j.rgb = rgb + 3 * r0; j.depth = depth + r0;
             j.acc = acc + (size_t)m * R + r0; j.sem = sem + ((size_t)m * R + r0) * C;
-            j.rgb_var = rgb_var + ((size_t)m * R + r0) * 3; j.depth_var = depth_var + (size_t)m * R + r0;
+            if (probabilistic) { j.rgb_var = wide + ((size_t)m * R + r0) * 3; j.depth_var = narrow + (size_t)m * R + r0; }
             j.total_samples = (int64_t *)take(64);
             j.workspace_bytes = mnf_render_workspace_bytes(r1 - r0, (int32_t)n_pix);
             j.workspace = take((size_t)j.workspace_bytes);
             jobs.push_back(j);
         }
     }
-    MNF_REQUIRE((int64_t)off <= workspace_bytes, "score_poses: internal workspace accounting error");
-    rc = mnf_render_jobs(jobs.data(), (int32_t)jobs.size(), res_x, res_y, res_z, aabb_host, &ro, stream);
+    MNF_REQUIRE((int64_t)off <= workspace_bytes, "%s: internal workspace accounting error", what);
+    *st = MemberStacks{probabilistic ? wide : nullptr, probabilistic ? narrow : nullptr, probabilistic ? nullptr : wide, probabilistic ? nullptr : narrow, acc, sem, C,
+                       base + off, workspace_bytes - (int64_t)off};
+    return mnf_render_jobs(jobs.data(), (int32_t)jobs.size(), res_x, res_y, res_z, aabb_host, &ro, stream);
+}
+
+extern "C" int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
+                               int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
+                               int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
+                               const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MemberStacks st;
+    int rc = render_members("score_poses", fields_host, binaries_host, bitgrids_host, n_members, res_x, res_y, res_z, aabb_host, c2w, n_views, width, height, focal,
+                            pix_idx, n_pix, opts, true, terms, workspace, workspace_bytes, stream, &st);
     if (rc) return rc;
-    return mnf_score_views(rgb_var, depth_var, acc, sem, n_members, n_views, (int32_t)n_pix, C, terms, stream);
+    return mnf_score_views(st.rgb_var, st.depth_var, st.acc, st.sem, n_members, n_views, (int32_t)n_pix, st.C, terms, stream);
+}
+
+extern "C" int64_t mnf_score_trajectory_workspace_bytes(int32_t n_members, int32_t n_views, int32_t n_pix, int32_t n_classes) {
+    if (n_members <= 0 || n_views <= 0 || n_pix <= 0 || n_classes <= 0) return -1;
+    const int64_t R = (int64_t)n_views * n_pix;
+    const int64_t per_member = R * (3 + 1 + 1 + n_classes) * 4 + 4 * 256;
+    const int G = score_groups(n_views, n_members);
+    int64_t render = 0;
+    for (int g = 0; g < G; ++g) render += mnf_render_workspace_bytes((int64_t)(group_lo(n_views, g + 1, G) - group_lo(n_views, g, G)) * n_pix, n_pix) + 256;
+    return R * 24 + 512 + n_members * (per_member + render + 64 * G + 256) + 4096 + mnf_score_ensemble_views_workspace_bytes(n_views, n_pix, n_classes) + 256;
+}
+
+extern "C" int mnf_score_trajectory(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
+                                    int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
+                                    int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
+                                    const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MemberStacks st;
+    int rc = render_members("score_trajectory", fields_host, binaries_host, bitgrids_host, n_members, res_x, res_y, res_z, aabb_host, c2w, n_views, width, height,
+                            focal, pix_idx, n_pix, opts, false, terms, workspace, workspace_bytes, stream, &st);
+    if (rc) return rc;
+    return mnf_score_ensemble_views(st.rgb, st.depth, st.acc, st.sem, n_members, 1, n_views, n_pix, st.C, terms, st.tail, st.tail_bytes, stream);
 }

@@ -1263,6 +1263,105 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
     return terms, trajectory_score(terms)
 
 
+# ------------------------------------------------------------------ ensemble-disagreement scorer (pipeline.py:800-916)
+ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_CLASSES = 64, 1024      # MNF_SCORE_ENSEMBLE_MAX_MEMBERS / _CLASSES (include/mi355nerf.h)
+
+
+@torch.no_grad()
+def ensemble_view_terms(rgb, depth, acc, sem):
+    """The four clipped per-view rows of `trajector_uncertainty` (pipeline.py:861-882) on the device (`mnf_score_ensemble_views`,
+    csrc/ensemble.hip).  Inputs are member-major stacks of the plain renders of M ensemble members for the same V views of P pixels:
+    rgb [M,V,P,3], depth [M,V,P], acc [M,V,P] (member 0 is read), sem [V,P,C] (member 0's logits, as the reference keeps them) or
+    [S,V,P,C] with 1 <= S <= M (the entropy is averaged over those members); fp32, GPU.  Returns [V,4] float64: 4000 x the
+    across-member rgb variance and 50 x the depth variance, clipped to [0, 100]; mean clip(1 / (acc + 1e-4) - 1, 0, 10000); 50 x the
+    softmax entropy, clipped to [0, 100]."""
+    L.require_gpu(rgb, depth, acc, sem)
+    if sem.dim() == 3:
+        sem = sem[None]
+    if sem.dim() != 4 or rgb.dim() != 4 or rgb.shape[-1] != 3:
+        raise ValueError(f"ensemble_view_terms takes rgb [M,V,P,3] and sem [S,V,P,C] or [V,P,C] (got {tuple(rgb.shape)}, {tuple(sem.shape)})")
+    S, V, P, C = (int(x) for x in sem.shape)
+    M = int(rgb.shape[0])
+    if tuple(rgb.shape) != (M, V, P, 3) or depth.numel() != M * V * P or acc.numel() != M * V * P:
+        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} / acc {tuple(acc.shape)} do not match {M} members of {V} views of {P} pixels")
+    lib = L.load_library()
+    r, d, a, s = (L.contig(t, torch.float32) for t in (rgb, depth, acc, sem))
+    terms = torch.empty(V, 4, dtype=torch.float64, device=sem.device)
+    with torch.cuda.device(sem.device):
+        nbytes = max(int(lib.mnf_score_ensemble_views_workspace_bytes(V, P, C)), 8)
+        ws = _workspace((sem.device, "ensemble"), nbytes)
+        L.launch(lib.mnf_score_ensemble_views, L.ptr(r), L.ptr(d), L.ptr(a), L.ptr(s), M, S, V, P, C, L.ptr(terms), L.ptr(ws), nbytes)
+    return terms
+
+
+def trajectory_view_indices(n_poses: int) -> np.ndarray:
+    """The 40 poses of a trajectory that the scorers render (pipeline.py:687-689, :819-821): 20 evenly spread over all but the last
+    20 poses, 20 over the last 20, truncated to integers."""
+    a = np.linspace(0, n_poses - 20, 20)
+    b = np.linspace(n_poses - 20, n_poses - 1, 20)
+    return np.hstack((a, b)).astype(int)
+
+
+def trajectory_uncertainty_from_terms(terms, step):
+    """pipeline.py:883-896: per-view uncertainty = the sum of the four columns of `terms` [V,4]; `step == -1` averages the last 11
+    views, any other step all of them.  Returns (uncertainty, max_idx); `max_idx` is `np.arange(V)` (the reference sorts its argsort)."""
+    t = terms.detach().cpu().numpy() if isinstance(terms, torch.Tensor) else np.asarray(terms)
+    per_view = t[:, 0] + t[:, 1] + t[:, 2] + t[:, 3]
+    max_idx = np.sort(np.argsort(per_view))
+    return (np.mean(per_view[-11:]) if step == -1 else np.mean(per_view[max_idx])), max_idx
+
+
+@torch.no_grad()
+def trajectory_uncertainty(radiance_fields, estimators, trajectory, step, width, height, focal, near_plane, render_step_size, cone_angle,
+                           alpha_thre, scale=0.1, device="cuda:0", group=None, one_call=True):
+    """`ActiveNeRFMapper.trajector_uncertainty` (pipeline.py:800-916): the 40 `trajectory_view_indices` poses of `trajectory` rendered by
+    every ensemble member (plain render, black background, 1024 samples per round: `render_image_from_pose`), reduced to the four clipped
+    rows on the device, ONE host copy of [V,4] doubles at the end.  `one_call=True` and no sharding: one C call (`mnf_score_trajectory`,
+    csrc/trainstep.hip); otherwise `_render_jobs` followed by `ensemble_view_terms`, the views sharded over the ranks of `group` exactly as
+    `score_views` shards them (`group=False`: all views on this rank, no exchange).  All routes give the same bits.
+    Returns (uncertainty, max_idx, rows): the first two as `trajectory_uncertainty_from_terms`, `rows` the [4,V] float64 host array
+    that the reference appends to `trajector_uncertainty_list[step - 1]`."""
+    import torch.distributed as dist
+    trajectory = np.asarray(trajectory)
+    poses = trajectory[trajectory_view_indices(len(trajectory))]
+    V, M = poses.shape[0], len(radiance_fields)
+    world, rank = 1, 0
+    if group is not False and dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if one_call and world == 1:
+        lib = L.load_library()
+        c2w = torch.from_numpy(np.stack([pose_to_c2w(np.asarray(p, np.float64)) for p in poses]).astype(np.float32)[:, :3, :4].copy()).to(device)
+        h, w = int(height * scale), int(width * scale)
+        idx = torch.from_numpy(subsample_indices(width * height, h * w)).to(device)
+        handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in radiance_fields])
+        grids = [_grid_args(e) for e in estimators]
+        bins = (ctypes.c_void_p * M)(*[g.binaries.data_ptr() for g in grids])
+        bits = (ctypes.c_void_p * M)(*[g.bits.data_ptr() for g in grids])
+        opts = _render_opts(max_samples=1024, near_plane=near_plane, far_plane=1e10, render_step_size=render_step_size, cone_angle=cone_angle,
+                            alpha_thre=alpha_thre, early_stop_eps=1e-4, probabilistic=False, rays_per_view=h * w, n_levels=grids[0].n_levels)
+        C = radiance_fields[0].num_semantic_classes
+        nbytes = int(lib.mnf_score_trajectory_workspace_bytes(M, V, h * w, C))
+        ws = _workspace(torch.device(device), nbytes)
+        terms = torch.empty(V, 4, dtype=torch.float64, device=device)
+        L.launch(lib.mnf_score_trajectory, handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, width,
+                 height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(opts), L.ptr(terms), L.ptr(ws), nbytes)
+    else:
+        lo, hi, per = shard_views(V, world, rank)
+        terms_local = torch.zeros(per, 4, dtype=torch.float64, device=device)
+        if hi > lo:
+            o, d, h, w = _pose_rays(poses[lo:hi], width, height, focal, scale, device)
+            n = hi - lo
+            outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], h * w, max_samples=1024, near_plane=near_plane,
+                                far_plane=1e10, render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre,
+                                early_stop_eps=1e-4, probabilistic=False, n_split=max(1, 4 // M))
+            terms_local[:n] = ensemble_view_terms(torch.stack([r["rgb"].reshape(n, h * w, 3) for r in outs]), torch.stack([r["depth"].reshape(n, h * w) for r in outs]),
+                                                  torch.stack([r["acc"].reshape(n, h * w) for r in outs]), outs[0]["sem"].reshape(n, h * w, -1))
+        terms = terms_local[:V] if world == 1 else gather_view_terms(terms_local, V, group)
+    rows = np.ascontiguousarray(terms.cpu().numpy().T)            # the one device-to-host copy
+    uncertainty, max_idx = trajectory_uncertainty_from_terms(rows.T, step)
+    return uncertainty, max_idx, rows
+
+
 # ------------------------------------------------------------------ held-out view evaluation (pipeline.py:550-613, :650-656, :1011)
 EVAL_COLUMNS = ("rgb_mse", "psnr", "depth_mse", "sem_ce", "sem_acc", "n_valid", "n_invalid", "reserved")     # columns of mnf_eval_views' metrics rows
 

@@ -585,6 +585,41 @@ int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binari
                     int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
                     const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- ensemble-disagreement scorer */
+
+/* scripts/pipeline.py:861-882 (`trajector_uncertainty`) on device.  Inputs are the plain renders of n_members ensemble members for
+ * the same n_views views of n_pix pixels: member-major arrays rgb [M,V,P,3], depth [M,V,P], acc [M,V,P] (only member 0 is read,
+ * pipeline.py:869) and sem [S,V,P,C] f32, the class logits of the first n_sem_members = S members, 1 <= S <= M (S = 1 is the
+ * reference; S > 1 averages the entropy over those members as np.mean(sem_entropy, axis=(0,2,3)) would).
+ * Output terms [V,4] f64, the four clipped rows of pipeline.py:875-882, per view:
+ *   [0] clip(4000 * mean_p mean_ch var_m(rgb), 0, 100)            [1] clip(50 * mean_p var_m(depth), 0, 100)
+ *   [2] mean_p clip(1 / (acc_0 + 1e-4) - 1, 0, 10000)             [3] clip(50 * mean_{s,p} H, 0, 100)
+ * with H = -sum_k p_k log(p_k + 1e-10), p the softmax of the logits (maximum subtracted), and var the population variance (np.var)
+ * taken in two passes (mean over the members, then the mean squared deviation).  All arithmetic is double from the widened fp32
+ * inputs; NaN propagates as through np.clip.  No atomics: the same inputs give the same bits, and a view's row depends on that
+ * view's data, P, M, S and C only, not on n_views or on its position in the call.  The stacks need 4-byte alignment only.
+ * workspace: mnf_score_ensemble_views_workspace_bytes(V, P, C) bytes, 8-byte aligned (per-workgroup partial sums).  Argument errors
+ * (n_members < 1, S outside [1, M], a workspace that is too small) return MNF_ERR_INVALID, n_members or n_classes above the two
+ * maxima below MNF_ERR_UNSUPPORTED, both before anything is enqueued; n_views == 0 returns MNF_OK.  Enqueues on `stream` and does
+ * not synchronise. */
+#define MNF_SCORE_ENSEMBLE_MAX_MEMBERS 64
+#define MNF_SCORE_ENSEMBLE_MAX_CLASSES 1024
+int64_t mnf_score_ensemble_views_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes);
+int mnf_score_ensemble_views(const float *rgb, const float *depth, const float *acc, const float *sem, int32_t n_members,
+                             int32_t n_sem_members, int32_t n_views, int64_t n_pix, int32_t n_classes, double *terms,
+                             void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
+/* scripts/pipeline.py:807-882 for one trajectory as ONE call, the plumbing of mnf_score_poses: poses (c2w [n_views,3,4] f32, device)
+ * -> the sub-sampled rays of every view (pix_idx [n_pix] int64, device) -> every member's plain render (not probabilistic, black
+ * background, opts->max_samples per round: what Dataset.render_image_from_pose does with 1024) as a job of mnf_render_jobs, laid out
+ * member-major in the workspace -> mnf_score_ensemble_views with S = 1 -> terms [n_views,4] f64.  opts->probabilistic and
+ * opts->render_bkgd are overridden. */
+int64_t mnf_score_trajectory_workspace_bytes(int32_t n_members, int32_t n_views, int32_t n_pix, int32_t n_classes);
+int mnf_score_trajectory(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
+                         int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
+                         int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
+                         const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 /* ---------------------------------------------------------------- held-out view evaluation */
 
 /* The error metrics of scripts/pipeline.py:550-613 (per test image: F.cross_entropy on the [H*W, C] logits, F.mse_loss on rgb and

@@ -35,6 +35,7 @@ SOURCES = {
     "trainstep.hip": ["-ffp-contract=off"],
     "eval.hip": [],
     "ensemble.hip": [],
+    "frames.hip": ["-ffp-contract=off"],    # every output byte is a chain of separately rounded operations
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
 }

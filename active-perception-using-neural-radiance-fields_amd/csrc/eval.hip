@@ -17,25 +17,23 @@
 // atomic anywhere: the same inputs give the same bits.  The confusion matrix is counted with integer atomics (an LDS histogram per
 // workgroup for C <= 64, flushed with one 64-bit global atomic per non-zero cell; straight to global above that).
 #include "common.h"
+#include "stage_dev.h"
 
 namespace mnf {
 namespace {
 
 constexpr int kEvalThreads = 256;
 constexpr int kEvalMaxBlocksPerView = 512;    // depends on P and C only: a view's sums do not depend on how many views share the call
-constexpr int kEvalStageBytes = 40960;        // LDS for a tile's logits; + 16 KB histogram + the reduction scratch stays under 64 KB
+constexpr int kEvalStageBytes = kStageBytes;  // LDS for a tile's logits; + 16 KB histogram + the reduction scratch stays under 64 KB
 constexpr int kEvalHistClasses = 64;          // C <= 64: per-workgroup LDS histogram (64 * 64 * 4 B = 16 KB)
 constexpr int kEvalPartials = 6;              // rgb squared error, depth squared error, cross-entropy, correct, valid, invalid
 
 struct EvalPlan { int tp; int64_t tiles; int nb; };
 
 inline bool eval_plan(int64_t n_pix, int32_t C, EvalPlan *pl) {
-    const int64_t cs = C | 1;
-    int64_t tp = kEvalStageBytes / (cs * 4);
+    const int tp = stage_tile_pixels(C, kEvalThreads);
     if (tp < 1) return false;
-    if (tp > kEvalThreads) tp = kEvalThreads;
-    if (tp >= 4) tp &= ~(int64_t)3;           // tiles of a multiple of four pixels keep every tile of an aligned view 16-byte aligned
-    pl->tp = (int)tp;
+    pl->tp = tp;
     pl->tiles = ceil_div(n_pix, tp);
     pl->nb = (int)(pl->tiles < kEvalMaxBlocksPerView ? pl->tiles : kEvalMaxBlocksPerView);
     return true;
@@ -71,30 +69,7 @@ __global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
         const float *src = sem + e0;
         const int n = np * C;
         __syncthreads();                                             // the previous tile's rows are read; the histogram is zeroed
-        const int head = vec_ok ? min(n, (int)((4 - (e0 & 3)) & 3)) : n;
-        const int nvec = (n - head) >> 2;
-        if (Cs == C) {
-            for (int i = tid; i < head; i += kEvalThreads) stage[i] = src[i];
-            for (int q = tid; q < nvec; q += kEvalThreads) {
-                const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
-                float *dst = stage + head + 4 * q;
-                dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
-            }
-            for (int i = head + 4 * nvec + tid; i < n; i += kEvalThreads) stage[i] = src[i];
-        } else {
-            for (int i = tid; i < head; i += kEvalThreads) stage[(i / C) * Cs + i % C] = src[i];
-            for (int q = tid; q < nvec; q += kEvalThreads) {
-                const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
-                const float xs[4] = {x.x, x.y, x.z, x.w};
-                int e = head + 4 * q, p = e / C, c = e - p * C;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    stage[p * Cs + c] = xs[k];
-                    if (++c == C) { c = 0; ++p; }
-                }
-            }
-            for (int i = head + 4 * nvec + tid; i < n; i += kEvalThreads) stage[(i / C) * Cs + i % C] = src[i];
-        }
+        stage_rows<kEvalThreads>(stage, src, n, C, Cs, e0, vec_ok, tid);
         __syncthreads();
         if (tid < np) {
             const int64_t p = p0 + tid, i = (int64_t)v * P + p;
@@ -109,14 +84,9 @@ __global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
             const double dd = (double)depth[i] - (double)gd;
             s_dep += dd * dd;
             const int64_t label = sem_u8 ? (int64_t)reinterpret_cast<const uint8_t *>(sems)[g] : reinterpret_cast<const int64_t *>(sems)[g];
-            // first maximal index; a NaN counts as the maximum (torch.argmax, np.argmax)
             const float *row = stage + tid * Cs;
-            float best = row[0];
-            int arg = 0;
-            for (int c = 1; c < C; ++c) {
-                const float x = row[c];
-                if (x > best || (x != x && best == best)) { best = x; arg = c; }
-            }
+            float best;
+            const int arg = first_argmax(row, C, &best);
             if (pred_labels) pred_labels[i] = (uint8_t)arg;
             if (label >= 0 && label < C) {
                 const double m = (double)best;

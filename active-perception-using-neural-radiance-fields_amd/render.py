@@ -1497,3 +1497,113 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
         for k in ("rgb", "acc", "depth", "sem") + (("pred_labels",) if labels else ()):
             out[k] = torch.cat(imgs[k])
     return out
+
+
+# ------------------------------------------------------------------ 8-bit frames (pipeline.py:918-1023, vis_nerf_habitat.py:142-179)
+FRAME_DEPTH_PIPELINE = (25.0, 1.0, 255.0, 1.0)      # (mul, div, clip_hi, gain): np.clip(dep * 25, 0, 255), pipeline.py:1003
+FRAME_DEPTH_VIEWER = (1.0, 10.0, 1.0, 255.0)        # np.clip(depth / 10, 0, 1) * 255, vis_nerf_habitat.py:142-179
+_FRAME_PLANES = (("rgb", 3), ("depth", 1), ("occ", 1), ("sem", 3), ("labels", 1))      # name, bytes per pixel
+
+
+def _frame_palette(palette, device, n_classes):
+    pal = palette if isinstance(palette, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(palette))
+    if pal.dtype != torch.uint8 or pal.dim() != 2 or pal.shape[1] != 3:
+        raise TypeError(f"palette must be a [K,3] uint8 array or tensor (got {tuple(pal.shape)} {pal.dtype})")
+    if pal.shape[0] < n_classes:
+        raise ValueError(f"palette has {pal.shape[0]} colours for {n_classes} classes")
+    return pal.to(device).contiguous()
+
+
+def _frame_args(depth_map, channel_order, labels, n_classes):
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb' (got {channel_order!r})")
+    if labels and n_classes > 256:
+        raise ValueError("the label plane is uint8: labels=True needs at most 256 classes")
+    dm = tuple(float(x) for x in depth_map)
+    if len(dm) != 4:
+        raise ValueError("depth_map is (mul, div, clip_hi, gain): FRAME_DEPTH_PIPELINE, FRAME_DEPTH_VIEWER or four numbers of the caller's")
+    return dm, int(channel_order == "bgr")
+
+
+def _frames_into(rgb, depth, acc, sem, pal, dm, bgr, out):
+    """`mnf_frames_views` (csrc/frames.hip) on V views of P pixels into the contiguous uint8 tensors of `out` (keys of _FRAME_PLANES; no
+    "labels" key: no label plane)."""
+    C = int(sem.shape[-1])
+    V = int(sem.shape[0])
+    if V == 0 or sem.numel() % (V * C):
+        raise ValueError(f"sem of shape {tuple(sem.shape)} does not hold {V} views of {C}-class pixels")
+    P = sem.numel() // (V * C)
+    if rgb.numel() != V * P * 3 or depth.numel() != V * P or acc.numel() != V * P:
+        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} / acc {tuple(acc.shape)} do not match {V} views of {P} pixels")
+    for name, k in _FRAME_PLANES:
+        if name in out and (out[name].dtype != torch.uint8 or out[name].numel() != V * P * k or not out[name].is_contiguous()):
+            raise ValueError(f"output plane {name} does not hold {V} x {P} x {k} contiguous bytes")
+    r, d, a, s = (L.contig(t, torch.float32) for t in (rgb, depth, acc, sem))
+    L.launch(L.load_library().mnf_frames_views, L.ptr(r), L.ptr(d), L.ptr(a), L.ptr(s), V, P, C, L.ptr(pal), int(pal.shape[0]), *dm, bgr,
+             L.ptr(out["rgb"]), L.ptr(out["depth"]), L.ptr(out["occ"]), L.ptr(out["sem"]), L.ptr(out.get("labels")))
+
+
+@torch.no_grad()
+def frames_from_renders(rgb, depth, acc, sem, palette, *, depth_map=FRAME_DEPTH_PIPELINE, channel_order="bgr", labels=False):
+    """The 8-bit frames of finished renders (`mnf_frames_views`, csrc/frames.hip), as `ActiveNeRFMapper.render` writes them with `cv2.imwrite`
+    (pipeline.py:976-1023): rgb [V,P,3], depth and acc [V,P] / [V,P,1], sem [V,P,C] device planes (or their [V,H,W,...] forms), `palette` any
+    [K,3] uint8 RGB array or tensor with K >= C (the reference's is habitat_sim's `d3_40_colors_rgb`).  Returns a dict of device uint8
+    tensors with the inputs' leading shape and does not synchronise: `rgb` [...,3] = round(x * 255) in float32, `depth` = round(clip(d * mul
+    / div, 0, clip_hi) * gain) in float64 with `depth_map` = (mul, div, clip_hi, gain) (FRAME_DEPTH_PIPELINE: clip(dep * 25, 0, 255);
+    FRAME_DEPTH_VIEWER: clip(depth / 10, 0, 1) * 255), `occ` = round(acc * 255), `sem` [...,3] = palette[argmax], and with `labels=True`
+    `labels` = the argmax itself (C <= 256).  Rounding is to nearest, ties to even, after clamping to [0, 255]; a NaN gives 0.
+    `channel_order="bgr"` stores the two colour planes as `cv2.imwrite` takes them, "rgb" as they are."""
+    L.require_gpu(rgb, depth, acc, sem)
+    C = int(sem.shape[-1])
+    dm, bgr = _frame_args(depth_map, channel_order, labels, C)
+    pal = _frame_palette(palette, sem.device, C)
+    lead = tuple(sem.shape[:-1])
+    out = {name: torch.empty(*lead, *((k,) if k == 3 else ()), dtype=torch.uint8, device=sem.device)
+           for name, k in _FRAME_PLANES if name != "labels" or labels}
+    _frames_into(rgb, depth, acc, sem, pal, dm, bgr, out)
+    return out
+
+
+@torch.no_grad()
+def render_frames(radiance_field, estimator, poses, width, height, focal, near_plane, render_step_size, scale, cone_angle, alpha_thre, palette, *,
+                  depth_map=FRAME_DEPTH_PIPELINE, channel_order="bgr", labels=False, views_per_call=4, max_samples=1024, to_host=True, device="cuda:0"):
+    """`ActiveNeRFMapper.render`'s predicted frames (pipeline.py:955-1023) as one call: `poses` are rendered exactly as `render_image_from_pose`
+    renders them (the same rays, options and black background), `views_per_call` at a time so that float planes exist for one group only, and
+    every group is converted on the device (`frames_from_renders`) into its slice of ONE uint8 block: 8 bytes per pixel (9 with `labels`)
+    instead of the 272 of the float64 stacks.  A view's render does not depend on the grouping, so neither do the bytes.
+    `to_host=True`: one device-to-host copy into one pinned block and one synchronisation at the end; the returned numpy arrays `rgb`
+    [P,h,w,3], `depth` [P,h,w], `occ` [P,h,w], `sem` [P,h,w,3] (and `labels` [P,h,w]) are views of that ONE block, which they keep alive: a
+    caller that retains one of them for long retains all of them (copy it out).  `to_host=False`: the device tensors, no synchronisation."""
+    poses = np.asarray(poses)
+    N, C = int(poses.shape[0]), int(radiance_field.num_semantic_classes)
+    if N == 0:
+        raise ValueError("render_frames needs at least one pose")
+    dm, bgr = _frame_args(depth_map, channel_order, labels, C)
+    pal = _frame_palette(palette, device, C)
+    h, w = int(height * scale), int(width * scale)
+    P = h * w
+    planes = [(name, k) for name, k in _FRAME_PLANES if name != "labels" or labels]
+    block = torch.empty(N * P * sum(k for _, k in planes), dtype=torch.uint8, device=device)
+    flat, off = {}, 0
+    for name, k in planes:
+        flat[name] = block[off:off + N * P * k].view(N, P * k)
+        off += N * P * k
+    per = max(1, int(views_per_call))
+    for g0 in range(0, N, per):
+        o, d, _, _ = _pose_rays(poses[g0:g0 + per], width, height, focal, scale, device)
+        V = o.shape[0] // P
+        r = render_views(radiance_field, estimator, o, d, P, max_samples, near_plane=near_plane, render_step_size=render_step_size,
+                         render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, image_hw=(h, w), n_split=None)
+        _frames_into(r["rgb"].view(V, P, 3), r["depth"].view(V, P), r["acc"].view(V, P), r["sem"].view(V, P, C), pal, dm, bgr,
+                     {name: flat[name][g0:g0 + V] for name, _ in planes})
+    if to_host:
+        host = torch.empty(block.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(block, non_blocking=True)
+        torch.cuda.current_stream(block.device).synchronize()
+        whole = host.numpy()
+    out, off = {}, 0
+    for name, k in planes:
+        shape = (N, h, w) + ((3,) if k == 3 else ())
+        out[name] = (whole if to_host else block)[off:off + N * P * k].reshape(shape)
+        off += N * P * k
+    return out

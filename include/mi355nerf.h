@@ -557,7 +557,7 @@ int mnf_planner_map(const uint8_t *binaries, int32_t n_members, int32_t res_x, i
 /* Optional in-library kernel timing for bench.py's roofline figures: between begin and end the library brackets its main
  * launches with hipEvent pairs on the launch stream, grouped by label: "field_render" (the fused field kernel of
  * mnf_render_test), "field_density", "field_forward", "field_train_forward", "dgrad", "wgrad", "hash_scatter",
- * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views".  mnf_profile_end synchronises the events, sums
+ * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views", "frames_views".  mnf_profile_end synchronises the events, sums
  * the milliseconds per label and returns the "field_render" totals; mnf_profile_query reads any label afterwards.
  * Process-wide (backward passes run on torch's autograd thread).  Not part of the reference surface. */
 int mnf_profile_begin(void);
@@ -647,6 +647,32 @@ int mnf_eval_views(const float *rgb, const float *depth, const float *sem, int32
                    int64_t pixels_per_image, const int64_t *image_ids, const int64_t *pix_idx,
                    double *metrics, int64_t *confusion, uint8_t *pred_labels,
                    void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
+/* ---------------------------------------------------------------- 8-bit frames of finished renders */
+
+/* The frame conversion of scripts/pipeline.py:976-1023 (per rendered pose: np.float32(rgb * 255), np.clip(dep * 25, 0, 255), acc * 255,
+ * np.argmax over the float64 [h, w, C] stack, the palette indexed by the label, cv2.cvtColor to BGR, cv2.imwrite narrowing to 8 bits) and
+ * of visualization/vis_nerf_habitat.py:142-179 (clip(depth / 10, 0, 1) * 255), as one pass over the finished planes of n_views views of
+ * n_pix pixels: rgb [V,P,3], depth [V,P], acc [V,P], sem [V,P,C] f32 (any 4-byte alignment).  With
+ *   sat8(x) = x clamped to [0, 255], rounded to nearest with ties to even, NaN -> 0, +inf -> 255, -inf -> 0
+ * the outputs (each may be NULL = skipped; each may start at ANY byte; no byte outside its extent is written) are
+ *   rgb8 [V,P,3] = sat8(x * 255.0f), multiplied and rounded in float32 (what np.float32(float64(x) * 255) is);
+ *   occ8 [V,P]   = sat8((double)acc * 255.0);
+ *   dep8 [V,P]   = sat8(clip(((double)d * depth_mul) / depth_div, 0, depth_clip_hi) * depth_gain) in float64, clip = np.clip (a NaN stays
+ *                  a NaN and becomes 0): (25, 1, 255, 1) is the pipeline's mapping, (1, 10, 1, 255) the viewer's;
+ *   labels [V,P] = the first maximal logit, a NaN counting as the maximum (np.argmax); needs C <= 256;
+ *   sem8 [V,P,3] = palette[label], palette [palette_entries,3] u8 RGB on the device, palette_entries >= C.
+ * bgr != 0 stores rgb8 and sem8 channel-reversed (what cv2.imwrite takes), 0 stores RGB.  sem and palette may be NULL only when sem8 and
+ * labels both are.  Argument errors (sizes <= 0, a null plane whose output is asked for, palette_entries < C, labels with C > 256,
+ * depth_div == 0 or a non-finite depth parameter, more than 65535 views) return MNF_ERR_INVALID before any HIP call; C > 10239 returns
+ * MNF_ERR_UNSUPPORTED; n_views == 0 returns MNF_OK.  Profile label: "frames_views".  Enqueues on `stream` and does not synchronise. */
+int mnf_frames_views(const float *rgb, const float *depth, const float *acc, const float *sem,
+                     int32_t n_views, int64_t n_pix, int32_t n_classes,
+                     const uint8_t *palette, int32_t palette_entries,
+                     double depth_mul, double depth_div, double depth_clip_hi, double depth_gain,
+                     int32_t bgr,
+                     uint8_t *rgb8, uint8_t *dep8, uint8_t *occ8, uint8_t *sem8, uint8_t *labels,
+                     mnf_stream_t stream);
 
 #ifdef __cplusplus
 }

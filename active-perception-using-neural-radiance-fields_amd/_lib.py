@@ -174,6 +174,9 @@ SIGNATURES = {
     "mnf_score_ensemble_views_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32]),
     "mnf_score_ensemble_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                            c_void_p]),
+    "mnf_score_view_maps_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32]),
+    "mnf_score_view_maps": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_double), POINTER(c_double), c_void_p, c_int64, c_void_p]),
     "mnf_score_trajectory_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mnf_score_trajectory": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                        c_float, c_void_p, c_int64, POINTER(RenderOpts), c_void_p, c_void_p, c_int64, c_void_p]),

@@ -36,6 +36,7 @@ SOURCES = {
     "eval.hip": [],
     "ensemble.hip": [],
     "frames.hip": ["-ffp-contract=off"],    # every output byte is a chain of separately rounded operations
+    "infomap.hip": ["-ffp-contract=off"],   # the heat bytes are a chain of separately rounded float64 operations
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
 }

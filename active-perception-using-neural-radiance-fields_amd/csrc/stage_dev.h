@@ -1,5 +1,5 @@
 // Staging of a tile's per-pixel logit rows in LDS, shared by the kernels that walk finished renders one pixel per lane
-// (eval.hip: eval_views_kernel, frames.hip: frames_views_kernel).
+// (eval.hip: eval_views_kernel, frames.hip: frames_views_kernel, infomap.hip: infomap_views_kernel).
 #pragma once
 #include "common.h"
 

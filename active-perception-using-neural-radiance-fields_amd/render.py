@@ -1263,6 +1263,97 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
     return terms, trajectory_score(terms)
 
 
+# ------------------------------------------------------------------ predictive-information maps (pipeline.py:727-774 kept per pixel)
+SCORE_MAPS_MAX_MEMBERS, SCORE_MAPS_MAX_CLASSES = 64, 1024      # MNF_SCORE_MAPS_MAX_MEMBERS / _CLASSES (include/mi355nerf.h)
+
+
+def _heat_range(heat_range):
+    """(lo[4], hi[4]) -> two ctypes double[4] arrays, or (None, None)."""
+    if heat_range is None:
+        return None, None
+    lo, hi = (np.asarray(x, np.float64).reshape(-1) for x in heat_range)
+    if lo.size != 4 or hi.size != 4:
+        raise ValueError("heat_range is (lo[4], hi[4]): one range per term (rgb, depth, semantic, occupancy)")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (lo == hi).any():
+        raise ValueError(f"heat_range needs finite lo != hi for every term (got lo {lo.tolist()}, hi {hi.tolist()})")
+    return (ctypes.c_double * 4)(*lo), (ctypes.c_double * 4)(*hi)
+
+
+def _view_maps_into(rv, dv, ac, sm, M, V, P, C, terms, maps, heat, lo, hi):
+    """`mnf_score_view_maps` (csrc/infomap.hip) on contiguous fp32 stacks into `terms` [V,4] f64, `maps` [V,P,4] f64 and `heat` [V,P,4] u8
+    (each a contiguous device tensor or None)."""
+    lib = L.load_library()
+    with torch.cuda.device(sm.device):
+        nbytes = max(int(lib.mnf_score_view_maps_workspace_bytes(V, P, C)), 8)
+        ws = _workspace((sm.device, "infomap"), nbytes)
+        L.launch(lib.mnf_score_view_maps, L.ptr(rv), L.ptr(dv), L.ptr(ac), L.ptr(sm), M, V, P, C, L.ptr(terms), L.ptr(maps), L.ptr(heat), lo, hi, L.ptr(ws),
+                 nbytes)
+
+
+@torch.no_grad()
+def view_information_maps(rgb_var, depth_var, acc, sem, *, maps=True, heat_range=None):
+    """Where a candidate view carries predictive information: the four terms of `score_view_terms` kept per pixel, on the device
+    (`mnf_score_view_maps`, csrc/infomap.hip).  Inputs as `score_view_terms` takes them: member-major stacks of the probabilistic renders
+    of M ensemble members for the same V views of P pixels, rgb_var [M,V,P,3], depth_var [M,V,P], acc [M,V,P], sem [M,V,P,C] (fp32, GPU);
+    up to 64 members and 1024 classes.  Returns (terms, maps, heat) and does not synchronise:
+      terms [V,4] float64      the per-view means (rgb, depth, semantic, occupancy; un-weighted: `trajectory_score` weighs them);
+      maps [V,P,4] float64     the terms of every pixel, or None with `maps=False`;
+      heat [V,P,4] uint8       round(clip((x - lo_k) / (hi_k - lo_k) * 255, 0, 255)) (ties to even, NaN -> 0) for `heat_range` = (lo[4],
+                               hi[4]), ready to index a colour table of the caller's; None without a range.
+    A view's rows depend on that view's data only: a view scored alone or inside any batch gives the same bits."""
+    if sem.dim() != 4 or rgb_var.dim() != 4 or rgb_var.shape[-1] != 3:
+        raise ValueError(f"view_information_maps takes rgb_var [M,V,P,3] and sem [M,V,P,C] (got {tuple(rgb_var.shape)}, {tuple(sem.shape)})")
+    M, V, P, C = (int(x) for x in sem.shape)
+    if tuple(rgb_var.shape) != (M, V, P, 3) or depth_var.numel() != M * V * P or acc.numel() != M * V * P:
+        raise ValueError(f"rgb_var {tuple(rgb_var.shape)} / depth_var {tuple(depth_var.shape)} / acc {tuple(acc.shape)} do not match {M} members of {V} views "
+                         f"of {P} pixels")
+    if min(M, P, C) < 1:
+        raise ValueError(f"view_information_maps needs at least one member, pixel and class (got M = {M}, P = {P}, C = {C})")
+    if M > SCORE_MAPS_MAX_MEMBERS or C > SCORE_MAPS_MAX_CLASSES:
+        raise ValueError(f"{M} members of {C} classes are more than the supported {SCORE_MAPS_MAX_MEMBERS} members of {SCORE_MAPS_MAX_CLASSES} classes")
+    lo, hi = _heat_range(heat_range)
+    L.require_gpu(rgb_var, depth_var, acc, sem)
+    rv, dv, ac, sm = (L.contig(t, torch.float32) for t in (rgb_var, depth_var, acc, sem))
+    terms = torch.empty(V, 4, dtype=torch.float64, device=sem.device)
+    out_maps = torch.empty(V, P, 4, dtype=torch.float64, device=sem.device) if maps else None
+    heat = torch.empty(V, P, 4, dtype=torch.uint8, device=sem.device) if lo is not None else None
+    _view_maps_into(rv, dv, ac, sm, M, V, P, C, terms, out_maps, heat, lo, hi)
+    return terms, out_maps, heat
+
+
+@torch.no_grad()
+def score_view_maps(radiance_fields, estimators, poses, width, height, focal, near_plane, render_step_size, scale, cone_angle,
+                    alpha_thre, device="cuda:0", *, heat_range=None, views_per_call=None):
+    """`score_views` on one rank with the per-pixel maps kept: `poses` are rendered exactly as `score_views` renders them (the same render
+    jobs with the same options), `views_per_call` poses at a time (None: all at once) so that the members' probabilistic planes exist for
+    one group only (a 640 x 640 view holds 59 MB of them per member), and every group is reduced on the device (`view_information_maps`)
+    into its slice of the outputs.  A view's render and its rows do not depend on the grouping, so neither do the bits.
+    Returns a dict of device tensors: `terms` [V,4] float64, `score` = `trajectory_score(terms)`, `maps` [V,h,w,4] float64, and `heat`
+    [V,h,w,4] uint8 for `heat_range` = (lo[4], hi[4]) (None without one)."""
+    poses = np.asarray(poses)
+    N, M = int(poses.shape[0]), len(radiance_fields)
+    if N == 0:
+        raise ValueError("score_view_maps needs at least one pose")
+    lo, hi = _heat_range(heat_range)
+    h, w = int(height * scale), int(width * scale)
+    P, C = h * w, int(radiance_fields[0].num_semantic_classes)
+    terms = torch.empty(N, 4, dtype=torch.float64, device=device)
+    maps = torch.empty(N, P, 4, dtype=torch.float64, device=device)
+    heat = torch.empty(N, P, 4, dtype=torch.uint8, device=device) if lo is not None else None
+    per = N if views_per_call is None else max(1, int(views_per_call))
+    for g0 in range(0, N, per):
+        o, d, _, _ = _pose_rays(poses[g0:g0 + per], width, height, focal, scale, device)
+        n = o.shape[0] // P
+        outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], P, max_samples=1024, near_plane=near_plane, far_plane=1e10,
+                            render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=1e-4,
+                            probabilistic=True, n_split=max(1, 4 // M))
+        rv = torch.stack([r["rgb_var"].reshape(n, P, 3) for r in outs]); dv = torch.stack([r["depth_var"].reshape(n, P) for r in outs])
+        ac = torch.stack([r["acc"].reshape(n, P) for r in outs]); sm = torch.stack([r["sem"].reshape(n, P, -1) for r in outs])
+        _view_maps_into(*(L.contig(t, torch.float32) for t in (rv, dv, ac, sm)), M, n, P, C, terms[g0:g0 + n], maps[g0:g0 + n],
+                        heat[g0:g0 + n] if heat is not None else None, lo, hi)
+    return dict(terms=terms, score=trajectory_score(terms), maps=maps.view(N, h, w, 4), heat=heat.view(N, h, w, 4) if heat is not None else None)
+
+
 # ------------------------------------------------------------------ ensemble-disagreement scorer (pipeline.py:800-916)
 ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_CLASSES = 64, 1024      # MNF_SCORE_ENSEMBLE_MAX_MEMBERS / _CLASSES (include/mi355nerf.h)
 

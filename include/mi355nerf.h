@@ -557,7 +557,7 @@ int mnf_planner_map(const uint8_t *binaries, int32_t n_members, int32_t res_x, i
 /* Optional in-library kernel timing for bench.py's roofline figures: between begin and end the library brackets its main
  * launches with hipEvent pairs on the launch stream, grouped by label: "field_render" (the fused field kernel of
  * mnf_render_test), "field_density", "field_forward", "field_train_forward", "dgrad", "wgrad", "hash_scatter",
- * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views", "frames_views".  mnf_profile_end synchronises the events, sums
+ * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views", "frames_views", "score_view_maps".  mnf_profile_end synchronises the events, sums
  * the milliseconds per label and returns the "field_render" totals; mnf_profile_query reads any label afterwards.
  * Process-wide (backward passes run on torch's autograd thread).  Not part of the reference surface. */
 int mnf_profile_begin(void);
@@ -584,6 +584,41 @@ int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binari
                     int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
                     int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
                     const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
+/* ---------------------------------------------------------------- predictive-information maps */
+
+/* scripts/pipeline.py:727-774 on device with the four terms KEPT PER PIXEL (the reference forms them as [V,h,w] arrays and collapses
+ * each with np.mean at :735 / :746 / :760 / :773; a caller who wants to see where a view carries information redoes them on the host
+ * from six float64 stacks, 272 bytes per pixel at M = 2, C = 29).  Inputs as mnf_score_views': the probabilistic renders of n_members
+ * ensemble members for the same n_views views of n_pix pixels, member-major rgb_var [M,V,P,3], depth_var [M,V,P], acc [M,V,P],
+ * sem [M,V,P,C] f32 (any 4-byte alignment).  Per pixel, in double from the widened fp32 inputs, k = 2 pi e, members added in order:
+ *   [0] rgb    mean over the three channels of  log(k (sum_m x) / 2 + 1e-4) / 2 - (1 / M) sum_m log(k x_m + 1e-4) / 2
+ *              (the / 2 under the first logarithm is the reference's, whatever M is: pipeline.py:733)
+ *   [1] depth  the same expression on the one channel of depth_var
+ *   [2] sem    H(mean_m p_m) - mean_m H(p_m), p_m the softmax of member m's logits (maximum subtracted),
+ *              H(q) = -sum_k (q_k + 1e-4) log(q_k + 1e-4)
+ *   [3] occ    B(mean_m a_m) - mean_m B(a_m), B(a) = -(a + 1e-4) log(a + 1e-4) - (1 - a + 1e-4) log(1 - a + 1e-4)
+ * NaN and inf propagate as they do in numpy.  Outputs (each may be NULL = skipped, at least one must not be; no byte outside an
+ * output's extent is written):
+ *   terms [V,4] f64   the per-view means, un-weighted, in mnf_score_views' column order; 8-byte aligned;
+ *   maps [V,P,4] f64  the four terms of every pixel; 8-byte aligned (16-byte aligned bases are stored with 16-byte stores);
+ *   heat8 [V,P,4] u8  sat8(((x - lo_k) / (hi_k - lo_k)) * 255.0) in float64 with exactly those operations in that order,
+ *                     sat8 as mnf_frames_views' (clamp to [0, 255], round to nearest even, NaN -> 0), lo = heat_lo_host[4] and
+ *                     hi = heat_hi_host[4] HOST doubles, hi < lo reverses a ramp; 4-byte aligned.  A colour look-up table is the
+ *                     caller's: index it with these bytes.
+ * No atomics: the same inputs give the same bits, and a view's rows depend on that view's data, P, M and C only, not on n_views or
+ * on its position in the call.  workspace: mnf_score_view_maps_workspace_bytes(V, P, C) bytes, 8-byte aligned (per-workgroup partial
+ * sums; read only when terms is asked for).  Argument errors (a size < 1, all three outputs NULL, heat8 without its ranges, hi == lo or
+ * a non-finite range, a misaligned maps / heat8, a workspace that is too small, more than 65535 views) return MNF_ERR_INVALID,
+ * n_members or n_classes above the two maxima below MNF_ERR_UNSUPPORTED, both before any HIP call; n_views == 0 returns MNF_OK.
+ * Profile label: "score_view_maps".  Enqueues on `stream` and does not synchronise. */
+#define MNF_SCORE_MAPS_MAX_MEMBERS 64
+#define MNF_SCORE_MAPS_MAX_CLASSES 1024
+int64_t mnf_score_view_maps_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes);
+int mnf_score_view_maps(const float *rgb_var, const float *depth_var, const float *acc, const float *sem, int32_t n_members,
+                        int32_t n_views, int64_t n_pix, int32_t n_classes, double *terms, double *maps, uint8_t *heat8,
+                        const double *heat_lo_host, const double *heat_hi_host, void *workspace, int64_t workspace_bytes,
+                        mnf_stream_t stream);
 
 /* ---------------------------------------------------------------- ensemble-disagreement scorer */
 

@@ -5,47 +5,20 @@
 //
 // One pass over the finished plain (non-probabilistic) renders of M members for the same V views of P pixels.
 //
-// Work split, as eval.hip's: a view's pixels are cut into tiles of `tp` pixels, a view's tiles into `nb` contiguous runs, one workgroup per
-// (run, view); tp and nb depend on P and C only, so a view's sums do not depend on how many views share the call or where it stands.
-// For every member s < S whose logits enter the entropy, a tile's tp * C logits are one contiguous piece of `sem`: the workgroup copies it
-// to LDS with 16-byte loads per lane (scalar loads up to the first 16-byte boundary of the ADDRESS and after the last, so a base that is
-// only 4-byte aligned is read wide as well), then lane t works on pixel t out of LDS, whose row stride C | 1 is odd: the 32 lanes of a
-// ds_read_b32 group hit 32 different banks.  Every logit is read from memory once.  The rgb / depth stacks are read once per pass of the
-// two-pass variance (mean over the members, then the mean squared deviation: the second pass hits the cache); a sum-of-squares form
-// cancels at depth 5 +- 1e-3 and is not used.  Per pixel (3 M + M + 1 + S C) * 4 bytes come from HBM.
+// The work split, the logit staging and the reduction of the four sums are view_dev.h's; a tile is staged once for every member s < S whose
+// logits enter the entropy, so every logit is read from memory once.  The rgb / depth stacks are read once per pass of the two-pass variance
+// (mean over the members, then the mean squared deviation: the second pass hits the cache); a sum-of-squares form cancels at depth 5 +- 1e-3
+// and is not used.  Per pixel (3 M + M + 1 + S C) * 4 bytes come from HBM.
 //
 // Everything is double from the widened fp32 inputs: ~2 C double exp / log per pixel and member, which is nothing beside the renders
-// (the fp64 transcendentals are software sequences of a few dozen fp64 FMAs at half the fp32 vector rate).  Sums are carried per lane over its
-// pixels, then a shuffle tree per wave, then the four waves in order, then ONE row of four partial sums per workgroup in the caller's
-// workspace; ensemble_finish_kernel adds a view's rows in a fixed order, scales and clips.  No atomic anywhere: the same inputs give the
-// same bits.  The clips are written as comparisons, so a NaN stays a NaN as it does through np.clip.
-#include "common.h"
+// (the fp64 transcendentals are software sequences of a few dozen fp64 FMAs at half the fp32 vector rate).  ensemble_finish_kernel scales
+// and clips a view's sums; the clips are written as comparisons, so a NaN stays a NaN as it does through np.clip.
+#include "view_dev.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kEnsThreads = 256;
-constexpr int kEnsMaxBlocksPerView = 512;      // depends on P and C only
-constexpr int kEnsStageBytes = 40960;          // LDS for a tile's logits
 constexpr int kEnsPartials = 4;                // sum_p,ch var_m(rgb); sum_p var_m(depth); sum_p clip(1/acc0 - 1); sum_s,p H
-
-struct EnsPlan { int tp; int64_t tiles; int nb; };
-
-inline void ens_plan(int64_t n_pix, int32_t C, EnsPlan *pl) {
-    const int64_t cs = C | 1;
-    int64_t tp = kEnsStageBytes / (cs * 4);       // >= 9 for C <= MNF_SCORE_ENSEMBLE_MAX_CLASSES
-    if (tp > kEnsThreads) tp = kEnsThreads;
-    if (tp >= 4) tp &= ~(int64_t)3;
-    pl->tp = (int)tp;
-    pl->tiles = ceil_div(n_pix, tp);
-    pl->nb = (int)(pl->tiles < kEnsMaxBlocksPerView ? pl->tiles : kEnsMaxBlocksPerView);
-}
-
-__device__ __forceinline__ double ens_wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
 
 // population variance of x[0], x[stride], ..., x[(M - 1) * stride] (np.var, ddof 0), two passes
 __device__ __forceinline__ double member_var(const float *__restrict__ x, int64_t stride, int M) {
@@ -60,11 +33,10 @@ __device__ __forceinline__ double member_var(const float *__restrict__ x, int64_
     return ss / (double)M;
 }
 
-__global__ void __launch_bounds__(kEnsThreads) ensemble_views_kernel(
+__global__ void __launch_bounds__(kViewThreads) ensemble_views_kernel(
     const float *__restrict__ rgb, const float *__restrict__ depth, const float *__restrict__ acc, const float *__restrict__ sem, int M, int S,
     int V, int64_t P, int C, int tp, int64_t tiles, double *__restrict__ partials) {
     extern __shared__ float stage[];                                 // [tp][C | 1]
-    __shared__ double red[kEnsThreads / 64][kEnsPartials];
     const int tid = threadIdx.x, v = blockIdx.y, nb = gridDim.x, b = blockIdx.x;
     const int Cs = C | 1;
     const int64_t VP = (int64_t)V * P;
@@ -82,33 +54,8 @@ __global__ void __launch_bounds__(kEnsThreads) ensemble_views_kernel(
             s_acc += inv < 0.0 ? 0.0 : (inv > 10000.0 ? 10000.0 : inv);
         }
         for (int s = 0; s < S; ++s) {
-            const float *src = sem + (((int64_t)s * V + v) * P + p0) * C;
-            const int n = np * C;
             __syncthreads();                                         // the previous piece's rows are read
-            const int head = min(n, (int)(((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 2));
-            const int nvec = (n - head) >> 2;
-            if (Cs == C) {
-                for (int i = tid; i < head; i += kEnsThreads) stage[i] = src[i];
-                for (int q = tid; q < nvec; q += kEnsThreads) {
-                    const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
-                    float *dst = stage + head + 4 * q;
-                    dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
-                }
-                for (int i = head + 4 * nvec + tid; i < n; i += kEnsThreads) stage[i] = src[i];
-            } else {
-                for (int i = tid; i < head; i += kEnsThreads) stage[(i / C) * Cs + i % C] = src[i];
-                for (int q = tid; q < nvec; q += kEnsThreads) {
-                    const float4 x = *reinterpret_cast<const float4 *>(src + head + 4 * q);
-                    const float xs[4] = {x.x, x.y, x.z, x.w};
-                    int e = head + 4 * q, p = e / C, c = e - p * C;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        stage[p * Cs + c] = xs[k];
-                        if (++c == C) { c = 0; ++p; }
-                    }
-                }
-                for (int i = head + 4 * nvec + tid; i < n; i += kEnsThreads) stage[(i / C) * Cs + i % C] = src[i];
-            }
+            stage_rows(stage, sem + (((int64_t)s * V + v) * P + p0) * C, np * C, C, Cs, tid);
             __syncthreads();
             if (tid < np) {
                 // H = -sum_k p_k log(p_k + 1e-10), p the float64 softmax with the maximum subtracted (pipeline.py:864-865)
@@ -128,34 +75,16 @@ __global__ void __launch_bounds__(kEnsThreads) ensemble_views_kernel(
         }
     }
     const double part[kEnsPartials] = {s_rgb, s_dep, s_acc, s_ent};
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < kEnsPartials; ++k) {
-        const double w = ens_wave_sum(part[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-    __syncthreads();
-    if (tid < kEnsPartials) {
-        double s = red[0][tid];
-        for (int w = 1; w < kEnsThreads / 64; ++w) s += red[w][tid];
-        partials[((int64_t)v * nb + b) * kEnsPartials + tid] = s;
-    }
+    store_partials(part, partials, v, nb, b, tid);
 }
 
 __device__ __forceinline__ double clip100(double x) { return x < 0.0 ? 0.0 : (x > 100.0 ? 100.0 : x); }
 
-// one wave per view: lane l adds rows l, l + 64, ... in order, then the shuffle tree; pipeline.py:875-882
+// one wave per view; pipeline.py:875-882
 __global__ void __launch_bounds__(64) ensemble_finish_kernel(const double *__restrict__ partials, int nb, int64_t P, int S, double *__restrict__ terms) {
     const int v = blockIdx.x, lane = threadIdx.x;
     double s[kEnsPartials];
-#pragma unroll
-    for (int k = 0; k < kEnsPartials; ++k) s[k] = 0.0;
-    for (int b = lane; b < nb; b += 64) {
-#pragma unroll
-        for (int k = 0; k < kEnsPartials; ++k) s[k] += partials[((int64_t)v * nb + b) * kEnsPartials + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kEnsPartials; ++k) s[k] = ens_wave_sum(s[k]);
+    sum_partials(partials, v, nb, lane, s);
     if (lane == 0) {
         double *t = terms + (int64_t)v * 4;
         t[0] = clip100(s[0] / (3.0 * (double)P) * 4000.0);
@@ -176,9 +105,7 @@ using namespace mnf;
 
 extern "C" int64_t mnf_score_ensemble_views_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes) {
     if (!ens_sizes_ok(n_views, n_pix, n_classes)) return 0;
-    EnsPlan pl;
-    ens_plan(n_pix, n_classes, &pl);
-    return (int64_t)n_views * pl.nb * kEnsPartials * (int64_t)sizeof(double);
+    return view_partials_bytes(n_views, view_plan(n_pix, stage_tile_pixels(n_classes)).nb, kEnsPartials);
 }
 
 extern "C" int mnf_score_ensemble_views(const float *rgb, const float *depth, const float *acc, const float *sem, int32_t n_members,
@@ -202,14 +129,13 @@ extern "C" int mnf_score_ensemble_views(const float *rgb, const float *depth, co
     MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(terms) & 7) == 0,
                 "score_ensemble_views: workspace and terms must be 8-byte aligned");
     MNF_REQUIRE(n_views <= 65535, "score_ensemble_views: at most 65535 views per call (got %d)", n_views);
-    EnsPlan pl;
-    ens_plan(n_pix, n_classes, &pl);
-    const int64_t need = (int64_t)n_views * pl.nb * kEnsPartials * (int64_t)sizeof(double);
+    const ViewPlan pl = view_plan(n_pix, stage_tile_pixels(n_classes));      // a tile of >= 8 pixels for C <= MNF_SCORE_ENSEMBLE_MAX_CLASSES
+    const int64_t need = view_partials_bytes(n_views, pl.nb, kEnsPartials);
     MNF_REQUIRE(workspace_bytes >= need, "score_ensemble_views: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     hipStream_t s = as_stream(stream);
     ProfScope prof("score_ensemble_views", s);
     const size_t lds = (size_t)pl.tp * (n_classes | 1) * sizeof(float);
-    hipLaunchKernelGGL(ensemble_views_kernel, dim3(pl.nb, n_views), dim3(kEnsThreads), lds, s, rgb, depth, acc, sem, n_members, n_sem_members, n_views, n_pix,
+    hipLaunchKernelGGL(ensemble_views_kernel, dim3(pl.nb, n_views), dim3(kViewThreads), lds, s, rgb, depth, acc, sem, n_members, n_sem_members, n_views, n_pix,
                        n_classes, pl.tp, pl.tiles, reinterpret_cast<double *>(workspace));
     int rc = launch_status("ensemble_views_kernel");
     if (rc) return rc;

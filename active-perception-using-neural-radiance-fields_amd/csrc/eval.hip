@@ -6,58 +6,29 @@
 // One pass over the finished renders of V views of P pixels.  Ground truth is read straight from the dataset's storage (u8 images,
 // f32 / f16 depths, i64 / u8 labels: the two layouts of gather_pixels_kernel, march.hip); no fp32 ground-truth image is written.
 //
-// Work split: a view's pixels are cut into tiles of `tp` pixels, a view's tiles into `nb` contiguous runs, one workgroup per (run, view).
-// A tile's tp * C logits are one contiguous piece of `sem`: the workgroup copies it to LDS with 16-byte loads per lane (scalar loads up
-// to the first 16-byte boundary and after the last), then lane t works on pixel t out of LDS, whose row stride C | 1 is odd, so the 32
-// lanes of an LDS access hit 32 different banks.  Per pixel (3 + 1 + C) * 4 bytes of render and 15 (u8 / f32 / i64) or 6 (u8 / f16 / u8)
-// bytes of ground truth are read, once.
-//
-// Sums are carried in double: per lane over its pixels, then a shuffle tree per wave, then the four waves in order, then ONE row of
-// partial sums per workgroup in the caller's workspace; eval_finish_kernel adds a view's rows in a fixed order.  No floating-point
-// atomic anywhere: the same inputs give the same bits.  The confusion matrix is counted with integer atomics (an LDS histogram per
-// workgroup for C <= 64, flushed with one 64-bit global atomic per non-zero cell; straight to global above that).
-#include "common.h"
-#include "stage_dev.h"
+// The work split, the logit staging and the reduction of the six sums are view_dev.h's.  Per pixel (3 + 1 + C) * 4 bytes of render and 15
+// (u8 / f32 / i64) or 6 (u8 / f16 / u8) bytes of ground truth are read, once.  The confusion matrix is counted with integer atomics (an LDS
+// histogram per workgroup for C <= 64, flushed with one 64-bit global atomic per non-zero cell; straight to global above that).
+#include "view_dev.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kEvalThreads = 256;
-constexpr int kEvalMaxBlocksPerView = 512;    // depends on P and C only: a view's sums do not depend on how many views share the call
-constexpr int kEvalStageBytes = kStageBytes;  // LDS for a tile's logits; + 16 KB histogram + the reduction scratch stays under 64 KB
-constexpr int kEvalHistClasses = 64;          // C <= 64: per-workgroup LDS histogram (64 * 64 * 4 B = 16 KB)
+constexpr int kEvalHistClasses = 64;          // C <= 64: per-workgroup LDS histogram (64 * 64 * 4 B = 16 KB; + kStageBytes + the reduction scratch < 64 KB)
 constexpr int kEvalPartials = 6;              // rgb squared error, depth squared error, cross-entropy, correct, valid, invalid
 
-struct EvalPlan { int tp; int64_t tiles; int nb; };
-
-inline bool eval_plan(int64_t n_pix, int32_t C, EvalPlan *pl) {
-    const int tp = stage_tile_pixels(C, kEvalThreads);
-    if (tp < 1) return false;
-    pl->tp = tp;
-    pl->tiles = ceil_div(n_pix, tp);
-    pl->nb = (int)(pl->tiles < kEvalMaxBlocksPerView ? pl->tiles : kEvalMaxBlocksPerView);
-    return true;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
-__global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
+__global__ void __launch_bounds__(kViewThreads) eval_views_kernel(
     const float *__restrict__ rgb, const float *__restrict__ depth, const float *__restrict__ sem, int64_t P, int C, int tp, int64_t tiles,
-    int vec_ok, const uint8_t *__restrict__ images, const void *__restrict__ depths, int depth_f16, const void *__restrict__ sems, int sem_u8,
+    const uint8_t *__restrict__ images, const void *__restrict__ depths, int depth_f16, const void *__restrict__ sems, int sem_u8,
     int64_t pixels_per_image, const int64_t *__restrict__ image_ids, const int64_t *__restrict__ pix_idx, double *__restrict__ partials,
     unsigned long long *__restrict__ confusion, uint8_t *__restrict__ pred_labels) {
     extern __shared__ float stage[];                                 // [tp][C | 1]
     __shared__ unsigned int hist[kEvalHistClasses * kEvalHistClasses];
-    __shared__ double red[kEvalThreads / 64][kEvalPartials];
     const int tid = threadIdx.x, v = blockIdx.y, nb = gridDim.x, b = blockIdx.x;
     const int Cs = C | 1;
     const bool lds_hist = confusion && C <= kEvalHistClasses;
     if (lds_hist) {
-        for (int i = tid; i < C * C; i += kEvalThreads) hist[i] = 0u;
+        for (int i = tid; i < C * C; i += kViewThreads) hist[i] = 0u;
     }
     const int64_t gt_base = image_ids[v] * pixels_per_image;
     const int64_t t0 = tiles * b / nb, t1 = tiles * (b + 1) / nb;
@@ -65,11 +36,8 @@ __global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t p0 = t * tp;
         const int np = (int)(P - p0 < tp ? P - p0 : tp);
-        const int64_t e0 = ((int64_t)v * P + p0) * C;
-        const float *src = sem + e0;
-        const int n = np * C;
         __syncthreads();                                             // the previous tile's rows are read; the histogram is zeroed
-        stage_rows<kEvalThreads>(stage, src, n, C, Cs, e0, vec_ok, tid);
+        stage_rows(stage, sem + ((int64_t)v * P + p0) * C, np * C, C, Cs, tid);
         __syncthreads();
         if (tid < np) {
             const int64_t p = p0 + tid, i = (int64_t)v * P + p;
@@ -102,39 +70,21 @@ __global__ void __launch_bounds__(kEvalThreads) eval_views_kernel(
             }
         }
     }
-    double part[kEvalPartials] = {s_rgb, s_dep, s_ce, n_ok, n_valid, n_bad};
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < kEvalPartials; ++k) {
-        const double w = wave_sum(part[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-    __syncthreads();                                                 // also: every histogram count of this workgroup is in
-    if (tid < kEvalPartials) {
-        double s = red[0][tid];
-        for (int w = 1; w < kEvalThreads / 64; ++w) s += red[w][tid];
-        partials[((int64_t)v * nb + b) * kEvalPartials + tid] = s;
-    }
+    const double part[kEvalPartials] = {s_rgb, s_dep, s_ce, n_ok, n_valid, n_bad};
+    store_partials(part, partials, v, nb, b, tid);                   // its barrier also: every histogram count of this workgroup is in
     if (lds_hist) {
-        for (int i = tid; i < C * C; i += kEvalThreads) {
+        for (int i = tid; i < C * C; i += kViewThreads) {
             const unsigned int n = hist[i];
             if (n) atomicAdd(&confusion[i], (unsigned long long)n);
         }
     }
 }
 
-// one wave per view: lane l adds rows l, l + 64, ... in order, then the shuffle tree
+// one wave per view
 __global__ void __launch_bounds__(64) eval_finish_kernel(const double *__restrict__ partials, int nb, int64_t P, double *__restrict__ metrics) {
     const int v = blockIdx.x, lane = threadIdx.x;
     double s[kEvalPartials];
-#pragma unroll
-    for (int k = 0; k < kEvalPartials; ++k) s[k] = 0.0;
-    for (int b = lane; b < nb; b += 64) {
-#pragma unroll
-        for (int k = 0; k < kEvalPartials; ++k) s[k] += partials[((int64_t)v * nb + b) * kEvalPartials + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kEvalPartials; ++k) s[k] = wave_sum(s[k]);
+    sum_partials(partials, v, nb, lane, s);
     if (lane == 0) {
         double *m = metrics + (int64_t)v * 8;
         const double mse = s[0] / (double)(3 * P);
@@ -156,9 +106,8 @@ __global__ void __launch_bounds__(64) eval_finish_kernel(const double *__restric
 using namespace mnf;
 
 extern "C" int64_t mnf_eval_views_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes) {
-    EvalPlan pl;
-    if (n_views < 0 || n_pix <= 0 || n_classes <= 0 || !eval_plan(n_pix, n_classes, &pl)) return 0;
-    return (int64_t)n_views * pl.nb * kEvalPartials * (int64_t)sizeof(double);
+    if (n_views < 0 || n_pix <= 0 || n_classes <= 0 || stage_tile_pixels(n_classes) < 1) return 0;
+    return view_partials_bytes(n_views, view_plan(n_pix, stage_tile_pixels(n_classes)).nb, kEvalPartials);
 }
 
 extern "C" int mnf_eval_views(const float *rgb, const float *depth, const float *sem, int32_t n_views, int64_t n_pix, int32_t n_classes,
@@ -184,21 +133,20 @@ extern "C" int mnf_eval_views(const float *rgb, const float *depth, const float 
     MNF_REQUIRE(metrics, "eval_views: metrics is null");
     MNF_REQUIRE(workspace, "eval_views: workspace is null");
     MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "eval_views: workspace must be 8-byte aligned");
-    EvalPlan pl;
-    if (!eval_plan(n_pix, n_classes, &pl)) {
-        set_error("eval_views: n_classes = %d is more than one LDS tile holds (%d)", n_classes, kEvalStageBytes / 4 - 1);
+    const int tp = stage_tile_pixels(n_classes);
+    if (tp < 1) {
+        set_error("eval_views: n_classes = %d is more than one LDS tile holds (%d)", n_classes, kStageBytes / 4 - 1);
         return MNF_ERR_UNSUPPORTED;
     }
-    const int64_t need = (int64_t)n_views * pl.nb * kEvalPartials * (int64_t)sizeof(double);
+    const ViewPlan pl = view_plan(n_pix, tp);
+    const int64_t need = view_partials_bytes(n_views, pl.nb, kEvalPartials);
     MNF_REQUIRE(workspace_bytes >= need, "eval_views: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     MNF_REQUIRE(n_views <= 65535, "eval_views: at most 65535 views per call (got %d)", n_views);
     hipStream_t s = as_stream(stream);
     ProfScope prof("eval_views", s);
     if (confusion) MNF_HIP(hipMemsetAsync(confusion, 0, (size_t)n_classes * n_classes * sizeof(int64_t), s));    // written, not accumulated into
-    const int vec_ok = (reinterpret_cast<uintptr_t>(sem) & 15) == 0;
     const size_t lds = (size_t)pl.tp * (n_classes | 1) * sizeof(float);
-    hipLaunchKernelGGL(eval_views_kernel, dim3(pl.nb, n_views), dim3(kEvalThreads), lds, s, rgb, depth, sem, n_pix, n_classes, pl.tp, pl.tiles, vec_ok,
-                       gt_images, gt_depths, depth_is_f16, gt_semantics, sem_is_u8, pixels_per_image, image_ids, pix_idx,
+    hipLaunchKernelGGL(eval_views_kernel, dim3(pl.nb, n_views), dim3(kViewThreads), lds, s, rgb, depth, sem, n_pix, n_classes, pl.tp, pl.tiles, gt_images, gt_depths, depth_is_f16, gt_semantics, sem_is_u8, pixels_per_image, image_ids, pix_idx,
                        reinterpret_cast<double *>(workspace), reinterpret_cast<unsigned long long *>(confusion), pred_labels);
     int rc = launch_status("eval_views_kernel");
     if (rc) return rc;

@@ -7,11 +7,10 @@
 // One streaming pass over the finished planes of V views of P pixels: (3 + 1 + 1 + C) * 4 bytes are read per pixel, once, and
 // 3 + 1 + 1 + 3 (+ 1 with the label plane) bytes are written.
 //
-// Work split (that of eval_views_kernel): a view's pixels are cut into tiles of `tp` pixels, a view's tiles into `nb` contiguous runs, one
-// workgroup per (run, view).  A tile's tp * C logits are staged in LDS (stage_dev.h), then lane t works on pixel t.
+// The work split and the logit staging are view_dev.h's; the stage exists only when a label is needed (a tile is 256 pixels otherwise).
 //
 // Every byte is a chain of separately rounded operations (this file is compiled with -ffp-contract=off):
-//   sat8(x)  = x clamped to [0, 255] and rounded to nearest, ties to even; NaN -> 0, +inf -> 255, -inf -> 0
+//   sat8(x)  = view_dev.h's: x clamped to [0, 255] and rounded to nearest, ties to even; NaN -> 0, +inf -> 255, -inf -> 0
 //   rgb8     = sat8(x * 255.0f), the product rounded to float32: np.float32(float64(x) * 255) is that number, since x * 255 is exact in
 //              float64 and is then rounded once
 //   occ8     = sat8((double)acc * 255.0)
@@ -23,30 +22,15 @@
 // bytes: a tile's bytes of each plane are assembled in LDS, shifted by the destination's offset inside its dword, and go out as whole
 // aligned dwords, one per lane; the (at most two) dwords that the tile only partly owns are stored byte by byte.  Nothing outside
 // an output's [V * P * k] bytes is written, and nothing inside it is read.
-#include "common.h"
-#include "stage_dev.h"
+#include "view_dev.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kFramesThreads = 256;
-constexpr int kFramesMaxBlocksPerView = 512;
-constexpr int kFramesWords3 = (kFramesThreads * 3 + 3) / 4 + 1;    // dwords of a tile's 3-byte plane shifted by up to 3 bytes
-constexpr int kFramesWords1 = (kFramesThreads + 3) / 4 + 1;
+constexpr int kFramesWords3 = (kViewThreads * 3 + 3) / 4 + 1;      // dwords of a tile's 3-byte plane shifted by up to 3 bytes
+constexpr int kFramesWords1 = (kViewThreads + 3) / 4 + 1;
 
 struct FrameDepth { double mul, div, hi, gain; };
-
-__device__ __forceinline__ uint8_t sat8(float y) {
-    if (!(y > 0.0f)) return 0;                                     // negative, -inf, NaN, zero
-    if (y >= 255.0f) return 255;
-    return (uint8_t)(int)rintf(y);                                 // round half to even
-}
-
-__device__ __forceinline__ uint8_t sat8(double y) {
-    if (!(y > 0.0)) return 0;
-    if (y >= 255.0) return 255;
-    return (uint8_t)(int)rint(y);
-}
 
 // Store the n bytes buf[mis .. mis + n) to dst[0 .. n), mis = dst & 3: dword w of `buf` is the aligned global dword at dst - mis + 4 w.
 __device__ __forceinline__ void flush_plane(const uint32_t *buf, uint8_t *__restrict__ dst, int n, int tid) {
@@ -54,7 +38,7 @@ __device__ __forceinline__ void flush_plane(const uint32_t *buf, uint8_t *__rest
     const int end = mis + n, nw = (end + 3) >> 2;
     uint8_t *base = dst - mis;
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(buf);
-    for (int w = tid; w < nw; w += kFramesThreads) {
+    for (int w = tid; w < nw; w += kViewThreads) {
         const int lo = 4 * w, hi = lo + 4;
         if (lo >= mis && hi <= end) {
             *reinterpret_cast<uint32_t *>(base + lo) = buf[w];
@@ -65,9 +49,9 @@ __device__ __forceinline__ void flush_plane(const uint32_t *buf, uint8_t *__rest
     }
 }
 
-__global__ void __launch_bounds__(kFramesThreads) frames_views_kernel(
+__global__ void __launch_bounds__(kViewThreads) frames_views_kernel(
     const float *__restrict__ rgb, const float *__restrict__ depth, const float *__restrict__ acc, const float *__restrict__ sem, int64_t P, int C,
-    int tp, int64_t tiles, int vec_ok, const uint8_t *__restrict__ palette, FrameDepth dm, int bgr, uint8_t *__restrict__ rgb8,
+    int tp, int64_t tiles, const uint8_t *__restrict__ palette, FrameDepth dm, int bgr, uint8_t *__restrict__ rgb8,
     uint8_t *__restrict__ dep8, uint8_t *__restrict__ occ8, uint8_t *__restrict__ sem8, uint8_t *__restrict__ labels) {
     extern __shared__ float stage[];                               // [tp][C | 1], only when a label is needed
     __shared__ uint32_t out3[2][kFramesWords3];                    // rgb8, sem8
@@ -82,7 +66,7 @@ __global__ void __launch_bounds__(kFramesThreads) frames_views_kernel(
         const int np = (int)(P - p0 < tp ? P - p0 : tp);
         __syncthreads();                                           // the previous tile's rows are read and its bytes are out
         if (want_label) {
-            stage_rows<kFramesThreads>(stage, sem + i0 * C, np * C, C, Cs, i0 * C, vec_ok, tid);
+            stage_rows(stage, sem + i0 * C, np * C, C, Cs, tid);
             __syncthreads();
         }
         uint8_t *d_rgb = rgb8 ? rgb8 + 3 * i0 : nullptr, *d_sem = sem8 ? sem8 + 3 * i0 : nullptr;
@@ -128,8 +112,6 @@ __global__ void __launch_bounds__(kFramesThreads) frames_views_kernel(
 
 using namespace mnf;
 
-static inline bool finite_d(double x) { return x - x == 0.0; }
-
 extern "C" int mnf_frames_views(const float *rgb, const float *depth, const float *acc, const float *sem, int32_t n_views, int64_t n_pix,
                                 int32_t n_classes, const uint8_t *palette, int32_t palette_entries, double depth_mul, double depth_div,
                                 double depth_clip_hi, double depth_gain, int32_t bgr, uint8_t *rgb8, uint8_t *dep8, uint8_t *occ8, uint8_t *sem8,
@@ -152,23 +134,21 @@ extern "C" int mnf_frames_views(const float *rgb, const float *depth, const floa
     MNF_REQUIRE(!want_label || sem, "frames_views: sem is null");
     MNF_REQUIRE(!want_label || palette, "frames_views: palette is null");
     MNF_REQUIRE(n_views <= 65535, "frames_views: at most 65535 views per call (got %d)", n_views);
-    int tp = kFramesThreads;
+    int tp = kViewThreads;
     if (want_label) {
-        tp = stage_tile_pixels(n_classes, kFramesThreads);
+        tp = stage_tile_pixels(n_classes);
         if (tp < 1) {
             set_error("frames_views: n_classes = %d is more than one LDS tile holds (%d)", n_classes, kStageBytes / 4 - 1);
             return MNF_ERR_UNSUPPORTED;
         }
     }
     if (!rgb8 && !dep8 && !occ8 && !want_label) return MNF_OK;     // every output skipped
-    const int64_t tiles = ceil_div(n_pix, tp);
-    const int nb = (int)(tiles < kFramesMaxBlocksPerView ? tiles : kFramesMaxBlocksPerView);
+    const ViewPlan pl = view_plan(n_pix, tp);
     hipStream_t s = as_stream(stream);
     ProfScope prof("frames_views", s);
-    const int vec_ok = (reinterpret_cast<uintptr_t>(sem) & 15) == 0;
     const size_t lds = want_label ? (size_t)tp * (n_classes | 1) * sizeof(float) : 0;
     const FrameDepth dm = {depth_mul, depth_div, depth_clip_hi, depth_gain};
-    hipLaunchKernelGGL(frames_views_kernel, dim3(nb, n_views), dim3(kFramesThreads), lds, s, rgb, depth, acc, sem, n_pix, n_classes, tp, tiles, vec_ok,
+    hipLaunchKernelGGL(frames_views_kernel, dim3(pl.nb, n_views), dim3(kViewThreads), lds, s, rgb, depth, acc, sem, n_pix, n_classes, tp, pl.tiles,
                        palette, dm, bgr != 0, rgb8, dep8, occ8, sem8, labels);
     return launch_status("frames_views_kernel");
 }

@@ -11,10 +11,8 @@
 //   occ    B(mean_m a_m) - mean_m B(a_m), B(a) = -(a + 1e-4) log(a + 1e-4) - (1 - a + 1e-4) log(1 - a + 1e-4)
 // NaN and inf propagate as they do in numpy.
 //
-// Work split, as ensemble_views_kernel's: a view's pixels are cut into tiles of `tp` pixels, a view's tiles into `nb` contiguous runs, one
-// workgroup per (run, view); tp depends on C only and nb on P and C, so a view's results do not depend on how many views share the call or
-// where it stands.  Member by member a tile's tp * C logits, one contiguous piece of `sem`, are staged in LDS (stage_dev.h), then lane t
-// works on pixel t out of LDS at the odd row stride C | 1.  The ensemble's class probabilities need an accumulator across the members: a row
+// The work split, the logit staging (member by member) and the reduction of the four sums are view_dev.h's.  The ensemble's class
+// probabilities need an accumulator across the members: a row
 // of C | 1 doubles per pixel in LDS next to the stage, which only the lane that owns the pixel touches (plain read-modify-writes, no
 // barrier of its own; an odd stride in 8-byte units puts the 32 lanes of a ds_read_b64 group on 32 different bank pairs).  No array is
 // sized by C or M per lane, so nothing spills to scratch and the same kernel serves 64 members and 1024 classes.  Stage and accumulator
@@ -27,55 +25,27 @@
 //
 // Outputs.  maps: the lane's four doubles are 32 contiguous bytes, stored as two 16-byte stores when the base is 16-byte aligned and as
 // four 8-byte stores otherwise.  heat8: sat8(((x - lo_k) / (hi_k - lo_k)) * 255.0), every operation rounded on its own (this file is
-// compiled with -ffp-contract=off), sat8 as in frames.hip; a pixel's four bytes go out as one aligned 32-bit store.  terms: sums are
-// carried per lane over its pixels, then a shuffle tree per wave, then the four waves in order, then ONE row of four partial sums per
-// workgroup in the caller's workspace; infomap_finish_kernel adds a view's rows in a fixed order and divides.  No atomic anywhere: the same
-// inputs give the same bits.
-#include "common.h"
-#include "stage_dev.h"
+// compiled with -ffp-contract=off), sat8 as in frames.hip; a pixel's four bytes go out as one aligned 32-bit store.  terms:
+// infomap_finish_kernel divides a view's sums.
+#include "view_dev.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kMapThreads = 256;
-constexpr int kMapMaxBlocksPerView = 512;      // depends on P and C only
 constexpr int kMapLdsBytes = 65536 - 256;      // stage + accumulator; the rest of 64 KB is left to the reduction's static scratch
+constexpr int kMapEntryBytes = 12;             // per class entry: a float of the stage and a double of the accumulator; a tile of >= 4 pixels for C <= 1024
 constexpr int kMapTerms = 4;                   // rgb, depth, semantic, occupancy: mnf_score_views' column order
 
-struct MapPlan { int tp; int64_t tiles; int nb; };
 struct HeatRange { double lo[kMapTerms], hi[kMapTerms]; };
 
-inline void map_plan(int64_t n_pix, int32_t C, MapPlan *pl) {
-    const int64_t cs = C | 1;
-    int64_t tp = kMapLdsBytes / (cs * 12);        // a float row of the stage and a double row of the accumulator; >= 5 for C <= 1024
-    if (tp > kMapThreads) tp = kMapThreads;
-    if (tp >= 4) tp &= ~(int64_t)3;               // stage_dev.h: tiles of a multiple of four pixels keep an aligned view's tiles 16-byte aligned
-    pl->tp = (int)tp;
-    pl->tiles = ceil_div(n_pix, tp);
-    pl->nb = (int)(pl->tiles < kMapMaxBlocksPerView ? pl->tiles : kMapMaxBlocksPerView);
-}
-
-__device__ __forceinline__ double map_wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
-// frames.hip's narrowing: clamp to [0, 255], round to nearest even, NaN -> 0
-__device__ __forceinline__ uint32_t map_sat8(double y) {
-    if (!(y > 0.0)) return 0;
-    if (y >= 255.0) return 255;
-    return (uint32_t)(int)rint(y);
-}
 
 __device__ __forceinline__ double binary_entropy(double a) { return -(a + 1e-4) * log(a + 1e-4) - (1.0 - a + 1e-4) * log(1.0 - a + 1e-4); }
 
-__global__ void __launch_bounds__(kMapThreads) infomap_views_kernel(
+__global__ void __launch_bounds__(kViewThreads) infomap_views_kernel(
     const float *__restrict__ rgb_var, const float *__restrict__ depth_var, const float *__restrict__ acc, const float *__restrict__ sem, int M,
-    int V, int64_t P, int C, int tp, int64_t tiles, int vec_ok, int maps16, HeatRange hr, double *__restrict__ partials,
+    int V, int64_t P, int C, int tp, int64_t tiles, int maps16, HeatRange hr, double *__restrict__ partials,
     double *__restrict__ maps, uint32_t *__restrict__ heat) {
     extern __shared__ double lds[];                                  // p_ens [tp][C | 1] f64, then stage [tp][C | 1] f32
-    __shared__ double red[kMapThreads / 64][kMapTerms];
     const int tid = threadIdx.x, v = blockIdx.y, nb = gridDim.x, b = blockIdx.x;
     const int Cs = C | 1;
     double *p_ens = lds + (int64_t)tid * Cs;                         // this lane's row; lanes >= tp never touch it
@@ -94,9 +64,8 @@ __global__ void __launch_bounds__(kMapThreads) infomap_views_kernel(
         if (own)
             for (int k = 0; k < C; ++k) p_ens[k] = 0.0;
         for (int m = 0; m < M; ++m) {
-            const int64_t e0 = (((int64_t)m * V + v) * P + p0) * C;
             __syncthreads();                                         // the previous piece's rows are read
-            stage_rows<kMapThreads>(stage, sem + e0, np * C, C, Cs, e0, vec_ok, tid);
+            stage_rows(stage, sem + (((int64_t)m * V + v) * P + p0) * C, np * C, C, Cs, tid);
             __syncthreads();
             if (own) {
                 const int64_t im = i + (int64_t)m * VP;
@@ -155,39 +124,21 @@ __global__ void __launch_bounds__(kMapThreads) infomap_views_kernel(
             if (heat) {
                 uint32_t w = 0;
 #pragma unroll
-                for (int k = 0; k < kMapTerms; ++k) w |= map_sat8(((px[k] - hr.lo[k]) / (hr.hi[k] - hr.lo[k])) * 255.0) << (8 * k);
+                for (int k = 0; k < kMapTerms; ++k) w |= (uint32_t)sat8(((px[k] - hr.lo[k]) / (hr.hi[k] - hr.lo[k])) * 255.0) << (8 * k);
                 heat[i] = w;
             }
         }
     }
     if (!partials) return;                                           // the same for every lane of the grid
     const double part[kMapTerms] = {s_rgb, s_dep, s_sem, s_occ};
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < kMapTerms; ++k) {
-        const double w = map_wave_sum(part[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-    __syncthreads();
-    if (tid < kMapTerms) {
-        double s = red[0][tid];
-        for (int w = 1; w < kMapThreads / 64; ++w) s += red[w][tid];
-        partials[((int64_t)v * nb + b) * kMapTerms + tid] = s;
-    }
+    store_partials(part, partials, v, nb, b, tid);
 }
 
-// one wave per view: lane l adds rows l, l + 64, ... in order, then the shuffle tree; the means of pipeline.py:735 / :746 / :760 / :773
+// one wave per view; the means of pipeline.py:735 / :746 / :760 / :773
 __global__ void __launch_bounds__(64) infomap_finish_kernel(const double *__restrict__ partials, int nb, int64_t P, double *__restrict__ terms) {
     const int v = blockIdx.x, lane = threadIdx.x;
     double s[kMapTerms];
-#pragma unroll
-    for (int k = 0; k < kMapTerms; ++k) s[k] = 0.0;
-    for (int b = lane; b < nb; b += 64) {
-#pragma unroll
-        for (int k = 0; k < kMapTerms; ++k) s[k] += partials[((int64_t)v * nb + b) * kMapTerms + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kMapTerms; ++k) s[k] = map_wave_sum(s[k]);
+    sum_partials(partials, v, nb, lane, s);
     if (lane == 0) {
         double *t = terms + (int64_t)v * 4;
         t[0] = s[0] / (3.0 * (double)P);
@@ -201,8 +152,6 @@ inline bool map_sizes_ok(int32_t n_views, int64_t n_pix, int32_t n_classes) {
     return n_views >= 0 && n_pix > 0 && n_classes > 0 && n_classes <= MNF_SCORE_MAPS_MAX_CLASSES;
 }
 
-inline bool finite_d(double x) { return x - x == 0.0; }
-
 }  // namespace
 }  // namespace mnf
 
@@ -210,9 +159,7 @@ using namespace mnf;
 
 extern "C" int64_t mnf_score_view_maps_workspace_bytes(int32_t n_views, int64_t n_pix, int32_t n_classes) {
     if (!map_sizes_ok(n_views, n_pix, n_classes)) return 0;
-    MapPlan pl;
-    map_plan(n_pix, n_classes, &pl);
-    return (int64_t)n_views * pl.nb * kMapTerms * (int64_t)sizeof(double);
+    return view_partials_bytes(n_views, view_plan(n_pix, stage_tile_pixels(n_classes, kMapEntryBytes, kMapLdsBytes)).nb, kMapTerms);
 }
 
 extern "C" int mnf_score_view_maps(const float *rgb_var, const float *depth_var, const float *acc, const float *sem, int32_t n_members,
@@ -247,21 +194,19 @@ extern "C" int mnf_score_view_maps(const float *rgb_var, const float *depth_var,
     MNF_REQUIRE((reinterpret_cast<uintptr_t>(heat8) & 3) == 0, "score_view_maps: heat8 must be 4-byte aligned");
     MNF_REQUIRE((reinterpret_cast<uintptr_t>(terms) & 7) == 0, "score_view_maps: terms must be 8-byte aligned");
     MNF_REQUIRE(n_views <= 65535, "score_view_maps: at most 65535 views per call (got %d)", n_views);
-    MapPlan pl;
-    map_plan(n_pix, n_classes, &pl);
+    const ViewPlan pl = view_plan(n_pix, stage_tile_pixels(n_classes, kMapEntryBytes, kMapLdsBytes));
     if (terms) {                                                     // the partial sums exist for the per-view means only
-        const int64_t need = (int64_t)n_views * pl.nb * kMapTerms * (int64_t)sizeof(double);
+        const int64_t need = view_partials_bytes(n_views, pl.nb, kMapTerms);
         MNF_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "score_view_maps: terms needs an 8-byte aligned workspace");
         MNF_REQUIRE(workspace_bytes >= need, "score_view_maps: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     }
     hipStream_t s = as_stream(stream);
     ProfScope prof("score_view_maps", s);
-    const size_t lds = (size_t)pl.tp * (n_classes | 1) * 12;
-    const int vec_ok = (reinterpret_cast<uintptr_t>(sem) & 15) == 0;
+    const size_t lds = (size_t)pl.tp * (n_classes | 1) * kMapEntryBytes;
     const int maps16 = (reinterpret_cast<uintptr_t>(maps) & 15) == 0;
     double *partials = terms ? reinterpret_cast<double *>(workspace) : nullptr;
-    hipLaunchKernelGGL(infomap_views_kernel, dim3(pl.nb, n_views), dim3(kMapThreads), lds, s, rgb_var, depth_var, acc, sem, n_members, n_views, n_pix,
-                       n_classes, pl.tp, pl.tiles, vec_ok, maps16, hr, partials, maps, reinterpret_cast<uint32_t *>(heat8));
+    hipLaunchKernelGGL(infomap_views_kernel, dim3(pl.nb, n_views), dim3(kViewThreads), lds, s, rgb_var, depth_var, acc, sem, n_members, n_views, n_pix,
+                       n_classes, pl.tp, pl.tiles, maps16, hr, partials, maps, reinterpret_cast<uint32_t *>(heat8));
     int rc = launch_status("infomap_views_kernel");
     if (rc || !terms) return rc;
     hipLaunchKernelGGL(infomap_finish_kernel, dim3(n_views), dim3(64), 0, s, partials, pl.nb, n_pix, terms);

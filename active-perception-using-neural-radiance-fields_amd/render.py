@@ -1200,6 +1200,60 @@ def trajectory_score(terms: torch.Tensor) -> torch.Tensor:
 
 
 LAST_SCORE_TOTALS = []
+_PROB_PLANES = (("rgb_var", (3,)), ("depth_var", ()), ("acc", ()), ("sem", (-1,)))      # name, trailing shape: what `score_view_terms` takes
+_PLAIN_PLANES = (("rgb", (3,)), ("depth", ()), ("acc", ()))                             # `ensemble_view_terms`' (its sem is member 0's)
+
+
+def _render_members(radiance_fields, estimators, o, d, P, planes, **opts):
+    """The rays `o`, `d` (views of P pixels) rendered by every ensemble member with the scorers' fixed options and the caller's `opts`
+    (near_plane, render_step_size, cone_angle, alpha_thre, probabilistic).  Returns (the member-major stacks [M,n,P,...] of `planes`, the
+    members' render outputs)."""
+    # every ensemble member renders the same rays: the members advance side by side as render jobs of one call (four jobs in
+    # flight — the caller's stream + the library's three shared side streams — is the measured optimum for these small views,
+    # profiles/r03_hw_queues.txt: two members are cut into two groups of views each, one member into four; rays stay in row-major
+    # march order — the 8x8-block order of full images buys nothing on 64x64 sub-sampled views: profiles/r03_split_experiment.txt)
+    M, n = len(radiance_fields), o.shape[0] // P
+    outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], P, max_samples=1024, far_plane=1e10, render_bkgd=torch.zeros(3),
+                        early_stop_eps=1e-4, n_split=max(1, 4 // M), **opts)
+    return [torch.stack([r[k].reshape(n, P, *tail) for r in outs]) for k, tail in planes], outs
+
+
+def _score_one_call(entry, workspace_bytes, radiance_fields, estimators, poses, width, height, focal, scale, device, **opts):
+    """ONE C call `entry` (csrc/trainstep.hip: mnf_score_poses, mnf_score_trajectory; `workspace_bytes` its size entry): poses -> the sub-sampled
+    rays of every view -> renders by every ensemble member with `opts` (near_plane, render_step_size, cone_angle, alpha_thre, probabilistic)
+    -> per-view terms [V,4] float64."""
+    V, M = poses.shape[0], len(radiance_fields)
+    c2w = torch.from_numpy(np.stack([pose_to_c2w(np.asarray(p, np.float64)) for p in poses]).astype(np.float32)[:, :3, :4].copy()).to(device)
+    h, w = int(height * scale), int(width * scale)
+    idx = torch.from_numpy(subsample_indices(width * height, h * w)).to(device)
+    handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in radiance_fields])
+    grids = [_grid_args(e) for e in estimators]
+    bins = (ctypes.c_void_p * M)(*[g.binaries.data_ptr() for g in grids])
+    bits = (ctypes.c_void_p * M)(*[g.bits.data_ptr() for g in grids])
+    ropts = _render_opts(max_samples=1024, far_plane=1e10, early_stop_eps=1e-4, rays_per_view=h * w, n_levels=grids[0].n_levels, **opts)   # row-major march order, as `score_views`
+    nbytes = int(workspace_bytes(M, V, h * w, radiance_fields[0].num_semantic_classes))
+    ws = _workspace(torch.device(device), nbytes)
+    terms = torch.empty(V, 4, dtype=torch.float64, device=device)
+    L.launch(entry, handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, width,
+             height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(ropts), L.ptr(terms), L.ptr(ws), nbytes)
+    return terms
+
+
+def _check_view_planes(sem, V, planes, M=None):
+    """The pixels per view P of the logits `sem`, [..., C] holding V views or (with `M`) [S,V,P,C], after checking that every (name, tensor, k)
+    of `planes` holds V views (of each of M members) of P pixels of k floats; with `M` the first plane is [M,V,P,3] exactly."""
+    C = int(sem.shape[-1])
+    if M is None:
+        if V == 0 or sem.numel() % (V * C):
+            raise ValueError(f"sem of shape {tuple(sem.shape)} does not hold {V} views of {C}-class pixels")
+        P = sem.numel() // (V * C)
+    else:
+        P = int(sem.shape[2])
+    n = V * P * (1 if M is None else M)
+    if any(t.numel() != n * k for _, t, k in planes) or (M is not None and tuple(planes[0][1].shape) != (M, V, P, 3)):
+        raise ValueError(" / ".join(f"{name} {tuple(t.shape)}" for name, t, _ in planes) + " do not match "
+                         + (f"{M} members of " if M is not None else "") + f"{V} views of {P} pixels")
+    return P
 
 
 @torch.no_grad()
@@ -1219,20 +1273,10 @@ def score_views(radiance_fields, estimators, poses, width, height, focal, near_p
     terms_local = torch.zeros(per, 4, dtype=torch.float64, device=device)
     if hi > lo:
         o, d, h, w = _pose_rays(poses[lo:hi], width, height, focal, scale, device)
-        n = hi - lo
-        # every ensemble member renders the same rays: the members advance side by side as render jobs of one call (four jobs in
-        # flight — the caller's stream + the library's three shared side streams — is the measured optimum for these small views,
-        # profiles/r03_hw_queues.txt: two members are cut into two groups of views each, one member into four; rays stay in row-major
-        # march order — the 8x8-block order of full images buys nothing on 64x64 sub-sampled views: profiles/r03_split_experiment.txt)
-        M = len(radiance_fields)
-        outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], h * w, max_samples=1024, near_plane=near_plane, far_plane=1e10,
-                            render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=1e-4,
-                            probabilistic=True, n_split=max(1, 4 // M))
-        totals = [r["total"] for r in outs]
-        rv = [r["rgb_var"].reshape(n, h * w, 3) for r in outs]; dv = [r["depth_var"].reshape(n, h * w) for r in outs]
-        ac = [r["acc"].reshape(n, h * w) for r in outs]; sm = [r["sem"].reshape(n, h * w, -1) for r in outs]
-        terms_local[:n] = score_view_terms(torch.stack(rv), torch.stack(dv), torch.stack(ac), torch.stack(sm))
-        LAST_SCORE_TOTALS[:] = totals           # per member: device int64 [kept, evaluated] samples of this rank's views (measurement aid)
+        stacks, outs = _render_members(radiance_fields, estimators, o, d, h * w, _PROB_PLANES, near_plane=near_plane, render_step_size=render_step_size,
+                                       cone_angle=cone_angle, alpha_thre=alpha_thre, probabilistic=True)
+        terms_local[:hi - lo] = score_view_terms(*stacks)
+        LAST_SCORE_TOTALS[:] = [r["total"] for r in outs]       # per member: device int64 [kept, evaluated] samples of this rank's views (measurement aid)
     terms = terms_local[:V] if group is False else gather_view_terms(terms_local, V, group)
     return terms, trajectory_score(terms)
 
@@ -1243,23 +1287,8 @@ def score_poses(radiance_fields, estimators, poses, width, height, focal, near_p
     """`score_views` on one rank as ONE C call (`mnf_score_poses`, csrc/trainstep.hip): poses -> the sub-sampled rays of every
     view -> probabilistic renders by every ensemble member -> per-view terms.  Returns (terms [V,4] float64, score)."""
     lib = L.load_library()
-    poses = np.asarray(poses)
-    V, M = poses.shape[0], len(radiance_fields)
-    c2w = torch.from_numpy(np.stack([pose_to_c2w(np.asarray(p, np.float64)) for p in poses]).astype(np.float32)[:, :3, :4].copy()).to(device)
-    h, w = int(height * scale), int(width * scale)
-    idx = torch.from_numpy(subsample_indices(width * height, h * w)).to(device)
-    handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in radiance_fields])
-    grids = [_grid_args(e) for e in estimators]
-    bins = (ctypes.c_void_p * M)(*[g.binaries.data_ptr() for g in grids])
-    bits = (ctypes.c_void_p * M)(*[g.bits.data_ptr() for g in grids])
-    opts = _render_opts(max_samples=1024, near_plane=near_plane, far_plane=1e10, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,
-                        early_stop_eps=1e-4, probabilistic=True, rays_per_view=h * w, n_levels=grids[0].n_levels)      # row-major march order, as `score_views`
-    C = radiance_fields[0].num_semantic_classes
-    nbytes = int(lib.mnf_score_poses_workspace_bytes(M, V, h * w, C))
-    ws = _workspace(torch.device(device), nbytes)
-    terms = torch.empty(V, 4, dtype=torch.float64, device=device)
-    L.launch(lib.mnf_score_poses, handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, width,
-             height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(opts), L.ptr(terms), L.ptr(ws), nbytes)
+    terms = _score_one_call(lib.mnf_score_poses, lib.mnf_score_poses_workspace_bytes, radiance_fields, estimators, np.asarray(poses), width, height, focal, scale, device,
+                            near_plane=near_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre, probabilistic=True)
     return terms, trajectory_score(terms)
 
 
@@ -1304,9 +1333,7 @@ def view_information_maps(rgb_var, depth_var, acc, sem, *, maps=True, heat_range
     if sem.dim() != 4 or rgb_var.dim() != 4 or rgb_var.shape[-1] != 3:
         raise ValueError(f"view_information_maps takes rgb_var [M,V,P,3] and sem [M,V,P,C] (got {tuple(rgb_var.shape)}, {tuple(sem.shape)})")
     M, V, P, C = (int(x) for x in sem.shape)
-    if tuple(rgb_var.shape) != (M, V, P, 3) or depth_var.numel() != M * V * P or acc.numel() != M * V * P:
-        raise ValueError(f"rgb_var {tuple(rgb_var.shape)} / depth_var {tuple(depth_var.shape)} / acc {tuple(acc.shape)} do not match {M} members of {V} views "
-                         f"of {P} pixels")
+    _check_view_planes(sem, V, (("rgb_var", rgb_var, 3), ("depth_var", depth_var, 1), ("acc", acc, 1)), M)
     if min(M, P, C) < 1:
         raise ValueError(f"view_information_maps needs at least one member, pixel and class (got M = {M}, P = {P}, C = {C})")
     if M > SCORE_MAPS_MAX_MEMBERS or C > SCORE_MAPS_MAX_CLASSES:
@@ -1344,12 +1371,9 @@ def score_view_maps(radiance_fields, estimators, poses, width, height, focal, ne
     for g0 in range(0, N, per):
         o, d, _, _ = _pose_rays(poses[g0:g0 + per], width, height, focal, scale, device)
         n = o.shape[0] // P
-        outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], P, max_samples=1024, near_plane=near_plane, far_plane=1e10,
-                            render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, early_stop_eps=1e-4,
-                            probabilistic=True, n_split=max(1, 4 // M))
-        rv = torch.stack([r["rgb_var"].reshape(n, P, 3) for r in outs]); dv = torch.stack([r["depth_var"].reshape(n, P) for r in outs])
-        ac = torch.stack([r["acc"].reshape(n, P) for r in outs]); sm = torch.stack([r["sem"].reshape(n, P, -1) for r in outs])
-        _view_maps_into(*(L.contig(t, torch.float32) for t in (rv, dv, ac, sm)), M, n, P, C, terms[g0:g0 + n], maps[g0:g0 + n],
+        stacks, _ = _render_members(radiance_fields, estimators, o, d, P, _PROB_PLANES, near_plane=near_plane, render_step_size=render_step_size,
+                                    cone_angle=cone_angle, alpha_thre=alpha_thre, probabilistic=True)
+        _view_maps_into(*(L.contig(t, torch.float32) for t in stacks), M, n, P, C, terms[g0:g0 + n], maps[g0:g0 + n],
                         heat[g0:g0 + n] if heat is not None else None, lo, hi)
     return dict(terms=terms, score=trajectory_score(terms), maps=maps.view(N, h, w, 4), heat=heat.view(N, h, w, 4) if heat is not None else None)
 
@@ -1373,8 +1397,7 @@ def ensemble_view_terms(rgb, depth, acc, sem):
         raise ValueError(f"ensemble_view_terms takes rgb [M,V,P,3] and sem [S,V,P,C] or [V,P,C] (got {tuple(rgb.shape)}, {tuple(sem.shape)})")
     S, V, P, C = (int(x) for x in sem.shape)
     M = int(rgb.shape[0])
-    if tuple(rgb.shape) != (M, V, P, 3) or depth.numel() != M * V * P or acc.numel() != M * V * P:
-        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} / acc {tuple(acc.shape)} do not match {M} members of {V} views of {P} pixels")
+    _check_view_planes(sem, V, (("rgb", rgb, 3), ("depth", depth, 1), ("acc", acc, 1)), M)
     lib = L.load_library()
     r, d, a, s = (L.contig(t, torch.float32) for t in (rgb, depth, acc, sem))
     terms = torch.empty(V, 4, dtype=torch.float64, device=sem.device)
@@ -1415,38 +1438,22 @@ def trajectory_uncertainty(radiance_fields, estimators, trajectory, step, width,
     import torch.distributed as dist
     trajectory = np.asarray(trajectory)
     poses = trajectory[trajectory_view_indices(len(trajectory))]
-    V, M = poses.shape[0], len(radiance_fields)
+    V = poses.shape[0]
     world, rank = 1, 0
     if group is not False and dist.is_available() and dist.is_initialized():
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     if one_call and world == 1:
         lib = L.load_library()
-        c2w = torch.from_numpy(np.stack([pose_to_c2w(np.asarray(p, np.float64)) for p in poses]).astype(np.float32)[:, :3, :4].copy()).to(device)
-        h, w = int(height * scale), int(width * scale)
-        idx = torch.from_numpy(subsample_indices(width * height, h * w)).to(device)
-        handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in radiance_fields])
-        grids = [_grid_args(e) for e in estimators]
-        bins = (ctypes.c_void_p * M)(*[g.binaries.data_ptr() for g in grids])
-        bits = (ctypes.c_void_p * M)(*[g.bits.data_ptr() for g in grids])
-        opts = _render_opts(max_samples=1024, near_plane=near_plane, far_plane=1e10, render_step_size=render_step_size, cone_angle=cone_angle,
-                            alpha_thre=alpha_thre, early_stop_eps=1e-4, probabilistic=False, rays_per_view=h * w, n_levels=grids[0].n_levels)
-        C = radiance_fields[0].num_semantic_classes
-        nbytes = int(lib.mnf_score_trajectory_workspace_bytes(M, V, h * w, C))
-        ws = _workspace(torch.device(device), nbytes)
-        terms = torch.empty(V, 4, dtype=torch.float64, device=device)
-        L.launch(lib.mnf_score_trajectory, handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, width,
-                 height, float(np.float32(focal)), L.ptr(idx), h * w, ctypes.byref(opts), L.ptr(terms), L.ptr(ws), nbytes)
+        terms = _score_one_call(lib.mnf_score_trajectory, lib.mnf_score_trajectory_workspace_bytes, radiance_fields, estimators, poses, width, height, focal, scale,
+                                device, near_plane=near_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre, probabilistic=False)
     else:
         lo, hi, per = shard_views(V, world, rank)
         terms_local = torch.zeros(per, 4, dtype=torch.float64, device=device)
         if hi > lo:
             o, d, h, w = _pose_rays(poses[lo:hi], width, height, focal, scale, device)
-            n = hi - lo
-            outs = _render_jobs([(rf, est, o, d) for rf, est in zip(radiance_fields, estimators)], h * w, max_samples=1024, near_plane=near_plane,
-                                far_plane=1e10, render_step_size=render_step_size, render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre,
-                                early_stop_eps=1e-4, probabilistic=False, n_split=max(1, 4 // M))
-            terms_local[:n] = ensemble_view_terms(torch.stack([r["rgb"].reshape(n, h * w, 3) for r in outs]), torch.stack([r["depth"].reshape(n, h * w) for r in outs]),
-                                                  torch.stack([r["acc"].reshape(n, h * w) for r in outs]), outs[0]["sem"].reshape(n, h * w, -1))
+            stacks, outs = _render_members(radiance_fields, estimators, o, d, h * w, _PLAIN_PLANES, near_plane=near_plane,
+                                           render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre, probabilistic=False)
+            terms_local[:hi - lo] = ensemble_view_terms(*stacks, outs[0]["sem"].reshape(hi - lo, h * w, -1))
         terms = terms_local[:V] if world == 1 else gather_view_terms(terms_local, V, group)
     rows = np.ascontiguousarray(terms.cpu().numpy().T)            # the one device-to-host copy
     uncertainty, max_idx = trajectory_uncertainty_from_terms(rows.T, step)
@@ -1497,11 +1504,7 @@ def eval_metrics(rgb, depth, sem, dataset, image_ids, pix_idx=None, confusion=Tr
     ids = _eval_index_tensor(image_ids, dev, len(dataset), "image_ids")
     V = int(ids.shape[0])
     ppi = int(dataset.height) * int(dataset.width)
-    if V == 0 or sem.numel() % (V * C):
-        raise ValueError(f"sem of shape {tuple(sem.shape)} does not hold {V} views of {C}-class pixels")
-    P = sem.numel() // (V * C)
-    if rgb.numel() != V * P * 3 or depth.numel() != V * P:
-        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} do not match {V} views of {P} pixels")
+    P = _check_view_planes(sem, V, (("rgb", rgb, 3), ("depth", depth, 1)))
     pix = None
     if pix_idx is not None:
         pix = _eval_index_tensor(pix_idx, dev, ppi, "pix_idx")
@@ -1619,13 +1622,8 @@ def _frame_args(depth_map, channel_order, labels, n_classes):
 def _frames_into(rgb, depth, acc, sem, pal, dm, bgr, out):
     """`mnf_frames_views` (csrc/frames.hip) on V views of P pixels into the contiguous uint8 tensors of `out` (keys of _FRAME_PLANES; no
     "labels" key: no label plane)."""
-    C = int(sem.shape[-1])
-    V = int(sem.shape[0])
-    if V == 0 or sem.numel() % (V * C):
-        raise ValueError(f"sem of shape {tuple(sem.shape)} does not hold {V} views of {C}-class pixels")
-    P = sem.numel() // (V * C)
-    if rgb.numel() != V * P * 3 or depth.numel() != V * P or acc.numel() != V * P:
-        raise ValueError(f"rgb {tuple(rgb.shape)} / depth {tuple(depth.shape)} / acc {tuple(acc.shape)} do not match {V} views of {P} pixels")
+    V, C = int(sem.shape[0]), int(sem.shape[-1])
+    P = _check_view_planes(sem, V, (("rgb", rgb, 3), ("depth", depth, 1), ("acc", acc, 1)))
     for name, k in _FRAME_PLANES:
         if name in out and (out[name].dtype != torch.uint8 or out[name].numel() != V * P * k or not out[name].is_contiguous()):
             raise ValueError(f"output plane {name} does not hold {V} x {P} x {k} contiguous bytes")

@@ -249,6 +249,30 @@ def test_two_runs_are_bitwise_equal(large):
     assert torch.equal(alone["metrics"].view(torch.int64)[0], a["metrics"].view(torch.int64)[1])
 
 
+@pytest.mark.parametrize("V,P,Cn", [(3, 301, 29),      # unpadded LDS rows, two tiles per view, odd view starts
+                                    (2, 63, 64)])       # padded rows (row stride C | 1 != C), one short tile
+def test_inputs_off_the_16_byte_grid(small, V, P, Cn):
+    """rgb, depth and sem starting 1, 2 and 3 floats into larger allocations (contiguous views of a flat buffer, which `eval_metrics` passes
+    through as they are: the staging takes a scalar head up to the first 16-byte boundary of the address) give the bits of the same values in
+    tensors of their own."""
+    from apnrf_amd import render as RD
+    ds = small["plain"]
+    g = torch.Generator().manual_seed(100 + Cn)
+    own = [torch.rand(V, P, 3, generator=g).to(DEV), (torch.rand(V, P, generator=g) * 6.0).to(DEV), (torch.randn(V, P, Cn, generator=g) * 3.0).to(DEV)]
+    shifted = []
+    for off, t in zip((1, 2, 3), own):
+        flat = torch.empty(t.numel() + 8, device=DEV)
+        view = flat[off:off + t.numel()].view(t.shape)
+        view.copy_(t)
+        assert view.is_contiguous() and t.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * off
+        shifted.append(view)
+    want = RD.eval_metrics(*own, ds, list(range(V)), labels=True)
+    got = RD.eval_metrics(*shifted, ds, list(range(V)), labels=True)
+    assert np.isfinite(want["metrics"].cpu().numpy()).all() and want["confusion"].sum().item() == V * P
+    assert torch.equal(got["metrics"].view(torch.int64), want["metrics"].view(torch.int64))
+    assert torch.equal(got["confusion"], want["confusion"]) and torch.equal(got["pred_labels"], want["pred_labels"])
+
+
 def test_evaluate_views_end_to_end(model, small):
     from apnrf_amd import render as RD
     field, est = model

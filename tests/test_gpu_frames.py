@@ -120,7 +120,7 @@ def _dev_ptr(addr):
 
 @pytest.mark.parametrize("off", [1, 2, 3])
 def test_unaligned_inputs_and_guarded_outputs(off):
-    """The raw entry point: `sem` 4 bytes into its allocation (no 16-byte loads: the scalar staging path), rgb / depth / acc 4 bytes in as
+    """The raw entry point: `sem` 4 bytes into its allocation (a scalar head of three floats, then 16-byte loads, then a scalar tail), rgb / depth / acc 4 bytes in as
     well, every output `off` bytes into a buffer pre-filled with 0xA5.  Results equal the restatement and no guard byte changes."""
     from apnrf_amd import _lib as L
     lib = L.load_library()

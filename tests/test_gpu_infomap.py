@@ -226,7 +226,7 @@ def _raw(stacks, in_off=0, maps_off=0, heat_off=0, want=("terms", "maps", "heat"
 
 @pytest.mark.parametrize("off", [0, 1, 2, 3])
 def test_unaligned_inputs_and_guarded_outputs(off):
-    """Inputs 0 - 3 floats into their allocations (the scalar staging path from 1 on), maps 8 bytes off the 16-byte grid for odd offsets
+    """Inputs 0 - 3 floats into their allocations (a scalar head up to the first 16-byte boundary, 16-byte loads, a scalar tail, from 1 on), maps 8 bytes off the 16-byte grid for odd offsets
     (four 8-byte stores), heat 4 bytes times the offset past its pad: the bits of the aligned call, and no guard byte changes."""
     for shape in [(2, 2, 257, 29), (3, 2, 300, 32)]:              # odd and even class counts: plain and padded LDS rows
         stacks, _ = case(shape)

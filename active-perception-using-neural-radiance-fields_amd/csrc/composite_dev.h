@@ -137,6 +137,9 @@ __device__ __forceinline__ float quad_reduce_scatter(float x0, float x1, float x
 struct WaveCounters {
     int view = -1, alive = 0;
     float kept = 0.f, marched = 0.f;
+#ifdef MNF_DIAG
+    int dead_tiles = 0, live_rays = 0, idle_rays = 0;   // MNF_ROUND_LOG: tiles without a kept sample; rays of the other tiles, and those of them without a kept sample
+#endif
 };
 
 __device__ __forceinline__ void flush_alive(const FusedRender &fr, WaveCounters &wc, int lane) {
@@ -149,6 +152,13 @@ __device__ __forceinline__ void flush_counters(const FusedRender &fr, WaveCounte
     if (lane == 0) {
         if (wc.kept > 0.f) atomicAdd(fr.totals, (unsigned long long)(wc.kept + 0.5f));
         if (wc.marched > 0.f) atomicAdd(fr.totals + 1, (unsigned long long)(wc.marched + 0.5f));
+#ifdef MNF_DIAG
+        if (fr.diag_counts) {
+            if (wc.dead_tiles) atomicAdd(fr.diag_counts, (uint32_t)wc.dead_tiles);
+            if (wc.live_rays) atomicAdd(fr.diag_counts + 1, (uint32_t)wc.live_rays);
+            if (wc.idle_rays) atomicAdd(fr.diag_counts + 2, (uint32_t)wc.idle_rays);
+        }
+#endif
     }
     wc.kept = 0.f; wc.marched = 0.f;
 }
@@ -161,6 +171,22 @@ struct TileSample {     // this lane's sample (lane = sample)
     float ts, te;
     float opac0;        // opacity of the ray before this round (prefetched)
 };
+
+// What decides whether this lane's sample counts at all (utils.py:712-725: samples with alpha < alpha_thre are dropped before any accumulation).  It needs the density
+// only, so the field kernel decides ONCE, right behind the base MLP, and hands the wave's ballot on: the tile's decision there (no bit set: no heads, no compositing)
+// and the compositing below read the same mask and can never disagree about a sample.  Carried as sigma * dt (in place of sigma: no extra register across the heads)
+// and the mask (a scalar pair); carrying alpha and a per-lane flag instead cost the live tiles 1 %.
+struct SampleKeep {
+    float sdt;                  // sigma * dt (0 for an unused column)
+    unsigned long long kept;    // the wave's ballot of `keep`: bit l = lane l's sample counts
+};
+__device__ __forceinline__ SampleKeep sample_keep(float alpha_thre, const TileSample &sm, float sigma) {
+    SampleKeep k;
+    k.sdt = sm.valid ? sigma * (sm.te - sm.ts) : 0.0f;
+    const float alpha = 1.0f - expf(-k.sdt);
+    k.kept = __ballot(sm.valid && !(alpha_thre > 0.f && !(alpha >= alpha_thre)));   // utils.py:714-725
+    return k;
+}
 
 // ---- per-ray bookkeeping by the owner lane (both compositing paths) ----
 __device__ __forceinline__ void finish_rays(const FusedRender &fr, int lane, const TileSample &sm, WaveCounters &wc, bool owner, int view,
@@ -187,11 +213,36 @@ __device__ __forceinline__ void finish_rays(const FusedRender &fr, int lane, con
     }
 }
 
+// A tile in which no sample is kept (every wk of the compositing below would be 0): all it owes is the retirement of its rays and the wave's counters, by the owner
+// lane of every run, from the run structure alone.  The ray's sums would all have grown by exact zeros (o_new = opac0), so no accumulator is read or written; works
+// for every slot form (it looks at ray ids, valid, opac0, stride and view only).
+__device__ __forceinline__ void dead_tile_rays(const FusedRender &fr, int lane, const TileSample &sm, WaveCounters &wc) {
+    const int prev_ray = __shfl_up(sm.ray, 1, 64);
+    const bool head = lane == 0 || prev_ray != sm.ray || sm.ray < 0;
+    const unsigned long long heads = __ballot(head);
+    const bool owner = sm.ray >= 0 && head;
+    const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
+    const int cnt = above ? __ffsll(above) : 64 - lane;                    // length of the run that starts here: its valid columns
+    bool still_alive = false;
+    if (owner) {
+        still_alive = (sm.opac0 <= fr.opc_thre) && (cnt == sm.stride);     // utils.py:751-756 with o_new = opac0
+        fr.alive[sm.ray] = still_alive;
+    }
+    if (__ballot(owner)) {
+        if (wc.view != sm.view) { flush_alive(fr, wc, lane); wc.view = sm.view; }
+        wc.alive += __popcll(__ballot(still_alive));
+        wc.marched += (float)__popcll(__ballot(sm.valid));
+    }
+#ifdef MNF_DIAG
+    wc.dead_tiles += 1;
+#endif
+}
+
 // Compositing of a tile whose slots are aligned runs of 4, 8 or 16 columns (see slot_totals): same arithmetic per sample as
 // the general path below, the per-ray sums as butterflies, and the 29 semantic sums reduce-scattered so that every lane of
 // a slot's first quad adds ONE row per register group into the ray's accumulator (8 read-modify-writes per lane and tile
 // instead of 32 by the slot's last lane).  Summation order differs from the general path (pairwise instead of front to back).
-__device__ __forceinline__ void fused_composite_slots(const FusedRender &fr, int C, int lane, const TileSample &sm, float sigma,
+__device__ __forceinline__ void fused_composite_slots(const FusedRender &fr, int C, int lane, const TileSample &sm, const SampleKeep &sk,
                                                       const float (&rgb)[3], const f32x16 (&sem)[CT], WaveCounters &wc, bool owner,
                                                       int view, int budget, const float (&c_prev)[3], float d_prev,
                                                       const float (&v_prev)[4]) {
@@ -210,7 +261,7 @@ __device__ __forceinline__ void fused_composite_slots(const FusedRender &fr, int
         for (int g = 0; g < 4; ++g) s_prev[ct][g] = (s_store[ct] && j + 4 * h + 8 * g < C) ? s_ptr[ct][8 * g] : 0.f;
     }
     // ---- weights (volrend.py:258-267, :361-365; utils.py:712-725): exclusive prefix of sigma*dt inside the slot ----
-    const float sdt = sm.valid ? sigma * (sm.te - sm.ts) : 0.0f;
+    const float sdt = sk.sdt;
     const int in_slot = lane & (stride - 1);
     float incl = sdt;
     {
@@ -220,10 +271,10 @@ __device__ __forceinline__ void fused_composite_slots(const FusedRender &fr, int
         if (stride >= 16) { t = dpp_f32<0x118, 0xf>(incl); incl += in_slot >= 8 ? t : 0.0f; }
     }
     const float excl = incl - sdt;
-    const float alpha = 1.0f - expf(-sdt);
+    const float alpha = 1.0f - expf(-sdt);                 // for the weight only: which samples count is sk.kept
     const float opac0 = sm.opac0;
     const float w = expf(-excl) * (1.0f - opac0) * alpha;
-    const bool keep = sm.valid && !(fr.alpha_thre > 0.f && !(alpha >= fr.alpha_thre));
+    const bool keep = (sk.kept >> lane) & 1ull;
     const float wk = keep ? w : 0.0f;
     const float tmid = sm.valid ? (sm.ts + sm.te) / 2.0f : 0.0f;   // an unused column holds whatever the workspace held before: 0 * NaN would poison the depth of its ray
     float tot[6] = {wk, wk * rgb[0], wk * rgb[1], wk * rgb[2], wk * tmid, sm.valid ? 1.0f : 0.0f};
@@ -251,11 +302,11 @@ __device__ __forceinline__ void fused_composite_slots(const FusedRender &fr, int
             if (s_store[ct] && j + 4 * h + 8 * g < C) s_ptr[ct][8 * g] = s_prev[ct][g] + z;
         }
     }
-    finish_rays(fr, lane, sm, wc, owner, view, budget, cnt, c_new, d_new, o_new, v_prev, vt, __popcll(__ballot(keep)), __popcll(__ballot(sm.valid)));
+    finish_rays(fr, lane, sm, wc, owner, view, budget, cnt, c_new, d_new, o_new, v_prev, vt, __popcll(sk.kept), __popcll(__ballot(sm.valid)));
 }
 
 __device__ __forceinline__ void fused_composite(const FusedRender &fr, int C, int lane, const TileSample &sm,
-                                                float sigma, const float (&rgb)[3], const f32x16 (&sem)[CT], WaveCounters &wc) {
+                                                const SampleKeep &sk, const float (&rgb)[3], const f32x16 (&sem)[CT], WaveCounters &wc) {
     const int c = lane & 31, h = lane >> 5;
     // run structure from the per-column ray ids: valid columns of a ray are consecutive lanes
     const int prev_ray = __shfl_up(sm.ray, 1, 64);
@@ -267,6 +318,13 @@ __device__ __forceinline__ void fused_composite(const FusedRender &fr, int C, in
     const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
     const int tail_lane = above ? lane + (__ffsll(above) - 1) : 63;
     const int maxlen = sm.stride;
+#ifdef MNF_DIAG
+    {   // MNF_ROUND_LOG: rays of this (live) tile, and those of them without a kept sample
+        const unsigned long long run = (tail_lane == 63 ? ~0ull : ((1ull << (tail_lane + 1)) - 1ull)) & ~((1ull << lane) - 1ull);
+        wc.live_rays += __popcll(__ballot(owner));
+        wc.idle_rays += __popcll(__ballot(owner && (sk.kept & run) == 0ull));
+    }
+#endif
     // ---- every load of the epilogue is issued here, before any arithmetic or store: they depend only on the run
     //      structure, and issued one read-modify-write at a time they cost four to five serial memory round trips
     //      per tile at two waves per SIMD ----
@@ -285,7 +343,7 @@ __device__ __forceinline__ void fused_composite(const FusedRender &fr, int C, in
     }
     const bool fast = (maxlen == 4 || maxlen == 8 || maxlen == 16) && !fr.general_only;   // wave-uniform: aligned power-of-two slots
     if (fast) {
-        fused_composite_slots(fr, C, lane, sm, sigma, rgb, sem, wc, owner, view, budget, c_prev, d_prev, v_prev);
+        fused_composite_slots(fr, C, lane, sm, sk, rgb, sem, wc, owner, view, budget, c_prev, d_prev, v_prev);
         return;
     }
     f32x16 s_prev[CT];
@@ -304,14 +362,14 @@ __device__ __forceinline__ void fused_composite(const FusedRender &fr, int C, in
         }
     }
     // ---- weights: w = exp(-excl_sum(sigma*dt)) * (1 - opacity_before) * alpha ----
-    const float sdt = sm.valid ? sigma * (sm.te - sm.ts) : 0.0f;
+    const float sdt = sk.sdt;
     float sc[1] = {sdt};
     seg_scan_dpp<1>(sc, heads, lane, maxlen);
     const float excl = sc[0] - sdt;
-    const float alpha = 1.0f - expf(-sdt);
+    const float alpha = 1.0f - expf(-sdt);                              // for the weight only: which samples count is sk.kept
     const float opac0 = sm.opac0;
     const float w = expf(-excl) * (1.0f - opac0) * alpha;               // volrend.py:258-267, :361-365; utils.py:712
-    const bool keep = sm.valid && !(fr.alpha_thre > 0.f && !(alpha >= fr.alpha_thre));   // utils.py:714-725
+    const bool keep = (sk.kept >> lane) & 1ull;                         // sample_keep(): utils.py:714-725
     const float wk = keep ? w : 0.0f;
     const float tmid = sm.valid ? (sm.ts + sm.te) / 2.0f : 0.0f;   // an unused column holds whatever the workspace held before: 0 * NaN would poison the depth of its ray
     // ---- per-ray sums of the lane=sample quantities ----
@@ -369,7 +427,7 @@ __device__ __forceinline__ void fused_composite(const FusedRender &fr, int C, in
             }
         }
     }
-    finish_rays(fr, lane, sm, wc, owner, view, budget, cnt, c_new, d_new, o_new, v_prev, vt, __popcll(__ballot(keep)), __popcll(__ballot(sm.valid)));
+    finish_rays(fr, lane, sm, wc, owner, view, budget, cnt, c_new, d_new, o_new, v_prev, vt, __popcll(sk.kept), __popcll(__ballot(sm.valid)));
 }
 
 MNF_DT_END

@@ -54,6 +54,9 @@ struct FusedRender {
     unsigned long long *totals;   // [2]: kept samples, evaluated samples
     int32_t rays_per_view, probabilistic;
     int32_t general_only;         // diagnostic (MNF_COMPOSITE_GENERAL=1): composite every tile with the general segmented-scan path
+    int32_t tile_skip;            // 0: a tile without a kept sample stops behind the density (field.hip).  Diagnostic: 1 (MNF_NO_TILE_SKIP=1) no tile does,
+                                  // 2 (MNF_TILE_SKIP_ALL=1) every tile does (wrong pictures: what a tile costs up to the density, on the same columns)
+    uint32_t *diag_counts;        // diagnostic (MNF_ROUND_LOG, -DMNF_DIAG kernels only): [3] tiles without a kept sample | rays of the other tiles | those of them without a kept sample
     float alpha_thre, opc_thre;
 };
 

@@ -509,6 +509,22 @@ __global__ void __launch_bounds__(kThreads, 2) field_kernel(const KernelArgs arg
             continue;
         }
 
+        // ---- renderer: does any sample of this tile count? ----
+        // The reference drops every sample with alpha < alpha_thre before it accumulates anything (utils.py:714-725), and alpha needs the density only.  A tile
+        // without a kept sample (wave-uniform) therefore stops here: no SH, no heads, no compositing, only its rays' retirement (dead_tile_rays).  The outputs keep
+        // their bits: with every weight 0 all per-ray totals of the compositing are exact zeros and x + 0.0f == x; the accumulators start at +0 and never become -0
+        // (+0 + -0 = +0), so s_prev + sum(sem * 0) is s_prev; the variances add 0 * e^2.  The one difference: a non-finite head output of an invisible sample
+        // (0 * Inf) no longer reaches its ray from such a tile — as in the reference, which indexes those samples away.
+        SampleKeep sk = {0.f, 0ull};
+        if (MODE == 2) {
+            sk = sample_keep(la.io.fr.alpha_thre, tsm, sigma);
+            const int tile_skip = la.io.fr.tile_skip;
+            if (tile_skip == 2 || (sk.kept == 0ull && tile_skip == 0)) {
+                dead_tile_rays(fr_of_kernarg(), in_loop_v(lane), tsm, wc);
+                continue;
+            }
+        }
+
         // ---- heads ----
         half8 bgeo[CT][1];
 #pragma unroll
@@ -564,7 +580,7 @@ __global__ void __launch_bounds__(kThreads, 2) field_kernel(const KernelArgs arg
             rgb[k] = 1.0f / (1.0f + expf(-(h ? t1 : t0)));   // ngp.py:211-212
         }
         if (MODE == 2) {
-            fused_composite(fr_of_kernarg(), in_loop(la.C), in_loop_v(lane), tsm, sigma, rgb, out_sem, wc);
+            fused_composite(fr_of_kernarg(), in_loop(la.C), in_loop_v(lane), tsm, sk, rgb, out_sem, wc);
             continue;
         }
         if (col < n) {

@@ -88,7 +88,7 @@ static int64_t carve(RenderWs *ws, char *base, int64_t n_rays, int32_t rays_per_
     p = take(n_views * 4); if (ws) ws->n_samples = (int32_t *)p;
     p = take(2 * n_views * 4); if (ws) ws->iter_samples = (int32_t *)p;
     p = take(n_views * 4); if (ws) ws->active = (int32_t *)p;
-    p = take(256); if (ws) { ws->n_cols = (int32_t *)p; ws->any_active = (int32_t *)p + 2; ws->overflow = (int32_t *)p + 4; }   // n_cols[2] | any_active[2] | overflow
+    p = take(256); if (ws) { ws->n_cols = (int32_t *)p; ws->any_active = (int32_t *)p + 2; ws->overflow = (int32_t *)p + 4; }   // n_cols[2] | any_active[2] | overflow | ... | words 8..10: the round log's tile counters (FusedRender::diag_counts)
     p = take(512); if (ws) ws->tickets = (uint32_t *)p;
     p = take(kMaxGridWords * 4); if (ws) ws->bitgrid = (uint32_t *)p;
     p = take(col_cap * 4); if (ws) ws->col_ray = (int32_t *)p;
@@ -589,6 +589,8 @@ int job_begin(RenderJob &j, mnf_field_t f, const uint8_t *binaries, int32_t res_
     io.fr.totals = reinterpret_cast<unsigned long long *>(total_samples);
     io.fr.rays_per_view = opts->rays_per_view; io.fr.probabilistic = opts->probabilistic;
     io.fr.general_only = diag_env("MNF_COMPOSITE_GENERAL") != nullptr;   // tests compare the two compositing paths with it
+    io.fr.tile_skip = diag_env("MNF_TILE_SKIP_ALL") ? 2 : (diag_env("MNF_NO_TILE_SKIP") ? 1 : 0);   // tests/diag_tile_skip.py compares 0 with 1; 2 measures a tile's cost up to the density
+    io.fr.diag_counts = round_log() ? reinterpret_cast<uint32_t *>(j.ws.n_cols) + 8 : nullptr;     // three spare words of the flag block (carve())
     io.fr.alpha_thre = opts->alpha_thre; io.fr.opc_thre = opc_thre;
     j.io = io;
     j.max_rounds = (int)ceil_div(opts->max_samples, j.min_samples);
@@ -626,6 +628,7 @@ int job_enqueue_block(RenderJob &j, int block) {
         int rc;
         {
             ProfScope ps("field_render", s);
+            if (round_log()) MNF_HIP(hipMemsetAsync(j.io.fr.diag_counts, 0, 3 * sizeof(uint32_t), s));
             if (round_log()) MNF_HIP(hipEventRecord(log_events()[0], s));
             rc = launch_field(j.f, j.io, false, s);   // field evaluation + compositing + ray retirement of this round
             if (round_log()) MNF_HIP(hipEventRecord(log_events()[1], s));
@@ -640,6 +643,8 @@ int job_enqueue_block(RenderJob &j, int block) {
             MNF_HIP(hipMemcpyAsync(act, j.ws.active, 4 * (n_views < 8 ? n_views : 8), hipMemcpyDeviceToHost, s));
             MNF_HIP(hipMemcpyAsync(act_all.data(), j.ws.active, 4 * (size_t)n_views, hipMemcpyDeviceToHost, s));
             MNF_HIP(hipMemcpyAsync(alive_all.data(), j.ws.alive_count + (parity ^ 1) * n_views, 4 * (size_t)n_views, hipMemcpyDeviceToHost, s));
+            uint32_t skip[3] = {0u, 0u, 0u};      // tiles without a kept sample | rays of the other tiles | those of them without a kept sample
+            MNF_HIP(hipMemcpyAsync(skip, j.io.fr.diag_counts, sizeof(skip), hipMemcpyDeviceToHost, s));
             MNF_HIP(hipStreamSynchronize(s));
             int n_act = 0; long long n_alive_after = 0;
             for (int v = 0; v < n_views; ++v) { n_act += act_all[v] != 0; n_alive_after += alive_all[v]; }
@@ -648,6 +653,7 @@ int job_enqueue_block(RenderJob &j, int block) {
             (void)hipEventElapsedTime(&ms_march, log_events()[2], log_events()[3]);
             fprintf(stderr, "[mnf round %d] cols %d  field %.4f ms (%.3f ns/col)  march %.4f ms  active_views %d  alive_after %lld  budgets", round, n_cols, ms, n_cols ? ms * 1e6 / n_cols : 0.0, ms_march, n_act, n_alive_after);
             for (int v = 0; v < n_views && v < 8; ++v) fprintf(stderr, " %d", act[v] ? ns[v] : 0);
+            fprintf(stderr, "  tiles %d dead %u  live_rays %u idle %u", (n_cols + 63) / 64, skip[0], skip[1], skip[2]);
             fprintf(stderr, "\n");
         }
     }

@@ -169,6 +169,9 @@ SIGNATURES = {
     "mnf_eval_views_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32]),
     "mnf_eval_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_ssim_views_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "mnf_ssim_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_double,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mnf_frames_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_double,
                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mnf_score_ensemble_views_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32]),

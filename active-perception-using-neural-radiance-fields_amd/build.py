@@ -37,6 +37,7 @@ SOURCES = {
     "ensemble.hip": [],
     "frames.hip": ["-ffp-contract=off"],    # every output byte is a chain of separately rounded operations
     "infomap.hip": ["-ffp-contract=off"],   # the heat bytes are a chain of separately rounded float64 operations
+    "ssim.hip": ["-ffp-contract=off"],      # 2 (m m) and m m + m m stay the same double: SSIM(x, x) is exactly 1
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
 }

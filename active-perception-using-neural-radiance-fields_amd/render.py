@@ -1530,9 +1530,76 @@ def eval_metrics(rgb, depth, sem, dataset, image_ids, pix_idx=None, confusion=Tr
     return dict(metrics=metrics, confusion=conf, pred_labels=pred)
 
 
+# structural similarity (Wang et al. 2004) over the valid windows: skimage's gaussian_weights=True form, mip-NeRF's compute_ssim
+SSIM_WINDOW, SSIM_SIGMA = 11, 1.5      # MNF_SSIM_WINDOW / MNF_SSIM_SIGMA (include/mi355nerf.h): fixed
+SSIM_K1, SSIM_K2 = 0.01, 0.03
+SSIM_MAX_CHANNELS = 4                  # MNF_SSIM_MAX_CHANNELS
+
+
+def _ssim_into(pred, target, target_u8, ids, ppi, V, H, W, K, data_range, ssim, maps, k1=SSIM_K1, k2=SSIM_K2):
+    """`mnf_ssim_views` (csrc/ssim.hip) on contiguous device tensors: `pred` [V,H,W,K] f32 against `target` (f32, same shape) or against
+    `target_u8` (dataset storage, view v = image `ids[v]`) into `ssim` [V] f64 and `maps` [V,H-10,W-10] f64 or None."""
+    lib = L.load_library()
+    with torch.cuda.device(pred.device):
+        nbytes = max(int(lib.mnf_ssim_views_workspace_bytes(V, H, W, K)), 8)
+        ws = _workspace((pred.device, "ssim"), nbytes)
+        L.launch(lib.mnf_ssim_views, L.ptr(pred), L.ptr(target), L.ptr(target_u8), L.ptr(ids), ppi, V, H, W, K, float(data_range), float(k1), float(k2),
+                 L.ptr(ssim), L.ptr(maps), L.ptr(ws), nbytes)
+
+
+def _ssim_outputs(V, H, W, maps, device):
+    ssim = torch.empty(V, dtype=torch.float64, device=device)
+    return ssim, (torch.empty(V, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1, dtype=torch.float64, device=device) if maps else None)
+
+
+@torch.no_grad()
+def ssim_views(pred, target, *, data_range=1.0, maps=False):
+    """Structural similarity of V views against V targets on the device (`mnf_ssim_views`, csrc/ssim.hip): what
+    `skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=data_range,
+    channel_axis=-1)` returns after its border crop — the 11 x 11 Gaussian window over the valid windows only, in float64 from the fp32
+    values.  `pred` and `target` are [V,H,W,K] fp32 GPU tensors, K <= 4; a [V,H,W] plane is K = 1.  Not only rgb: depth against depth with
+    `data_range` = the depth span, or one ensemble member's render against another's.
+    Returns dict(ssim=[V] float64, maps=[V,H-10,W-10] float64 | None) as device tensors (a map is the mean of the channels' SSIM at every
+    window centre) and does not synchronise.  A view's bits do not depend on the other views of the call."""
+    if pred.shape != target.shape or pred.dim() not in (3, 4):
+        raise ValueError(f"ssim_views takes pred and target of one shape [V,H,W,K] or [V,H,W] (got {tuple(pred.shape)}, {tuple(target.shape)})")
+    V, H, W = (int(x) for x in pred.shape[:3])
+    K = int(pred.shape[3]) if pred.dim() == 4 else 1
+    if not 1 <= K <= SSIM_MAX_CHANNELS:
+        raise ValueError(f"ssim_views takes 1 to {SSIM_MAX_CHANNELS} channels (got {K})")
+    if not (np.isfinite(data_range) and data_range > 0):
+        raise ValueError(f"data_range must be finite and positive (got {data_range})")
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f"SSIM's {SSIM_WINDOW} x {SSIM_WINDOW} window needs images of at least that size (got {H} x {W})")
+    L.require_gpu(pred, target)
+    ssim, out_maps = _ssim_outputs(V, H, W, maps, pred.device)
+    _ssim_into(L.contig(pred, torch.float32), L.contig(target, torch.float32), None, None, 0, V, H, W, K, data_range, ssim, out_maps)
+    return dict(ssim=ssim, maps=out_maps)
+
+
+@torch.no_grad()
+def ssim_metrics(rgb, dataset, image_ids, *, maps=False):
+    """`ssim_views` of finished rgb renders against the images a `Dataset` holds: rgb [V,H,W,3] or [V,P,3] (P = the dataset's height x
+    width) for the images `image_ids` [V].  `dataset.images` is read as it is stored (u8, (float)u8 / 255.0f per channel: the pixels
+    `Dataset.__getitem__` hands out); no fp32 ground-truth image is made.  data_range is 1.  Returns what `ssim_views` returns."""
+    L.require_gpu(rgb, dataset.images)
+    if dataset.images.dtype != torch.uint8:
+        raise TypeError("ssim_metrics reads u8 images")
+    H, W = int(dataset.height), int(dataset.width)
+    ids = _eval_index_tensor(image_ids, rgb.device, len(dataset), "image_ids")
+    V = int(ids.shape[0])
+    if rgb.dim() not in (3, 4) or int(rgb.shape[0]) != V or int(rgb.shape[-1]) != 3 or rgb.numel() != V * H * W * 3:
+        raise ValueError(f"ssim_metrics takes rgb [V,H,W,3] or [V,H*W,3] of {V} views of {H} x {W} pixels (got {tuple(rgb.shape)})")
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f"SSIM's {SSIM_WINDOW} x {SSIM_WINDOW} window needs images of at least that size (got {H} x {W})")
+    ssim, out_maps = _ssim_outputs(V, H, W, maps, rgb.device)
+    _ssim_into(L.contig(rgb, torch.float32), None, dataset.images.contiguous(), ids, H * W, V, H, W, 3, 1.0, ssim, out_maps)
+    return dict(ssim=ssim, maps=out_maps)
+
+
 @torch.no_grad()
 def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, render_step_size, cone_angle, alpha_thre, max_samples=1024,
-                   render_bkgd=None, views_per_call=4, return_images=False, labels=False):
+                   render_bkgd=None, views_per_call=4, return_images=False, labels=False, ssim=False):
     """The evaluation block of `nerf_training` (pipeline.py:550-613) as one call: the held-out images `indices` of `dataset` are rendered
     `views_per_call` at a time — one batched `mnf_generate_rays` (all pixels, row-major: the evaluation branch of `Dataset.fetch_data`),
     one batched test render (a view's result is that of `render_image_with_occgrid_test` on `dataset[i]["rays"]`, bit for bit, whatever
@@ -1542,7 +1609,9 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
     with `pixel_accuracy` and `miou` (`miou_from_confusion`); `mean` = {"psnr", "depth_mse", "sem_ce"}, the three numbers
     pipeline.py:650-656 prints.  Raises ValueError when a view has labels outside [0, C) (so does torch's cross_entropy).
     `return_images=True` adds the device tensors `rgb` [N,H,W,3], `acc` [N,H,W,1], `depth` [N,H,W,1], `sem` [N,H,W,C], and
-    `pred_labels` [N,H,W] uint8 with `labels=True` (the argmax image of pipeline.py:1011)."""
+    `pred_labels` [N,H,W] uint8 with `labels=True` (the argmax image of pipeline.py:1011).
+    `ssim=True` adds `ssim`, the per-view float64 structural similarity of the rgb render against the stored image (`ssim_metrics`, on
+    the device, in the same single copy), and `mean["ssim"]`."""
     lib = L.load_library()
     idx = [int(i) for i in (indices.tolist() if hasattr(indices, "tolist") else indices)]
     if not idx:
@@ -1555,7 +1624,7 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
     L.require_gpu(dataset.images, dataset.camtoworlds)
     bkgd = torch.ones(3) if render_bkgd is None else render_bkgd.detach().cpu()      # a host tensor: the render options take host floats
     per = max(1, int(views_per_call))
-    rows, conf, imgs = [], None, dict(rgb=[], acc=[], depth=[], sem=[], pred_labels=[])
+    rows, conf, imgs, sims = [], None, dict(rgb=[], acc=[], depth=[], sem=[], pred_labels=[]), []
     for g0 in range(0, len(idx), per):
         ids = torch.tensor(idx[g0:g0 + per], dtype=torch.int64, device=dev)
         V = int(ids.shape[0])
@@ -1568,6 +1637,8 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
         m = eval_metrics(r["rgb"], r["depth"], r["sem"], dataset, ids, None, confusion=True, labels=labels and return_images)
         rows.append(m["metrics"])
         conf = m["confusion"] if conf is None else conf + m["confusion"]
+        if ssim:
+            sims.append(ssim_metrics(r["rgb"].view(V, H, W, 3), dataset, ids)["ssim"])
         if return_images:
             for k in ("rgb", "acc", "depth", "sem"):
                 imgs[k].append(r[k].view(V, H, W, -1))
@@ -1575,9 +1646,9 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
                 imgs["pred_labels"].append(m["pred_labels"].view(V, H, W))
     n = len(idx)
     # the one device-to-host copy: the metric rows and the matrix (its int64 bits carried as float64 words) in one block
-    host = torch.cat([torch.cat(rows).reshape(-1), conf.view(torch.float64).reshape(-1)]).cpu()
+    host = torch.cat([torch.cat(rows).reshape(-1), conf.view(torch.float64).reshape(-1)] + sims).cpu()
     met = host[:n * 8].numpy().reshape(n, 8)
-    confusion = host[n * 8:].view(torch.int64).numpy().reshape(C, C).copy()
+    confusion = host[n * 8:n * 8 + C * C].view(torch.int64).numpy().reshape(C, C).copy()
     if (met[:, 6] > 0).any():
         bad = [idx[k] for k in np.nonzero(met[:, 6] > 0)[0]]
         raise ValueError(f"ground-truth labels outside [0, {C}) in image(s) {bad}: {int(met[:, 6].sum())} pixels")
@@ -1587,6 +1658,9 @@ def evaluate_views(radiance_field, estimator, dataset, indices, *, near_plane, r
     out["pixel_accuracy"] = float(np.trace(confusion) / total) if total else float("nan")
     out["miou"] = miou_from_confusion(confusion)
     out["mean"] = {"psnr": float(np.mean(out["psnr"])), "depth_mse": float(np.mean(out["depth_mse"])), "sem_ce": float(np.mean(out["sem_ce"]))}
+    if ssim:
+        out["ssim"] = host[n * 8 + C * C:].numpy().copy()
+        out["mean"]["ssim"] = float(np.mean(out["ssim"]))
     if return_images:
         for k in ("rgb", "acc", "depth", "sem") + (("pred_labels",) if labels else ()):
             out[k] = torch.cat(imgs[k])

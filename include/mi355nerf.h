@@ -683,6 +683,38 @@ int mnf_eval_views(const float *rgb, const float *depth, const float *sem, int32
                    double *metrics, int64_t *confusion, uint8_t *pred_labels,
                    void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
+/* The structural similarity (SSIM, Wang et al. 2004) that belongs next to the PSNR of scripts/pipeline.py:550-613 (the reference imports
+ * skimage at :20; a caller who wants the number copies the float planes of every view to the host and filters them there), as one pass
+ * over the finished planes of n_views views of height x width pixels of `channels` channels: pred [V,H,W,K] f32 against target_f32
+ * [V,H,W,K] f32, or against target_u8, the dataset's image storage [N,pixels_per_image,3] u8 (view v is image image_ids[v], int64 on
+ * the device; needs K = 3 and pixels_per_image == H * W; a stored byte is (float)u8 / 255.0f as mnf_gather_pixels computes it).
+ * Exactly one of the two targets is given.  The quantity is what skimage.metrics.structural_similarity(gaussian_weights=True,
+ * sigma=1.5, use_sample_covariance=False, data_range=L, channel_axis=-1) returns after its border crop, over the VALID windows only,
+ * in double from the widened fp32 inputs:
+ *   g[i] = exp(-0.5 ((i - 5) / 1.5)^2), i = 0 .. 10, normalised to sum 1; the window is g (x) g, applied separably, rows (along W)
+ *   first, then columns, taps added in index order, no padding: outputs exist for the (H - 10) x (W - 10) window centres only;
+ *   per channel the five filtered planes mx, my, E[xx], E[yy], E[xy]; vx = E[xx] - mx mx, vy likewise, cxy = E[xy] - mx my;
+ *   S_c = ((2 mx my + C1) (2 cxy + C2)) / ((mx mx + my my + C1) (vx + vy + C2)), C1 = (k1 L)^2, C2 = (k2 L)^2, L = data_range
+ *   (k1 = 0.01, k2 = 0.03 are the usual constants).
+ * Outputs: ssim [V] f64 = the sum of S_c over centres and channels / ((H - 10) (W - 10) K); map [V,H-10,W-10] f64 or NULL =
+ * (S_0 + ... + S_{K-1}) / K per centre; both 8-byte aligned, no byte outside them is written.  Identical images give exactly 1.0 at
+ * every centre.  NaN / inf propagate as they do in numpy: a NaN pixel makes exactly the <= 11 x 11 centres whose window covers it NaN.
+ * No floating-point atomics: the same inputs give the same bits, and a view's bits depend on that view's data, H, W and K only, not
+ * on n_views or on its position in the call.  The f32 planes need 4-byte alignment only; nothing outside the planes is read.
+ * workspace: mnf_ssim_views_workspace_bytes(V, H, W, K) bytes, 8-byte aligned (per-workgroup partial sums).  Argument errors (H or
+ * W < 11, K outside 1 .. 4, both or neither target, a u8 target with K != 3 or pixels_per_image != H * W, a non-finite or
+ * non-positive data_range, a non-finite or negative k1 / k2, ssim NULL, a misaligned map, a workspace that is too small, more than
+ * 65535 views) return MNF_ERR_INVALID before any HIP call; n_views == 0 returns MNF_OK.  Profile label: "ssim_views".  Enqueues on
+ * `stream` and does not synchronise. */
+#define MNF_SSIM_WINDOW 11
+#define MNF_SSIM_SIGMA 1.5
+#define MNF_SSIM_MAX_CHANNELS 4
+int64_t mnf_ssim_views_workspace_bytes(int32_t n_views, int32_t height, int32_t width, int32_t channels);
+int mnf_ssim_views(const float *pred, const float *target_f32, const uint8_t *target_u8, const int64_t *image_ids,
+                   int64_t pixels_per_image, int32_t n_views, int32_t height, int32_t width, int32_t channels,
+                   double data_range, double k1, double k2, double *ssim, double *map,
+                   void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 /* ---------------------------------------------------------------- 8-bit frames of finished renders */
 
 /* The frame conversion of scripts/pipeline.py:976-1023 (per rendered pose: np.float32(rgb * 255), np.clip(dep * 25, 0, 255), acc * 255,

@@ -318,7 +318,8 @@ extern "C" int mnf_occ_sample_cells(const float *occs, const uint32_t *bitgrid, 
                                     const int64_t *indices_in, const float *jitter_in, int64_t n_in,
                                     int64_t *cell_idx, float *points, int64_t capacity, void *workspace, int64_t workspace_bytes,
                                     mnf_stream_t stream) {
-    MNF_REQUIRE(occs && aabb_host && cell_idx && points && workspace, "occ_sample_cells: null pointer");
+    // a list of capacity 0 (fewer than four cells after the warm-up) has no storage: an empty tensor's pointer is null
+    MNF_REQUIRE(occs && aabb_host && workspace && (capacity == 0 || (cell_idx && points)), "occ_sample_cells: null pointer");
     MNF_REQUIRE(res_x > 0 && res_y > 0 && res_z > 0, "occ_sample_cells: bad resolution");
     const int64_t cells = (int64_t)res_x * res_y * res_z;
     MNF_REQUIRE(cells < ((int64_t)1 << 31), "occ_sample_cells: grid too large");

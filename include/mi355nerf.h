@@ -198,7 +198,8 @@ int mnf_accumulate_along_rays_backward(const float *weights, const float *values
  * mnf_update_occupancy does the whole chain for one level with the field's own density kernel as occ_eval_fn
  * (scripts/pipeline.py:376-378: query_density(x) * render_step_size).
  * The sample list has a fixed capacity (mnf_occ_list_capacity: every cell during warm-up, 2 * (cells / 4) afterwards);
- * unused slots hold cell index -1 and a point inside the box.  Draws: Philox4x32-10, counter (element, 0, kind, step),
+ * unused slots hold cell index -1 and a point inside the box (the box centre); a capacity of 0 — fewer than four cells past
+ * the warm-up — is valid: nothing is written and cell_idx / points may be NULL.  Draws: Philox4x32-10, counter (element, 0, kind, step),
  * key = seed, kind 0 uniform / 1 occupied / 2 warm-up; word 0 -> cell, words 1..3 -> in-cell offsets (24-bit).  Tests
  * pass the reference's recorded draws instead (indices_in, jitter_in [n_in,3]).  Duplicate cells: the last list element
  * wins.  workspace: mnf_occ_workspace_bytes(cells, fused), the same buffer for sample and apply of one refresh. */

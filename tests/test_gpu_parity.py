@@ -874,7 +874,9 @@ def test_occupancy_update_device_rng_and_fused_path(scene):
     warm-up touches every cell once (occs == max(0 * decay, density * step) of a point inside the cell); afterwards only
     listed cells change, the uniform half lands on ~N distinct cells, every occupied cell is re-evaluated while there are
     fewer than N of them, the same seed reproduces the update bit for bit, and the single-call fused form
-    (mnf_update_occupancy) equals the three-call form with the same seed."""
+    (mnf_update_occupancy) equals the three-call form with the same seed.
+    The bit-exact statement of this path — the Philox stream, the occupied half, apply, binarize, several levels and the
+    fused call against the numpy restatement tests/occ_ref.py — is tests/test_gpu_occupancy.py; here only statistics."""
     from apnrf_amd.nerfacc import FieldDensityOcc, OccGridEstimator
     hip = H.hip_field(scene)
     step_size = 1e-3

@@ -137,6 +137,8 @@ SIGNATURES = {
                                      c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mnf_field_forward_train_samples": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_field_backward_inputs": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "mnf_ray_input_gradients": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     "mnf_presample_create": (c_int32, [POINTER(c_void_p)]),
     "mnf_presample_destroy": (None, [c_void_p]),
     "mnf_train_presample_workspace_bytes": (c_int64, [c_int32, c_int64]),

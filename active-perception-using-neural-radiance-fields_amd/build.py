@@ -22,13 +22,14 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + INCLUDE, "-I" + CSRC]
 # march.hip / render.hip hold the bit-exact marcher: no FMA contraction (see csrc/march_dev.h)
-# value: (source file, extra flags); field / train are built twice: fp16 and bf16 matrix-core operands (csrc/common.h)
+# value: (source file, extra flags); field / train / inputgrad are built twice: fp16 and bf16 matrix-core operands (csrc/common.h)
 SOURCES = {
     "api.cpp": [],
     "march.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "field.hip": ["-fno-slp-vectorize"],   # packed-fp32 pairing of the compositing butterflies keeps their DPP operands from folding into the adds
     "train.hip": [],
+    "inputgrad.hip": [],
     "composite_train.hip": [],
     "occupancy.hip": ["-ffp-contract=off"],
     "vanilla.hip": [],
@@ -40,6 +41,7 @@ SOURCES = {
     "ssim.hip": ["-ffp-contract=off"],      # 2 (m m) and m m + m m stay the same double: SSIM(x, x) is exactly 1
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
+    "inputgrad.hip@bf16": ["-DMNF_BF16"],
 }
 # translation units that read diagnostic knobs (csrc/common.h: diag_env): recompiled with -DMNF_DIAG for the diag library
 DIAG_UNITS = ("render.hip", "field.hip", "train.hip", "field.hip@bf16", "train.hip@bf16", "trainstep.hip")

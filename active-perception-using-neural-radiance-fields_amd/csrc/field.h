@@ -114,6 +114,18 @@ struct TrainBuf {
     int32_t rows;
 };
 
+// What the backward leaves in the train workspace for the input gradients (inputgrad.hip): the un-scaled feature gradients, the normalised positions
+// and the loss-scaled pre-activation gradients of the rgb head's first layer (rows row_dZr1 .. row_dZr1 + W/2 of `act`), plus the handle's map from
+// the head's SH weights W1[j][k] (k < 16) to their slot in d_frags.
+struct InputGradView {
+    const void *act;          // [tiles][rows][64] 16-bit elements
+    const float *dX;          // [16][Np][4]
+    const float *xn;          // [n][3]
+    int64_t Np;
+    int32_t rows, row_dZr1;
+    const int32_t *sh_slot;   // [W/2][16] device: index into d_frags
+};
+
 // dispatchers on the handle's operand type (defined once, in the fp16 translation units)
 void free_train_state(mnf_field_t f);
 int launch_field(mnf_field_t f, const FieldIO &io, bool density_only, hipStream_t stream, const TrainBuf *train = nullptr);
@@ -136,6 +148,9 @@ int backward(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_
                       const float *d_density, const float *d_sem, const float *rgb, const float *density, void *workspace,          \
                       int64_t workspace_bytes, float loss_scale, float *g_base, float *g_head, float *g_sem, bool zero_grads,       \
                       bool positions_normalized, bool deterministic, hipStream_t stream);                                           \
+    int input_grad_view_impl(mnf_field_t f, void *workspace, int64_t n, InputGradView &view);                                        \
+    int field_input_grad_impl(mnf_field_t f, const InputGradView &view, const float *directions, int64_t n, float loss_scale,       \
+                              float *d_positions, float *d_directions, hipStream_t stream);                                          \
     }
 MNF_DECLARE_DT_IMPL(f16)
 MNF_DECLARE_DT_IMPL(bf16)

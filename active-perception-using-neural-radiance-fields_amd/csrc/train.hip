@@ -845,6 +845,7 @@ struct TrainTables {
     std::vector<WgradJob> jobs;
     std::vector<WgradGroup> groups;
     int rows, mask_blocks, mask_bytes;
+    int row_dZr1;      // first row of the rgb head's first-layer pre-activation gradients (the input gradients read them)
 };
 
 static void add_jobs(std::vector<WgradJob> &jobs, int buf, int64_t off, int n_out_real, int stride, int n_in_real,
@@ -881,6 +882,7 @@ static TrainTables build_tables(int C) {
     const int sem_pad = ((C + 15) / 16) * 16;
     TrainTables tt;
     tt.rows = T::rows; tt.mask_blocks = T::mask_blocks; tt.mask_bytes = T::mask_bytes;
+    tt.row_dZr1 = T::rdZr1;
     // parameter offsets (reference state_dict layout)
     int64_t b_in = 0, b_hid = (int64_t)W * 64, b_out = b_hid + (int64_t)(NH - 1) * W * W;
     int64_t h_in = 0, h_hid = (int64_t)Wh * 32, h_out = h_hid + (int64_t)Wh * Wh;
@@ -974,6 +976,8 @@ struct TrainState {
     size_t partials_floats = 0;
     // binned scatter of the large hashed levels (allocated on first use, grows with the sample bound): item lists + list cursors
     uint32_t *d_bin_cursors = nullptr;
+    // forward fragment slot of the rgb head's SH weights W1[j][k], j < W/2, k < 16 (the direction gradient stages them from d_frags)
+    int32_t *d_sh_slot = nullptr;
 };
 
 static int ensure_train_state(mnf_field_t f) {
@@ -984,6 +988,7 @@ static int ensure_train_state(mnf_field_t f) {
         set_error("train: unsupported neurons=%d layers=%d", f->cfg.neurons, f->cfg.layers);
         return MNF_ERR_UNSUPPORTED;
     }
+    std::vector<int32_t> sh_slot((size_t)(f->cfg.neurons / 2) * 16, -1);
     {   // parameter id -> forward fragment slot
         std::vector<int32_t> slot_of[3];
         slot_of[0].assign((size_t)f->n_base_mlp, -1); slot_of[1].assign((size_t)f->n_head, -1); slot_of[2].assign((size_t)f->n_sem, -1);
@@ -993,6 +998,9 @@ static int ensure_train_state(mnf_field_t f) {
         }
         for (auto &s : ts->tt.fragT)
             if (s >= 0) s = slot_of[s >> 28][s & 0x0FFFFFFF];
+        // rgb head, first layer W1[W/2][32] at offset 0 of the head vector: columns 0..15 are the SH inputs
+        for (size_t j = 0; j < sh_slot.size() / 16; ++j)
+            for (int k = 0; k < 16; ++k) sh_slot[j * 16 + k] = slot_of[1][j * 32 + k];
     }
     hipError_t e = hipMalloc((void **)&ts->d_fragT_src, ts->tt.fragT.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&ts->d_fragT, ts->tt.fragT.size() * sizeof(uint16_t));
@@ -1002,6 +1010,8 @@ static int ensure_train_state(mnf_field_t f) {
     if (e == hipSuccess) e = hipMemcpy(ts->d_fragT_src, ts->tt.fragT.data(), ts->tt.fragT.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ts->d_jobs, ts->tt.jobs.data(), ts->tt.jobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&ts->d_bin_cursors, (size_t)16 * kMaxBins * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&ts->d_sh_slot, sh_slot.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(ts->d_sh_slot, sh_slot.data(), sh_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     // side streams: the process-wide ones (common.h shared_side_stream), not a pair per train state
     ts->side = shared_side_stream(0);
     ts->side2 = shared_side_stream(1);
@@ -1030,6 +1040,7 @@ void free_train_state_impl(mnf_field_t f) {
     if (ts->d_qtable) (void)hipFree(ts->d_qtable);
     if (ts->d_partials) (void)hipFree(ts->d_partials);
     if (ts->d_bin_cursors) (void)hipFree(ts->d_bin_cursors);
+    if (ts->d_sh_slot) (void)hipFree(ts->d_sh_slot);
     if (ts->ev_fork) (void)hipEventDestroy(ts->ev_fork);
     if (ts->ev_join) (void)hipEventDestroy(ts->ev_join);
     for (int c = 0; c < 4; ++c) if (ts->ev_chunk[c]) (void)hipEventDestroy(ts->ev_chunk[c]);
@@ -1093,6 +1104,16 @@ int64_t train_workspace_bytes_impl(mnf_field_t f, int64_t n) {
     TrainTables tt;
     if (!tables_for(f->cfg.neurons, f->cfg.layers, f->cfg.num_semantic_classes, tt)) return -1;
     return carve_train(tt, f, nullptr, n).bytes;
+}
+
+// The parts of a train workspace the input gradients read (inputgrad.hip), as the last backward on this handle left them.  No HIP call.
+int input_grad_view_impl(mnf_field_t f, void *workspace, int64_t n, InputGradView &view) {
+    TrainState *ts = reinterpret_cast<TrainState *>(f->train_state);
+    MNF_REQUIRE(ts, "field_backward_inputs: no train forward or backward has run on this handle (call mnf_field_backward first)");
+    const WsView v = carve_train(ts->tt, f, workspace, n);
+    view.act = v.act; view.dX = v.dX; view.xn = v.xn; view.Np = v.Np;
+    view.rows = ts->tt.rows; view.row_dZr1 = ts->tt.row_dZr1; view.sh_slot = ts->d_sh_slot;
+    return MNF_OK;
 }
 
 int forward_train_impl(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream, bool deterministic) {

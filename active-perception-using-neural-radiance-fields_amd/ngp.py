@@ -35,10 +35,41 @@ def _xavier_uniform_(flat: torch.Tensor, shapes, gen: torch.Generator):
     return k
 
 
+def _field_backward(ctx, g_rgb, g_sigma, g_sem, want_params, dirs, want_pos, want_dir):
+    """The backward both autograd nodes share: `mnf_field_backward` on the node's workspace, then — only when an input gradient is asked for —
+    `mnf_field_backward_inputs` on the same workspace.  -> (d_pos [n,3] | None, d_dir [n,3] | None, g_base, g_head, g_sem), a parameter gradient
+    None where `want_params` says it is not needed.  With frozen parameters the parameter gradients are still computed (into scratch) and dropped:
+    the input gradients read what that backward leaves in the workspace."""
+    lib = L.load_library()
+    module = ctx.module
+    pos, rgb, sigma = ctx.saved_tensors[:3]
+    dev = pos.device
+    h = module._handle
+    g_base = torch.empty_like(module.mlp_base.params)
+    g_head = torch.empty_like(module.mlp_head.params)
+    g_s = torch.empty_like(module.mlp_sem.params)
+    zeros = lambda g, shape: torch.zeros(shape, device=dev) if g is None else L.contig(g, torch.float32)
+    g_rgb, g_sigma = zeros(g_rgb, rgb.shape), zeros(g_sigma, sigma.shape)
+    g_sem = zeros(g_sem, (ctx.n, module.num_semantic_classes))
+    L.launch(lib.mnf_field_backward, h, L.ptr(pos), ctx.n, L.ptr(g_rgb), L.ptr(g_sigma), L.ptr(g_sem), L.ptr(rgb), L.ptr(sigma),
+                                   L.ptr(ctx.ws), ctx.nbytes, float(module.loss_scale), L.ptr(g_base), L.ptr(g_head), L.ptr(g_s))
+    d_pos = d_dir = None
+    if want_pos or want_dir:
+        d_pos = torch.zeros(ctx.n, 3, device=dev) if want_pos else None
+        d_dir = torch.zeros(ctx.n, 3, device=dev) if want_dir else None
+        if ctx.n:
+            L.launch(lib.mnf_field_backward_inputs, h, L.ptr(pos), L.ptr(dirs) if want_dir else None, ctx.n, L.ptr(ctx.ws), ctx.nbytes,
+                     float(module.loss_scale), L.ptr(d_pos), L.ptr(d_dir))
+    ctx.ws = None
+    return (d_pos, d_dir) + tuple(g if w else None for g, w in zip((g_base, g_head, g_s), want_params))
+
+
 class _FieldFunction(torch.autograd.Function):
     """Differentiable field evaluation: what `loss.backward()` reaches inside tiny-cuda-nn in the reference
     (scripts/pipeline.py:518).  Forward keeps the activations in a workspace; backward returns dL/d(params) for the
-    three flat parameter vectors (positions and directions get no gradient, as in the reference's use)."""
+    three flat parameter vectors and, when `pos` / `dirs` require a gradient, dL/d(positions) / dL/d(directions) as tiny-cuda-nn's
+    input gradient does (`mnf_field_backward_inputs`; nothing more is launched when neither asks).  With frozen parameters the parameter
+    gradients are still computed into scratch and dropped."""
 
     @staticmethod
     def forward(ctx, module, pos, dirs, p_base, p_head, p_sem):
@@ -54,31 +85,20 @@ class _FieldFunction(torch.autograd.Function):
             L.launch(lib.mnf_field_forward_train, h, L.ptr(pos), L.ptr(dirs), n, L.ptr(rgb), L.ptr(sigma), L.ptr(sem), L.ptr(ws),
                                                 nbytes)
         ctx.module, ctx.ws, ctx.nbytes, ctx.n = module, ws, nbytes, n
-        ctx.save_for_backward(pos, rgb, sigma)
+        ctx.save_for_backward(pos, rgb, sigma, dirs)
         return rgb, sigma, sem
 
     @staticmethod
     def backward(ctx, g_rgb, g_sigma, g_sem):
-        lib = L.load_library()
-        module = ctx.module
-        pos, rgb, sigma = ctx.saved_tensors
-        dev = pos.device
-        h = module._handle
-        g_base = torch.empty_like(module.mlp_base.params)
-        g_head = torch.empty_like(module.mlp_head.params)
-        g_s = torch.empty_like(module.mlp_sem.params)
-        zeros = lambda g, shape: torch.zeros(shape, device=dev) if g is None else L.contig(g, torch.float32)
-        g_rgb, g_sigma = zeros(g_rgb, rgb.shape), zeros(g_sigma, sigma.shape)
-        g_sem = zeros(g_sem, (ctx.n, module.num_semantic_classes))
-        L.launch(lib.mnf_field_backward, h, L.ptr(pos), ctx.n, L.ptr(g_rgb), L.ptr(g_sigma), L.ptr(g_sem), L.ptr(rgb), L.ptr(sigma),
-                                       L.ptr(ctx.ws), ctx.nbytes, float(module.loss_scale), L.ptr(g_base), L.ptr(g_head), L.ptr(g_s))
-        ctx.ws = None
-        return None, None, None, g_base, g_head, g_s
+        need = ctx.needs_input_grad
+        return (None,) + _field_backward(ctx, g_rgb, g_sigma, g_sem, need[3:6], ctx.saved_tensors[3], need[1], need[2])
 
 
 class _FieldSamplesFunction(torch.autograd.Function):
     """`_FieldFunction` for packed samples given as (ray, t_start, t_end): the closure of utils.py:122-137 (ray gathers, `origins + dirs * (t_starts + t_ends) / 2`)
-    happens inside the forward kernel (`mnf_field_forward_train_samples`), which also leaves the positions the backward's hash-table scatter reads."""
+    happens inside the forward kernel (`mnf_field_forward_train_samples`), which also leaves the positions the backward's hash-table scatter reads.
+    When `rays_o` / `rays_d` require a gradient the per-sample input gradients are summed per ray by `mnf_ray_input_gradients` over the run bounds of
+    `ray_indices`: the samples must be grouped by ray, as the sampler returns them.  `t_starts` / `t_ends` get no gradient."""
 
     @staticmethod
     def forward(ctx, module, rays_o, rays_d, ray_indices, t_starts, t_ends, p_base, p_head, p_sem):
@@ -95,12 +115,35 @@ class _FieldSamplesFunction(torch.autograd.Function):
             L.launch(lib.mnf_field_forward_train_samples, h, L.ptr(rays_o), L.ptr(rays_d), L.ptr(ray_indices), L.ptr(t_starts), L.ptr(t_ends), n,
                      L.ptr(rgb), L.ptr(sigma), L.ptr(sem), L.ptr(pos), L.ptr(ws), nbytes)
         ctx.module, ctx.ws, ctx.nbytes, ctx.n = module, ws, nbytes, n
-        ctx.save_for_backward(pos, rgb, sigma)
+        ctx.n_rays = rays_o.shape[0]
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ctx.save_for_backward(pos, rgb, sigma, rays_d, ray_indices, t_starts, t_ends)
+        else:
+            ctx.save_for_backward(pos, rgb, sigma)
         return rgb, sigma, sem
 
     @staticmethod
     def backward(ctx, g_rgb, g_sigma, g_sem):
-        return (None, None, None, None, None, None) + _FieldFunction.backward(ctx, g_rgb, g_sigma, g_sem)[3:]
+        need = ctx.needs_input_grad
+        want_o, want_d = need[1], need[2]
+        dirs = None
+        if want_d:
+            rays_d, ray_indices = ctx.saved_tensors[3:5]
+            dirs = rays_d[ray_indices].contiguous()      # the per-sample directions the forward kernel gathered
+        d_pos, d_dir, *g_params = _field_backward(ctx, g_rgb, g_sigma, g_sem, need[6:9], dirs, want_o or want_d, want_d)
+        g_o = g_d = None
+        if want_o or want_d:
+            from . import nerfacc as NA
+            _, ray_indices, t_starts, t_ends = ctx.saved_tensors[3:7]
+            dev, R = d_pos.device, ctx.n_rays
+            g_o = torch.zeros(R, 3, device=dev) if want_o else None
+            g_d = torch.zeros(R, 3, device=dev) if want_d else None
+            if R and ctx.n:
+                packed = NA.pack_info_grouped(ray_indices, R)
+                starts, cnts = packed[:, 0].contiguous(), packed[:, 1].contiguous()
+                L.launch(L.load_library().mnf_ray_input_gradients, L.ptr(d_pos), L.ptr(d_dir), L.ptr(t_starts), L.ptr(t_ends), L.ptr(starts), L.ptr(cnts),
+                         R, ctx.n, L.ptr(g_o), L.ptr(g_d))
+        return (None, g_o, g_d, None, None, None) + tuple(g_params)
 
 
 class RaySigmaFn:
@@ -279,12 +322,15 @@ class NGPRadianceField(torch.nn.Module):
         h = self._ensure_handle()
         L.require_gpu(positions, directions)
         shp = positions.shape[:-1]
+        if torch.is_grad_enabled() and (positions.requires_grad or directions.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # the inputs go in un-detached: a position or direction that requires a gradient gets one (tiny-cuda-nn's dL/d(input))
+            pos = L.contig(positions.reshape(-1, 3), torch.float32)
+            dirs = L.contig(directions.reshape(-1, 3), torch.float32)
+            rgb, sigma, sem = _FieldFunction.apply(self, pos, dirs, self.mlp_base.params, self.mlp_head.params, self.mlp_sem.params)
+            return rgb.view(*shp, 3), sigma.view(*shp, 1), sem.view(*shp, self.num_semantic_classes)
         pos = L.contig(positions.detach().reshape(-1, 3), torch.float32)
         dirs = L.contig(directions.detach().reshape(-1, 3), torch.float32)
         n = pos.shape[0]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            rgb, sigma, sem = _FieldFunction.apply(self, pos, dirs, self.mlp_base.params, self.mlp_head.params, self.mlp_sem.params)
-            return rgb.view(*shp, 3), sigma.view(*shp, 1), sem.view(*shp, self.num_semantic_classes)
         rgb = torch.empty(n, 3, device=pos.device, dtype=torch.float32)
         sigma = torch.empty(n, 1, device=pos.device, dtype=torch.float32)
         sem = torch.empty(n, self.num_semantic_classes, device=pos.device, dtype=torch.float32)
@@ -293,9 +339,11 @@ class NGPRadianceField(torch.nn.Module):
 
     def forward_samples_grad(self, rays_o, rays_d, ray_indices, t_starts, t_ends):
         """`forward(origins[ray_indices] + viewdirs[ray_indices] * (t_starts + t_ends)[:, None] / 2, viewdirs[ray_indices])` (utils.py:122-137) with the
-        gathers and the positions formed inside the kernel; differentiable w.r.t. the three parameter vectors -> (rgb [N,3], density [N,1], sem [N,C])."""
+        gathers and the positions formed inside the kernel; differentiable w.r.t. the three parameter vectors and w.r.t. `rays_o` / `rays_d` where they
+        require a gradient (not w.r.t. `t_starts` / `t_ends`) -> (rgb [N,3], density [N,1], sem [N,C]).  For the ray gradients the samples must be
+        grouped by ray (every sample of a ray next to each other), as the sampler returns them."""
         L.require_gpu(rays_o, rays_d, ray_indices, t_starts, t_ends)
-        o, d = L.contig(rays_o.detach(), torch.float32), L.contig(rays_d.detach(), torch.float32)
+        o, d = L.contig(rays_o, torch.float32), L.contig(rays_d, torch.float32)
         ri, ts, te = L.contig(ray_indices, torch.int64), L.contig(t_starts.detach(), torch.float32), L.contig(t_ends.detach(), torch.float32)
         return _FieldSamplesFunction.apply(self, o, d, ri, ts, te, self.mlp_base.params, self.mlp_head.params, self.mlp_sem.params)
 

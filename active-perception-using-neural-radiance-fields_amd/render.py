@@ -227,14 +227,16 @@ _CompositeTrain = NA._CompositeTrain     # csrc/composite_train.hip behind autog
 
 
 def sem_rendering(radiance_field, rays: Rays, t_starts, t_ends, ray_indices, n_rays, render_bkgd=None):
-    """utils.py:362-461 on packed samples.  With autograd enabled the field is evaluated through its differentiable forward — the closure of
-    utils.py:122-137 inside the kernel (`forward_samples_grad`), or in torch for a field without it or for rays / distances that themselves want
-    gradients (none come back through the field, as in the reference) — and composited by `_CompositeTrain`; otherwise the fused no-grad kernel."""
+    """utils.py:362-461 on packed samples.  With autograd enabled and a parameter — or, for a field with `forward_samples_grad`, `rays.origins` /
+    `rays.viewdirs` — requiring a gradient, the field is evaluated through its differentiable forward: the closure of utils.py:122-137 inside the kernel
+    (`forward_samples_grad`, which also returns the gradients of the rays), or in torch for a field without it or for distances that themselves want
+    gradients; the result is composited by `_CompositeTrain`.  Otherwise the fused no-grad kernel."""
     C = radiance_field.num_semantic_classes
     dev = t_starts.device
-    differentiable = torch.is_grad_enabled() and any(p.requires_grad for p in radiance_field.parameters())
-    if t_starts.shape[0] != 0 and differentiable and hasattr(radiance_field, "forward_samples_grad") and not (
-            rays.origins.requires_grad or rays.viewdirs.requires_grad or t_starts.requires_grad or t_ends.requires_grad):
+    in_kernel = hasattr(radiance_field, "forward_samples_grad")
+    differentiable = torch.is_grad_enabled() and (any(p.requires_grad for p in radiance_field.parameters())
+                                                  or (in_kernel and (rays.origins.requires_grad or rays.viewdirs.requires_grad)))
+    if t_starts.shape[0] != 0 and differentiable and in_kernel and not (t_starts.requires_grad or t_ends.requires_grad):
         rgbs, sigmas, sems = radiance_field.forward_samples_grad(rays.origins, rays.viewdirs, ray_indices, t_starts, t_ends)
         sigmas = sigmas.squeeze(-1)
     elif t_starts.shape[0] != 0 and differentiable:
@@ -283,6 +285,26 @@ def render_image_with_occgrid_with_depth_guide(radiance_field, estimator, rays: 
     colors, opacities, depths, semantics = (torch.cat([r[k] for r in results], 0) for k in range(4))
     shp = tuple(rays_shape[:-1])
     return colors.view(*shp, -1), opacities.view(*shp, -1), depths.view(*shp, -1), semantics.view(*shp, -1), sum(r[4] for r in results)
+
+
+def transform_rays(rays: Rays, rotvec: torch.Tensor, trans: torch.Tensor) -> Rays:
+    """Rays under the rigid motion a pose refiner optimises, as a 6-vector (rotvec [3] axis-angle, trans [3]): directions are rotated by the Rodrigues
+    matrix R = I + a K + b K^2 of `rotvec` (a = sin t / t, b = (1 - cos t) / t^2, t = |rotvec|; below t^2 = 1e-6 their Taylor series, so value and
+    gradient are finite at rotvec = 0), origins are rotated about the rays' common origin (their mean) and translated.  Pure torch, differentiable with
+    respect to `rotvec`, `trans` and the rays; any device."""
+    o, d = rays.origins, rays.viewdirs
+    rotvec, trans = rotvec.to(d).reshape(3), trans.to(o).reshape(3)
+    t2 = (rotvec * rotvec).sum()
+    small = t2 < 1e-6
+    t2s = torch.where(small, torch.ones_like(t2), t2)      # the branch not taken must not put sqrt'(0) into the gradient
+    t = torch.sqrt(t2s)
+    a = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, torch.sin(t) / t)
+    b = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, (1.0 - torch.cos(t)) / t2s)
+    zero = torch.zeros_like(t2)
+    K = torch.stack([torch.stack([zero, -rotvec[2], rotvec[1]]), torch.stack([rotvec[2], zero, -rotvec[0]]), torch.stack([-rotvec[1], rotvec[0], zero])])
+    R = torch.eye(3, dtype=d.dtype, device=d.device) + a * K + b * (K @ K)
+    centre = o.detach().reshape(-1, 3).mean(0)
+    return Rays((o - centre) @ R.T + centre + trans, d @ R.T)
 
 
 def allreduce_gradients(parameters, group=None, skip=None):
@@ -770,7 +792,8 @@ def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float 
     render beyond its sample bounds is repeated with larger ones (it is pure).  More than four occupancy levels, or a ray past the sampler's scratch row, hand
     over to `render_image_with_occgrid_with_depth_guide`; the hand-over follows `radiance_field.training` as the drop-in does: `stratified=False` is honoured
     (the field is put into eval mode for the call), `stratified=True` on a field in eval mode is not, and the drop-in has no `early_stop_eps`, `seed` or
-    `deterministic` to pass on.
+    `deterministic` to pass on.  So does a call whose `rays.origins` or `rays.viewdirs` requires a gradient (with autograd on): the drop-in returns the ray
+    gradients, `mnf_train_render_backward` has no form that does.
     One backward per render, and the parameters must not change between the two (both raise `MnfError`).  Under `torch.no_grad()`, or with no parameter
     requiring a gradient, nothing is kept for a backward.  `latest_train_render(radiance_field)` has the device counters and the skip flag."""
     _LAST_RENDER.pop(radiance_field, None)
@@ -789,6 +812,8 @@ def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float 
 
     if estimator.levels > 4 or rays.origins.numel() == 0:
         return hand_over()
+    if torch.is_grad_enabled() and (rays.origins.requires_grad or rays.viewdirs.requires_grad):
+        return hand_over()      # gradients of the rays: the drop-in delivers them (`sem_rendering`), the fused backward has no ray-gradient form
     st, seed = _train_state(radiance_field), _step_seed(None, seed)      # one draw per render, whatever the number of attempts
     differentiable = torch.is_grad_enabled() and any(p_.requires_grad for p_ in radiance_field.parameters())
     opts_kw = dict(near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,

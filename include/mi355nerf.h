@@ -389,6 +389,32 @@ int mnf_field_forward_train_samples(mnf_field_t f, const float *rays_o, const fl
                                     float *sem, float *positions_out, void *workspace, int64_t workspace_bytes,
                                     mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- training: gradients with respect to the field's inputs
+ * tiny-cuda-nn returns dL/d(input) of its encodings and networks behind `loss.backward()` (scripts/pipeline.py:518; the modules of
+ * perception/models/radiance_fields/ngp.py:123-169): the gradient a pose refiner needs with the parameters frozen.
+ *
+ * mnf_field_backward_inputs replaces that input gradient for NGPRadianceField.forward: d_positions [n,3] and / or d_directions [n,3]
+ * (either may be NULL, fp32, overwritten) from what mnf_field_backward left in `workspace`.  Call it after mnf_field_backward with the
+ * same f, n, workspace and loss_scale; nothing in between may write the workspace or reload weights (the head weights are the handle's
+ * own 16-bit copies).  It only reads the workspace: any number of calls, the same workspace gives the same bits.  The position gradient
+ * is that of the fp32 trilinear blend whatever blend_fp16 says, the aabb selector contributes nothing.  `positions` is not read (the
+ * workspace holds them normalised) and may be NULL; `directions` [n,3] may be NULL when d_directions is.
+ * Both outputs NULL, n < 0, loss_scale <= 0 or d_directions without directions return MNF_ERR_INVALID, n == 0 returns MNF_OK, a
+ * workspace smaller than mnf_field_train_workspace_bytes(f, n) returns MNF_ERR_WORKSPACE: all before any HIP call.  Profile label:
+ * "field_input_grad".  Enqueues on `stream` and does not synchronise. */
+int mnf_field_backward_inputs(mnf_field_t f, const float *positions, const float *directions, int64_t n,
+                              void *workspace, int64_t workspace_bytes, float loss_scale,
+                              float *d_positions, float *d_directions, mnf_stream_t stream);
+/* The same tcnn input gradient carried on to the rays of packed samples grouped by ray (the closure of utils.py:122-137,
+ * positions = origins + dirs * (t_starts + t_ends) / 2, directions = dirs): g_rays_o[r] = sum_s d_positions[s],
+ * g_rays_d[r] = sum_s ((t_starts[s] + t_ends[s]) / 2 * d_positions[s] + d_directions[s]) over the samples
+ * chunk_starts[r] .. chunk_starts[r] + chunk_cnts[r] - 1 of ray r.  One wave per ray: lane L adds samples L, L + 64, ... in index
+ * order, the 64 partial sums are added by a fixed butterfly; fp32, no atomics, rays without samples get exact zeros.  d_directions may
+ * be NULL (position term only); one of g_rays_o / g_rays_d [n_rays,3] may be NULL.  Enqueues on `stream` and does not synchronise. */
+int mnf_ray_input_gradients(const float *d_positions, const float *d_directions, const float *t_starts, const float *t_ends,
+                            const int64_t *chunk_starts, const int64_t *chunk_cnts, int32_t n_rays, int64_t n_samples,
+                            float *g_rays_o, float *g_rays_d, mnf_stream_t stream);
+
 /* ---------------------------------------------------------------- one training iteration's forward + loss + backward
  * scripts/pipeline.py:472-518 for one model as ONE call: the train render `render_image_with_occgrid_with_depth_guide`
  * (perception/models/utils.py:63-219: occupancy sampling with stratified near planes, density pre-pass and visibility filter,
@@ -557,7 +583,7 @@ int mnf_planner_map(const uint8_t *binaries, int32_t n_members, int32_t res_x, i
 
 /* Optional in-library kernel timing for bench.py's roofline figures: between begin and end the library brackets its main
  * launches with hipEvent pairs on the launch stream, grouped by label: "field_render" (the fused field kernel of
- * mnf_render_test), "field_density", "field_forward", "field_train_forward", "dgrad", "wgrad", "hash_scatter",
+ * mnf_render_test), "field_density", "field_forward", "field_train_forward", "dgrad", "wgrad", "hash_scatter", "field_input_grad",
  * "composite_train_forward", "composite_train_backward", "sample_rays", "eval_views", "frames_views", "score_view_maps".  mnf_profile_end synchronises the events, sums
  * the milliseconds per label and returns the "field_render" totals; mnf_profile_query reads any label afterwards.
  * Process-wide (backward passes run on torch's autograd thread).  Not part of the reference surface. */

@@ -155,6 +155,9 @@ SIGNATURES = {
     "mnf_train_render_backward": (c_int32, [c_void_p, c_int32, POINTER(TrainOpts), c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                             c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                             c_void_p]),
+    "mnf_train_render_backward_rays": (c_int32, [c_void_p, c_int32, POINTER(TrainOpts), c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                                 c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "mnf_score_poses_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mnf_score_poses": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                   c_float, c_void_p, c_int64, POINTER(RenderOpts), c_void_p, c_void_p, c_int64, c_void_p]),

@@ -126,6 +126,21 @@ struct InputGradView {
     const int32_t *sh_slot;   // [W/2][16] device: index into d_frags
 };
 
+// The fused train render's ray gradients (inputgrad.hip train_render_ray_grad_kernel): what of the step's workspace the kernel reads beside the field's train
+// workspace, and where the sums go.
+struct RayGradIO {
+    const float *xn;                              // [n][3] aabb-normalised positions of the kept samples
+    const float *t_starts, *t_ends;               // [n]
+    const int64_t *kept_starts, *kept_cnts;       // [n_rays]
+    const int64_t *n_dev;                         // device: the surviving count the backward worked on
+    const int32_t *skip;                          // device: the step's skip flag
+    const float *rays_d;                          // [n_rays][3]; NULL without g_d
+    int32_t n_rays;
+    int64_t n;                                    // the sample arrays' bound (the field workspace was carved for it)
+    float loss_scale;
+    float *g_o, *g_d;                             // [n_rays][3] each, overwritten; either may be NULL
+};
+
 // dispatchers on the handle's operand type (defined once, in the fp16 translation units)
 void free_train_state(mnf_field_t f);
 int launch_field(mnf_field_t f, const FieldIO &io, bool density_only, hipStream_t stream, const TrainBuf *train = nullptr);
@@ -134,6 +149,7 @@ int forward_train(mnf_field_t f, const FieldIO &io, void *workspace, int64_t wor
 int backward(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_dev, const float *d_rgb, const float *d_density,
              const float *d_sem, const float *rgb, const float *density, void *workspace, int64_t workspace_bytes, float loss_scale,
              float *g_base, float *g_head, float *g_sem, bool zero_grads, bool positions_normalized, bool deterministic, hipStream_t stream);
+int train_render_ray_grad(mnf_field_t f, void *field_ws, const RayGradIO &io, hipStream_t stream);
 
 #define MNF_DECLARE_DT_IMPL(ns)                                                                                                      \
     namespace ns {                                                                                                                   \
@@ -151,6 +167,7 @@ int backward(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_
     int input_grad_view_impl(mnf_field_t f, void *workspace, int64_t n, InputGradView &view);                                        \
     int field_input_grad_impl(mnf_field_t f, const InputGradView &view, const float *directions, int64_t n, float loss_scale,       \
                               float *d_positions, float *d_directions, hipStream_t stream);                                          \
+    int train_render_ray_grad_impl(mnf_field_t f, void *field_ws, const RayGradIO &io, hipStream_t stream);                          \
     }
 MNF_DECLARE_DT_IMPL(f16)
 MNF_DECLARE_DT_IMPL(bf16)

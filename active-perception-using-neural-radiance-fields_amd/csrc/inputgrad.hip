@@ -5,9 +5,10 @@
 //                             dL/d(position) = trilinear derivative of the 16 hash levels applied to dX, and (optional)
 //                             dL/d(direction) = W1_head[:, 0:16]^T dZr1 through the closed-form Jacobian of the degree-4 SH.
 //   ray_input_grad_kernel     per ray, packed samples grouped by ray: g_o = sum d_pos, g_d = sum (t_mid * d_pos + d_dir).
+//   train_render_ray_grad_kernel   the two as one launch for the fused train render: from the step's workspace to g_o / g_d, one wave per ray.
 //
-// Both only read their inputs: no atomics, no cross-workgroup sums, the same inputs give the same bits.
-#include "field_dev.h"
+// All only read their inputs: no atomics, no cross-workgroup sums, the same inputs give the same bits.
+#include "inputgrad_dev.h"
 
 MNF_DT_BEGIN
 
@@ -28,41 +29,6 @@ struct InputGradArgs {
 };
 
 constexpr int kGradThreads = 256;     // one lane = one sample, a wave = one 64-sample tile of the workspace
-constexpr int kMaxHeadWidth = 64;     // W / 2 at W = 128
-#ifndef MNF_GRAD_LEVELS
-#define MNF_GRAD_LEVELS 4
-#endif
-// hash levels per group of gathers: 4 (the forward's group) = 234 VGPRs, two waves per SIMD; 2 = 126 VGPRs, four waves per SIMD, measured 4 % slower
-// (profiles/input_grad_levels_ab.txt)
-constexpr int kGradLevels = MNF_GRAD_LEVELS;
-static_assert(16 % kGradLevels == 0, "whole groups");
-
-// d(feature)/d(frac) of one level applied to the level's feature gradient g: with D[c] = dot(g, entry of corner c) (c = bx + 2 by + 4 bz)
-//   x: sum_{by,bz} wy wz (D[1,by,bz] - D[0,by,bz]), likewise y and z; times d(frac)/d(xn) = scale.  fp32 throughout, whatever the forward's blend
-// precision was (straight-through, as the oracle's).
-__device__ __forceinline__ void level_grad(const LevelMeta m, const float xn[3], const LevelPrep &p, const tab4 (&v)[8], const float4 g, float (&acc)[3]) {
-    float D[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        D[c] = __builtin_fmaf((float)v[c][3], g.w, __builtin_fmaf((float)v[c][2], g.z, __builtin_fmaf((float)v[c][1], g.y, (float)v[c][0] * g.x)));
-    // the fractions exactly as hash_prep formed them
-    const float px = __builtin_fmaf(m.scale, xn[0], 0.5f), py = __builtin_fmaf(m.scale, xn[1], 0.5f);
-    const float fx = px - floorf(px), fy = py - floorf(py);
-    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            gx = __builtin_fmaf(wy[a] * p.wz[b], D[1 + 2 * a + 4 * b] - D[2 * a + 4 * b], gx);      // a = by, b = bz
-            gy = __builtin_fmaf(wx[a] * p.wz[b], D[a + 2 + 4 * b] - D[a + 4 * b], gy);              // a = bx, b = bz
-            const float wxy = a ? p.wxy[b].y : p.wxy[b].x;                                          // a = bx, b = by
-            gz = __builtin_fmaf(wxy, D[a + 2 * b + 4] - D[a + 2 * b], gz);
-        }
-    acc[0] = __builtin_fmaf(m.scale, gx, acc[0]);
-    acc[1] = __builtin_fmaf(m.scale, gy, acc[1]);
-    acc[2] = __builtin_fmaf(m.scale, gz, acc[2]);
-}
 
 __global__ void __launch_bounds__(kGradThreads) field_input_grad_kernel(const InputGradArgs args) {
     __shared__ float s_w[kMaxHeadWidth * 16];      // W1_head[j][k], k < 16: every lane reads the same word (broadcast)
@@ -139,21 +105,8 @@ __global__ void __launch_bounds__(kGradThreads) field_input_grad_kernel(const In
                 for (int k = 1; k < 16; ++k) s[k] = __builtin_fmaf(s_w[(j0 + j) * 16 + k], z[j], s[k]);      // (k = 0: the constant harmonic)
         }
         if (valid) {
-            // the forward's argument (field_dev.h sh4): 2u - 1 with u = (d + 1) / 2, chain factor 1
-            const float x = ((args.dirs[3 * i] + 1.0f) / 2.0f) * 2.0f - 1.0f;
-            const float y = ((args.dirs[3 * i + 1] + 1.0f) / 2.0f) * 2.0f - 1.0f;
-            const float z = ((args.dirs[3 * i + 2] + 1.0f) / 2.0f) * 2.0f - 1.0f;
-            const float x2 = x * x, y2 = y * y, z2 = z * z;
-            constexpr float c1 = 0.48860251190291987f, c2 = 1.0925484305920792f, c3 = 0.94617469575755997f, c5 = 0.54627421529603959f,
-                            c6 = 0.59004358992664352f, c7 = 2.8906114426405538f, c8 = 0.45704579946446572f, c9 = 0.3731763325901154f,
-                            c10 = 1.4453057213202769f;
-            // Jacobian of the 16 polynomials of sh4, column by column
-            const float gx = -c1 * s[3] + c2 * y * s[4] - c2 * z * s[7] + 2.0f * c5 * x * s[8] - 6.0f * c6 * x * y * s[9] + c7 * y * z * s[10]
-                             + c8 * (1.0f - 5.0f * z2) * s[13] + 2.0f * c10 * x * z * s[14] + 3.0f * c6 * (y2 - x2) * s[15];
-            const float gy = -c1 * s[1] + c2 * x * s[4] - c2 * z * s[5] - 2.0f * c5 * y * s[8] + 3.0f * c6 * (y2 - x2) * s[9] + c7 * x * z * s[10]
-                             + c8 * (1.0f - 5.0f * z2) * s[11] - 2.0f * c10 * y * z * s[14] + 6.0f * c6 * x * y * s[15];
-            const float gz = c1 * s[2] - c2 * y * s[5] + 2.0f * c3 * z * s[6] - c2 * x * s[7] + c7 * x * y * s[10] - 10.0f * c8 * y * z * s[11]
-                             + c9 * (15.0f * z2 - 3.0f) * s[12] - 10.0f * c8 * x * z * s[13] + c10 * (x2 - y2) * s[14];
+            float gx, gy, gz;
+            sh4_jacobian_t(args.dirs + 3 * i, s, gx, gy, gz);
             args.d_dir[3 * i] = gx * args.inv_scale;
             args.d_dir[3 * i + 1] = gy * args.inv_scale;
             args.d_dir[3 * i + 2] = gz * args.inv_scale;
@@ -178,6 +131,175 @@ int field_input_grad_impl(mnf_field_t f, const InputGradView &view, const float 
         hipLaunchKernelGGL(field_input_grad_kernel, dim3((unsigned)ceil_div(n, kGradThreads)), dim3(kGradThreads), 0, stream, a);
     }
     return launch_status("field_input_grad_kernel");
+}
+
+// ---- the two kernels above as one, for the fused train render (trainstep.hip: mnf_train_render_backward_rays): from the step's workspace straight to the
+// per-ray sums, no per-sample array in between.
+// field_input_grad_kernel's two loops as functions.  (That kernel keeps them written out: called through these its register allocation changes, 234 -> 243
+// VGPRs, and its instruction stream is pinned.)
+// acc += sum over the 16 levels of level_grad, for the lane's sample at xn with its feature gradients at gsrc[level * Np] (dX, [16][Np][4]).
+// The forward's gathers, double-buffered as its prep[q] groups: kGradLevels levels per group, the next group's loads are issued before this one's
+// are consumed, so up to 2 x 8 x kGradLevels gathers are in flight per lane.  `in_box` is wave-uniform (hash_prep).
+__device__ __forceinline__ void levels_grad(const tab4 *table, const LevelsPtr lv, const float4 *gsrc, int64_t Np, const float xn[3], bool in_box,
+                                            float (&acc)[3]) {
+    LevelPrep prep[2][kGradLevels];
+    tab4 v[2][kGradLevels][8];
+    float4 g[2][kGradLevels];
+#pragma unroll
+    for (int q = 0; q < kGradLevels; ++q) {
+        hash_prep(level_meta(lv, q), xn, prep[0][q], in_box);
+        hash_load(table, prep[0][q], v[0][q]);
+        g[0][q] = gsrc[(int64_t)q * Np];
+    }
+#pragma unroll
+    for (int kb = 0; kb < 16 / kGradLevels; ++kb) {
+        const int cur = kb & 1, nxt = cur ^ 1;
+        if (kb + 1 < 16 / kGradLevels) {
+#pragma unroll
+            for (int q = 0; q < kGradLevels; ++q) {
+                const int l = kGradLevels * (kb + 1) + q;
+                hash_prep(level_meta(lv, l), xn, prep[nxt][q], in_box);
+                hash_load(table, prep[nxt][q], v[nxt][q]);
+                g[nxt][q] = gsrc[(int64_t)l * Np];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kGradLevels; ++q) level_grad(level_meta(lv, kGradLevels * kb + q), xn, prep[cur][q], v[cur][q], g[cur][q], acc);
+        // pin the group's arithmetic here: left free, the compiler sinks all 16 levels' sums behind the last gather and keeps every entry live
+        asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// s[k] += sum_j W1_head[j][k] dZr1[j] of the lane's sample for the 15 non-constant harmonics (k = 0: the constant one); `dz`: the sample's column in
+// row row_dZr1 of its activation tile (row j of the tile is 64 consecutive 16-bit values, one per lane), `s_w`: W1_head[j][k], k < 16, in LDS (every
+// lane reads the same word: broadcast)
+__device__ __forceinline__ void head_sh_sums(const half_t *dz, const float *s_w, int Wh, float (&s)[16]) {
+    for (int j0 = 0; j0 < Wh; j0 += 8) {
+        float z[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = (float)dz[(int64_t)(j0 + j) * 64];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int k = 1; k < 16; ++k) s[k] = __builtin_fmaf(s_w[(j0 + j) * 16 + k], z[j], s[k]);
+    }
+}
+
+struct RayGradArgs {
+    const tab4 *table;
+    const LevelMeta *levels;
+    const float *xn;              // [n][3] the kept samples' aabb-normalised positions (FieldIO::xn_out)
+    const float *dX;              // [16][Np][4]
+    int64_t Np, n;                // n: the arrays' bound (max_kept)
+    const half_t *act;
+    int32_t rows, row_dZr1, Wh;
+    const half_t *frags;
+    const int32_t *sh_slot;
+    const float *t_starts, *t_ends;                   // [n] kept
+    const int64_t *kept_starts, *kept_cnts;           // [n_rays] the rays' runs
+    const int64_t *n_dev;         // the surviving count the backward worked on (a cleared count: dX is stale, nothing is summed)
+    const int32_t *skip;          // the step's skip flag (raised: zeros)
+    const float *rays_d;          // [n_rays][3], only read with g_d
+    int32_t n_rays;
+    float inv_scale;
+    float inv_extent[3];
+    float *g_o, *g_d;             // [n_rays][3] each, either may be NULL
+};
+
+constexpr int kRayGradThreads = 256;  // four rays per workgroup
+
+// One wave per ray (ray_input_grad_kernel's shape).  Lane L takes the ray's kept samples L, L + 64, ... in index order: field_input_grad_kernel's position
+// gradient of each, added to the lane's partial sums of d_pos and t_mid d_pos; then, for g_d, the lane's partial sums of the 15 non-constant
+// s[k] = sum_j W1_head[j][k] dZr1[j] (a second pass: the 15 sums are not live beside the gathers).  A fixed butterfly (lane ^ 32, ^ 16, ... ^ 1) adds the 64
+// partial sums, and the SH Jacobian — linear in s, and every sample of a ray shares the ray's direction — is applied once per ray.  No atomics; the order of
+// every sum depends on nothing but the ray's sample count.
+__global__ void __launch_bounds__(kRayGradThreads) train_render_ray_grad_kernel(const RayGradArgs args) {
+    __shared__ float s_w[kMaxHeadWidth * 16];
+    const bool want_dir = args.g_d != nullptr;     // uniform
+    if (want_dir) {
+        for (int i = threadIdx.x; i < args.Wh * 16; i += kRayGradThreads) {
+            const int32_t s = args.sh_slot[i];
+            s_w[i] = s >= 0 ? (float)args.frags[s] : 0.0f;
+        }
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t ray = (int64_t)blockIdx.x * (kRayGradThreads / 64) + (threadIdx.x >> 6);
+    if (ray >= args.n_rays) return;
+    int64_t s0 = args.kept_starts[ray], cnt = args.kept_cnts[ray];
+    if (s0 < 0 || cnt < 0) { s0 = 0; cnt = 0; }
+    int64_t lim = args.n_dev[0] < args.n ? args.n_dev[0] : args.n;      // never past the arrays, and never into what the backward did not write
+    if (args.skip[0] > 0) lim = 0;
+    const int64_t s1 = s0 + cnt < lim ? s0 + cnt : lim;
+    const int c = __builtin_amdgcn_readfirstlane(s1 > s0 ? (int)(s1 - s0) : 0);      // the ray's samples that count (wave-uniform)
+
+    float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
+    for (int base = 0; base < c; base += 64) {
+        const bool valid = base + lane < c;
+        const int64_t i = s0 + (valid ? base + lane : c - 1);            // lanes past the run shadow its last sample and add nothing
+        float xn[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) xn[d] = args.xn[3 * i + d];
+        const bool inside = xn[0] > 0.0f && xn[0] < 1.0f && xn[1] > 0.0f && xn[1] < 1.0f && xn[2] > 0.0f && xn[2] < 1.0f;
+        const bool in_box = __ballot(!inside) == 0ull;
+        const LevelsPtr lv = levels_here(args.levels);
+        float acc[3] = {0.f, 0.f, 0.f};
+        levels_grad(args.table, lv, reinterpret_cast<const float4 *>(args.dX) + i, args.Np, xn, in_box, acc);
+        const float tm = (args.t_starts[i] + args.t_ends[i]) / 2.0f;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float p = valid ? acc[d] * args.inv_extent[d] : 0.0f;
+            so[d] += p;
+            sd[d] = __builtin_fmaf(tm, p, sd[d]);
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            so[d] += __shfl_xor(so[d], m, 64);
+            sd[d] += __shfl_xor(sd[d], m, 64);
+        }
+    if (args.g_o && lane < 3) args.g_o[3 * ray + lane] = lane == 0 ? so[0] : (lane == 1 ? so[1] : so[2]);
+    if (!want_dir) return;
+
+    float s[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s[k] = 0.0f;
+    for (int base = lane; base < c; base += 64) {
+        const int64_t i = s0 + base;
+        head_sh_sums(args.act + ((i >> 6) * args.rows + args.row_dZr1) * 64 + (i & 63), s_w, args.Wh, s);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+        for (int k = 1; k < 16; ++k) s[k] += __shfl_xor(s[k], m, 64);
+    float gx, gy, gz;
+    sh4_jacobian_t(args.rays_d + 3 * ray, s, gx, gy, gz);
+    if (lane < 3) args.g_d[3 * ray + lane] = lane == 0 ? sd[0] + gx * args.inv_scale : (lane == 1 ? sd[1] + gy * args.inv_scale : sd[2] + gz * args.inv_scale);
+}
+
+int train_render_ray_grad_impl(mnf_field_t f, void *field_ws, const RayGradIO &io, hipStream_t stream) {
+    InputGradView view;
+    const int rc = input_grad_view_impl(f, field_ws, io.n, view);
+    if (rc) return rc;
+    RayGradArgs a;
+    a.table = reinterpret_cast<const tab4 *>(f->d_table);
+    a.levels = reinterpret_cast<const LevelMeta *>(reinterpret_cast<const char *>(f->d_frags) + (size_t)f->shape.blocks_total * 1024);
+    a.xn = io.xn; a.dX = view.dX; a.Np = view.Np; a.n = io.n;
+    a.act = reinterpret_cast<const half_t *>(view.act); a.rows = view.rows; a.row_dZr1 = view.row_dZr1; a.Wh = f->cfg.neurons / 2;
+    a.frags = reinterpret_cast<const half_t *>(f->d_frags); a.sh_slot = view.sh_slot;
+    a.t_starts = io.t_starts; a.t_ends = io.t_ends; a.kept_starts = io.kept_starts; a.kept_cnts = io.kept_cnts; a.n_dev = io.n_dev; a.skip = io.skip;
+    a.rays_d = io.rays_d; a.n_rays = io.n_rays; a.inv_scale = 1.0f / io.loss_scale;
+    for (int d = 0; d < 3; ++d) a.inv_extent[d] = 1.0f / (f->cfg.aabb[3 + d] - f->cfg.aabb[d]);
+    a.g_o = io.g_o; a.g_d = io.g_d;
+    MNF_REQUIRE(a.Wh <= kMaxHeadWidth, "train_render_backward_rays: unsupported width");
+    {
+        ProfScope ps("train_render_ray_grad", stream);
+        hipLaunchKernelGGL(train_render_ray_grad_kernel, dim3((unsigned)ceil_div(io.n_rays, kRayGradThreads / 64)), dim3(kRayGradThreads), 0, stream, a);
+    }
+    return launch_status("train_render_ray_grad_kernel");
 }
 
 MNF_DT_END
@@ -218,6 +340,10 @@ __global__ void __launch_bounds__(256) ray_input_grad_kernel(const float *__rest
         if (g_o) g_o[3 * ray + lane] = lane == 0 ? so[0] : (lane == 1 ? so[1] : so[2]);
         if (g_d) g_d[3 * ray + lane] = lane == 0 ? sd[0] : (lane == 1 ? sd[1] : sd[2]);
     }
+}
+
+int train_render_ray_grad(mnf_field_t f, void *field_ws, const RayGradIO &io, hipStream_t stream) {
+    return f->cfg.mfma_bf16 ? bf16::train_render_ray_grad_impl(f, field_ws, io, stream) : f16::train_render_ray_grad_impl(f, field_ws, io, stream);
 }
 
 }  // namespace mnf

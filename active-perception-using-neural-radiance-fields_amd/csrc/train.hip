@@ -1139,8 +1139,11 @@ int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_
     const bool factored = take_factored_output_gradient(fg);      // first of all: taken (and cleared) on every path out of this call
     MNF_REQUIRE(f && f->params_loaded, "field_backward: parameters not loaded");
     MNF_REQUIRE(n >= 0 && loss_scale > 0.f, "field_backward: bad arguments");
-    MNF_REQUIRE(g_base && g_head && g_sem, "field_backward: null gradient buffer");
-    if (zero_grads) {
+    // all three NULL: no parameter gradients (the fused train render with frozen parameters, mnf_train_render_backward_rays): the output gradients and dgrad
+    // run as ever and leave dX and the activation gradients in the workspace; no weight gradients, no hash scatter, no side stream
+    const bool frozen = !g_base && !g_head && !g_sem;
+    MNF_REQUIRE(frozen || (g_base && g_head && g_sem), "field_backward: null gradient buffer");
+    if (zero_grads && !frozen) {
         MNF_HIP(hipMemsetAsync(g_base, 0, (size_t)f->n_base * 4, s));
         MNF_HIP(hipMemsetAsync(g_head, 0, (size_t)f->n_head * 4, s));
         MNF_HIP(hipMemsetAsync(g_sem, 0, (size_t)f->n_sem * 4, s));
@@ -1164,9 +1167,11 @@ int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_
         repl_entries += f->levels[l].size;
         repl_levels = l + 1;
     }
-    MNF_HIP(hipEventRecord(ts->ev_entry, s));
-    MNF_HIP(hipStreamWaitEvent(ts->side, ts->ev_entry, 0));
-    if (repl_levels && !deterministic) MNF_HIP(hipMemsetAsync(v.repl, 0, (size_t)kReplicas * repl_entries * 4 * sizeof(float), ts->side));
+    if (!frozen) {
+        MNF_HIP(hipEventRecord(ts->ev_entry, s));
+        MNF_HIP(hipStreamWaitEvent(ts->side, ts->ev_entry, 0));
+    }
+    if (repl_levels && !deterministic && !frozen) MNF_HIP(hipMemsetAsync(v.repl, 0, (size_t)kReplicas * repl_entries * 4 * sizeof(float), ts->side));
     // transposed fp16 weight fragments from the handle's forward fragments (the parameters of the last set_params)
     const int64_t n_frag = (int64_t)ts->tt.fragT.size();
     hipLaunchKernelGGL(gather_fragsT_kernel, dim3((unsigned)ceil_div(n_frag > 16 * kMaxBins ? n_frag : (int64_t)16 * kMaxBins, 256)), dim3(256), 0, s, ts->d_fragT_src,
@@ -1186,6 +1191,7 @@ int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_
     // measured (profiles/r04_bwd_chunks.txt): 5.77 / 5.52 / 5.60 ms per step with 1 / 2 / 4 ranges.
     int n_chunks = (!deterministic && n >= ((int64_t)1 << 18)) ? 2 : 1;
     if (chunks_env >= 1 && chunks_env <= 4 && !deterministic) n_chunks = chunks_env;
+    if (frozen) n_chunks = 1;      // (the ranges exist to start a scatter early: without one, one launch)
     if (!positions_normalized) {   // (the train step's forward hands over normalised positions already: FieldIO::xn_out)
         const float *ab = f->cfg.aabb;
         const int64_t blocks = ceil_div(3 * n, 256);
@@ -1209,12 +1215,12 @@ int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_
         MNF_CASE(64, 1) MNF_CASE(64, 2) MNF_CASE(64, 3) MNF_CASE(64, 4)
 #endif
 #undef MNF_CASE
-        MNF_HIP(hipEventRecord(ts->ev_chunk[c], s));      // ---- fork point of range c: its scatter may start (the weight gradients stay on the caller's stream)
+        if (!frozen) MNF_HIP(hipEventRecord(ts->ev_chunk[c], s));      // ---- fork point of range c: its scatter may start (the weight gradients stay on the caller's stream)
     }
     prof_stop(prof_dgrad, s);
     MNF_REQUIRE(ok, "field_backward: unsupported shape");
     rc = launch_status("dgrad_kernel");
-    if (rc) return rc;
+    if (rc || frozen) return rc;
     hipStream_t ss = ts->side;
     // weight gradients
     const int n_groups = (int)ts->tt.groups.size();
@@ -1595,6 +1601,7 @@ extern "C" int mnf_field_backward(mnf_field_t f, const float *positions, int64_t
                                   void *workspace, int64_t workspace_bytes, float loss_scale,
                                   float *g_base, float *g_head, float *g_sem, mnf_stream_t stream) {
     MNF_REQUIRE(f, "field_backward: null handle");
+    MNF_REQUIRE(g_base && g_head && g_sem, "field_backward: null gradient buffer");
     return backward(f, positions, n, nullptr, d_rgb, d_density, d_sem, rgb, density, workspace, workspace_bytes, loss_scale, g_base, g_head, g_sem, true,
                     false, false, as_stream(stream));
 }

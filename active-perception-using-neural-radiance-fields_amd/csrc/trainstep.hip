@@ -718,6 +718,21 @@ extern "C" int mnf_train_render_forward(mnf_field_t f, const uint8_t *binaries, 
     return launch_status("outputs_kernel");
 }
 
+// What the two backward entry points share behind their argument checks: the head (gradients_in_kernel) and step_backward
+static int render_backward(mnf_field_t f, const StepWs &w, int32_t n_rays, const mnf_train_opts *opts, const GradIn &i_rgb, const GradIn &i_acc, const GradIn &i_dep,
+                           const GradIn &i_sem, float *g_base, float *g_head, float *g_sem_params, int64_t *counts_dev, int32_t *skip_dev, int64_t max_kept,
+                           mnf_stream_t stream) {
+    int64_t *eff = w.totals + 4;
+    const float *bk = opts->render_bkgd_dev;      // as the forward chose it: the caller's device colour, or the by-value one the forward left in the workspace
+    if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) bk = w.alpha_thre + 8;
+    const GradFills z = {g_base, g_head, g_sem_params, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem};
+    hipLaunchKernelGGL(gradients_in_kernel, dim3(fill_blocks((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), n_rays, f->cfg.num_semantic_classes, i_rgb, i_acc,
+                       i_dep, i_sem, w.g_rgb, w.g_acc, w.g_dep, w.g_sem, z, counts_dev, skip_dev, eff, render_ticket(w));
+    int rc = launch_status("gradients_in_kernel");
+    if (rc) return rc;
+    return step_backward(f, w, n_rays, opts, bk, w.g_acc, eff, max_kept, g_base, g_head, g_sem_params, stream);
+}
+
 extern "C" int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *g_rgb, int64_t g_rgb_row_stride,
                                          int64_t g_rgb_col_stride, const float *g_acc, int64_t g_acc_row_stride, const float *g_depth, int64_t g_depth_row_stride,
                                          const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base, float *g_head, float *g_sem_params,
@@ -731,16 +746,39 @@ extern "C" int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mn
     MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0, "train_render_backward: bad sizes");
     const StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
     if (workspace_bytes < w.bytes) { set_error("train_render_backward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
-    int64_t *eff = w.totals + 4;
-    const float *bk = opts->render_bkgd_dev;      // as the forward chose it: the caller's device colour, or the by-value one the forward left in the workspace
-    if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) bk = w.alpha_thre + 8;
-    const GradFills z = {g_base, g_head, g_sem_params, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem};
-    hipLaunchKernelGGL(gradients_in_kernel, dim3(fill_blocks((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), n_rays, f->cfg.num_semantic_classes,
-                       GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
-                       GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, w.g_rgb, w.g_acc, w.g_dep, w.g_sem, z, counts_dev, skip_dev, eff, render_ticket(w));
-    int rc = launch_status("gradients_in_kernel");
+    return render_backward(f, w, n_rays, opts, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
+                           GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params, counts_dev, skip_dev, max_kept, stream);
+}
+
+// mnf_train_render_backward, then the ray gradients from what it left in the workspace (inputgrad.hip).  The three parameter pointers all NULL: the parameters are
+// frozen — the head fills nothing and the field's backward stops behind dgrad (train.hip backward_impl).
+extern "C" int mnf_train_render_backward_rays(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *rays_d, const float *g_rgb,
+                                              int64_t g_rgb_row_stride, int64_t g_rgb_col_stride, const float *g_acc, int64_t g_acc_row_stride, const float *g_depth,
+                                              int64_t g_depth_row_stride, const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base,
+                                              float *g_head, float *g_sem_params, float *g_rays_o, float *g_rays_d, int64_t *counts_dev, int32_t *skip_dev,
+                                              int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    MNF_REQUIRE(f && f->params_loaded && opts && counts_dev && skip_dev, "train_render_backward_rays: bad handle or options");
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_backward_rays: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
+                opts->struct_size, sizeof(mnf_train_opts));
+    MNF_REQUIRE(!opts->presampled, "train_render_backward_rays: opts->presampled must be NULL");
+    MNF_REQUIRE(g_rays_o || g_rays_d, "train_render_backward_rays: no ray gradient asked for (mnf_train_render_backward is the call without)");
+    MNF_REQUIRE(!g_rays_d || rays_d, "train_render_backward_rays: g_rays_d needs rays_d, the directions the forward was given");
+    const bool frozen = !g_base && !g_head && !g_sem_params;
+    MNF_REQUIRE(frozen || (g_base && g_head && g_sem_params), "train_render_backward_rays: the three parameter gradients are given together, or all NULL (frozen)");
+    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->loss_scale > 0.f, "train_render_backward_rays: bad sizes");
+    const StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
+    if (!workspace || workspace_bytes < w.bytes) {
+        set_error("train_render_backward_rays: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes);
+        return MNF_ERR_WORKSPACE;
+    }
+    int rc = render_backward(f, w, n_rays, opts, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
+                             GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params, counts_dev, skip_dev, max_kept, stream);
     if (rc) return rc;
-    return step_backward(f, w, n_rays, opts, bk, w.g_acc, eff, max_kept, g_base, g_head, g_sem_params, stream);
+    RayGradIO io = {};
+    io.xn = w.k_pos; io.t_starts = w.k_ts; io.t_ends = w.k_te; io.kept_starts = w.kept_starts; io.kept_cnts = w.kept_cnts;
+    io.n_dev = w.totals + 5; io.skip = skip_dev; io.rays_d = rays_d; io.n_rays = n_rays; io.n = max_kept; io.loss_scale = opts->loss_scale;
+    io.g_o = g_rays_o; io.g_d = g_rays_d;
+    return train_render_ray_grad(f, w.field_ws, io, as_stream(stream));
 }
 
 // view groups per member of a scoring call.  FOUR render jobs in flight (the caller's stream + the three shared side streams) is the measured optimum for

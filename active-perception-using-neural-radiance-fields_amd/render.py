@@ -7,6 +7,7 @@ running on libmi355nerf.so.
   render_probablistic_image_with_occgrid_test     utils.py:782-1032
   render_image_with_occgrid_with_depth_guide      utils.py:63-219   (forward; see DESIGN.md §Scope for backward)
   fused_train_render                              utils.py:63-219 on the one-call step's kernels, differentiable (any torch loss behind it)
+  fused_train_render_rays                         the same, also differentiable with respect to the rays (a pose refiner behind transform_rays)
   sem_rendering                                   utils.py:362-461
   generate_image_rays / render_*_from_pose        habitat_to_data.py:274-549
   probablistic_uncertainty -> score_views         pipeline.py:666-798
@@ -738,7 +739,41 @@ def _launch_train_render(st, radiance_field, estimator, rays, render_bkgd, seed,
     L.launch(lib.mnf_train_render_forward, handle, L.ptr(grid.binaries), L.ptr(grid.bits), L.ptr(grid.occs), *grid.res, grid.aabb, L.ptr(o), L.ptr(d), R,
              ctypes.byref(opts), L.ptr(rgb), L.ptr(acc), L.ptr(depth), L.ptr(sem), L.ptr(counts), L.ptr(skip), cap_m, cap_k, L.ptr(ws), nbytes)
     return dict(rgb=rgb, acc=acc, depth=depth, sem=sem, counts=counts, skip=skip, _rays=R, _field=radiance_field, _handle=handle, _opts=opts, _keep=bk_dev,
+                _dirs=d if own_workspace else None,      # the contiguous fp32 [R,3] directions the kernels read: a ray-gradient backward reads them again
                 _caps=(cap_m, cap_k), _ws=ws if own_workspace else None, _nbytes=nbytes, _versions=radiance_field._loaded_versions)
+
+
+def _train_render_backward(call, grads_out, want_params, want_o=False, want_d=False):
+    """The backward both autograd nodes of `fused_train_render` share: `mnf_train_render_backward`, or — when a ray gradient is asked for —
+    `mnf_train_render_backward_rays`, with whatever gradients autograd delivered (None as NULL, strides passed through, no `.contiguous()`).
+    `want_params` False: the parameter pointers go in as NULL (frozen: no weight gradients, no hash scatter).  -> (three parameter gradients | None, g_o, g_d)."""
+    field = call["_field"]
+    if call["_ws"] is None:
+        raise L.MnfError("fused_train_render: a second backward through the same render (its backward overwrites the workspace the first one read); "
+                         "render again")
+    if field._loaded_versions != call["_versions"] or _param_versions(field) != call["_versions"]:
+        raise L.MnfError("fused_train_render: the field's parameters changed between the render and its backward (an optimizer step, a load): the 16-bit "
+                         "weights in the handle are no longer the forward's")
+    params = (field.mlp_base.params, field.mlp_head.params, field.mlp_sem.params)
+    grads = [torch.empty_like(p_, memory_format=torch.contiguous_format) for p_ in params] if want_params else None
+    dev, R = call["counts"].device, call["_rays"]
+    gs = [None if g is None else g.to(device=dev, dtype=torch.float32) for g in grads_out]      # (no-ops: autograd delivers fp32 on the device)
+    st0 = lambda g: 0 if g is None else g.stride(0)
+    st1 = lambda g: 0 if g is None else g.stride(1)
+    ws, call["_ws"] = call["_ws"], None
+    lib = L.load_library()
+    g_in = (L.ptr(gs[0]), st0(gs[0]), st1(gs[0]), L.ptr(gs[1]), st0(gs[1]), L.ptr(gs[2]), st0(gs[2]), L.ptr(gs[3]), st0(gs[3]), st1(gs[3]))
+    g_par = tuple(L.ptr(g) for g in grads) if want_params else (None, None, None)
+    tail = (L.ptr(call["counts"]), L.ptr(call["skip"]), *call["_caps"], L.ptr(ws), call["_nbytes"])
+    g_o = g_d = None
+    if want_o or want_d:
+        g_o = torch.empty(R, 3, device=dev) if want_o else None
+        g_d = torch.empty(R, 3, device=dev) if want_d else None
+        L.launch(lib.mnf_train_render_backward_rays, call["_handle"], R, ctypes.byref(call["_opts"]), L.ptr(call["_dirs"]), *g_in, *g_par, L.ptr(g_o), L.ptr(g_d),
+                 *tail)
+    else:
+        L.launch(lib.mnf_train_render_backward, call["_handle"], R, ctypes.byref(call["_opts"]), *g_in, *g_par, *tail)
+    return grads, g_o, g_d
 
 
 class _TrainRender(torch.autograd.Function):
@@ -756,25 +791,31 @@ class _TrainRender(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_rgb, g_acc, g_depth, g_sem):
-        call = ctx.call
-        field = call["_field"]
-        if call["_ws"] is None:
-            raise L.MnfError("fused_train_render: a second backward through the same render (its backward overwrites the workspace the first one read); "
-                             "render again")
-        if field._loaded_versions != call["_versions"] or _param_versions(field) != call["_versions"]:
-            raise L.MnfError("fused_train_render: the field's parameters changed between the render and its backward (an optimizer step, a load): the 16-bit "
-                             "weights in the handle are no longer the forward's")
-        params = (field.mlp_base.params, field.mlp_head.params, field.mlp_sem.params)
-        grads = [torch.empty_like(p_, memory_format=torch.contiguous_format) for p_ in params]
-        dev, R = call["counts"].device, call["_rays"]
-        gs = [None if g is None else g.to(device=dev, dtype=torch.float32) for g in (g_rgb, g_acc, g_depth, g_sem)]      # (no-ops: autograd delivers fp32 on the device)
-        st0 = lambda g: 0 if g is None else g.stride(0)
-        st1 = lambda g: 0 if g is None else g.stride(1)
-        ws, call["_ws"] = call["_ws"], None
-        L.launch(L.load_library().mnf_train_render_backward, call["_handle"], R, ctypes.byref(call["_opts"]), L.ptr(gs[0]), st0(gs[0]), st1(gs[0]),
-                 L.ptr(gs[1]), st0(gs[1]), L.ptr(gs[2]), st0(gs[2]), L.ptr(gs[3]), st0(gs[3]), st1(gs[3]), L.ptr(grads[0]), L.ptr(grads[1]), L.ptr(grads[2]),
-                 L.ptr(call["counts"]), L.ptr(call["skip"]), *call["_caps"], L.ptr(ws), call["_nbytes"])
+        grads, _, _ = _train_render_backward(ctx.call, (g_rgb, g_acc, g_depth, g_sem), True)
         return None, grads[0], grads[1], grads[2]
+
+
+class _TrainRenderRays(torch.autograd.Function):
+    """`_TrainRender` with `rays.origins` and `rays.viewdirs` as inputs besides the three parameter vectors (`fused_train_render_rays`): its
+    backward is `mnf_train_render_backward_rays`, asked only for what `ctx.needs_input_grad` wants — the parameter pointers NULL when no parameter requires
+    a gradient — and returns the ray gradients in the shape and dtype of the tensors it was given.  The sample set is a constant of the render."""
+
+    @staticmethod
+    def forward(ctx, call, origins, viewdirs, p_base, p_head, p_sem):
+        planes = tuple(call.pop(k) for k in ("rgb", "acc", "depth", "sem"))
+        ctx.call = call
+        ctx.ray_meta = ((origins.shape, origins.dtype), (viewdirs.shape, viewdirs.dtype))
+        ctx.set_materialize_grads(False)
+        return planes
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb, g_acc, g_depth, g_sem):
+        need = ctx.needs_input_grad
+        grads, g_o, g_d = _train_render_backward(ctx.call, (g_rgb, g_acc, g_depth, g_sem), any(need[3:6]), need[1], need[2])
+        g_rays = tuple(None if g is None else g.view(shape).to(dtype) for g, (shape, dtype) in zip((g_o, g_d), ctx.ray_meta))
+        g_params = tuple(g if w else None for g, w in zip(grads, need[3:6])) if grads is not None else (None, None, None)
+        return (None,) + g_rays + g_params
 
 
 def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float = 0.0, far_plane: float = 1e10, render_step_size: float = 1e-3,
@@ -793,9 +834,30 @@ def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float 
     over to `render_image_with_occgrid_with_depth_guide`; the hand-over follows `radiance_field.training` as the drop-in does: `stratified=False` is honoured
     (the field is put into eval mode for the call), `stratified=True` on a field in eval mode is not, and the drop-in has no `early_stop_eps`, `seed` or
     `deterministic` to pass on.  So does a call whose `rays.origins` or `rays.viewdirs` requires a gradient (with autograd on): the drop-in returns the ray
-    gradients, `mnf_train_render_backward` has no form that does.
+    gradients; `fused_train_render_rays` is the same call kept on the fused route.
     One backward per render, and the parameters must not change between the two (both raise `MnfError`).  Under `torch.no_grad()`, or with no parameter
     requiring a gradient, nothing is kept for a backward.  `latest_train_render(radiance_field)` has the device counters and the skip flag."""
+    return _fused_train_render(radiance_field, estimator, rays, False, near_plane, far_plane, render_step_size, render_bkgd, cone_angle, alpha_thre,
+                               early_stop_eps, depth, stratified, seed, deterministic)
+
+
+def fused_train_render_rays(radiance_field, estimator, rays: Rays, near_plane: float = 0.0, far_plane: float = 1e10, render_step_size: float = 1e-3,
+                            render_bkgd: Optional[torch.Tensor] = None, cone_angle: float = 0.0, alpha_thre: float = 0.0, early_stop_eps: float = 1e-4,
+                            depth: Optional[torch.Tensor] = None, stratified=None, seed: "int | None" = None, deterministic: bool = False):
+    """`fused_train_render` — same arguments, same five results, same bookkeeping — for a caller who differentiates with respect to the RAYS: a call whose
+    `rays.origins` or `rays.viewdirs` requires a gradient (with autograd on) stays on the fused route instead of handing over.  Its backward
+    (`mnf_train_render_backward_rays`) returns dL/d(`rays.origins`) and dL/d(`rays.viewdirs`), in the shape and dtype of the tensors given, beside — or, with
+    every parameter frozen, instead of — the parameter gradients; with frozen parameters it launches no weight gradient and no hash-table scatter (pose
+    refinement behind `transform_rays`: INTEGRATION.md §A).  The sample set is a constant of the render, as on the drop-in route; no gradient reaches the
+    distances or the background colour.  Without a ray that requires a gradient it is `fused_train_render`; more than four occupancy levels or a ray past
+    the scratch row still hand over (the drop-in returns the ray gradients there)."""
+    return _fused_train_render(radiance_field, estimator, rays, True, near_plane, far_plane, render_step_size, render_bkgd, cone_angle, alpha_thre,
+                               early_stop_eps, depth, stratified, seed, deterministic)
+
+
+def _fused_train_render(radiance_field, estimator, rays, ray_gradients, near_plane, far_plane, render_step_size, render_bkgd, cone_angle, alpha_thre,
+                        early_stop_eps, depth, stratified, seed, deterministic):
+    """What `fused_train_render` (`ray_gradients` False: rays that require a gradient hand over) and `fused_train_render_rays` (True) share"""
     _LAST_RENDER.pop(radiance_field, None)
 
     def hand_over():
@@ -812,10 +874,11 @@ def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float 
 
     if estimator.levels > 4 or rays.origins.numel() == 0:
         return hand_over()
-    if torch.is_grad_enabled() and (rays.origins.requires_grad or rays.viewdirs.requires_grad):
-        return hand_over()      # gradients of the rays: the drop-in delivers them (`sem_rendering`), the fused backward has no ray-gradient form
+    want_rays = torch.is_grad_enabled() and (rays.origins.requires_grad or rays.viewdirs.requires_grad)
+    if want_rays and not ray_gradients:
+        return hand_over()      # gradients of the rays: the drop-in delivers them (`sem_rendering`); the fused route does for `fused_train_render_rays` only
     st, seed = _train_state(radiance_field), _step_seed(None, seed)      # one draw per render, whatever the number of attempts
-    differentiable = torch.is_grad_enabled() and any(p_.requires_grad for p_ in radiance_field.parameters())
+    differentiable = torch.is_grad_enabled() and (want_rays or any(p_.requires_grad for p_ in radiance_field.parameters()))
     opts_kw = dict(near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, cone_angle=cone_angle, alpha_thre=alpha_thre,
                    early_stop_eps=early_stop_eps, stratified=stratified, deterministic=deterministic)
     for attempt in range(4):
@@ -831,7 +894,10 @@ def fused_train_render(radiance_field, estimator, rays: Rays, near_plane: float 
         raise L.MnfError("fused_train_render: sample bounds kept growing")
     estimator.last_sampling = {"n_marched": int(c[0])}
     _LAST_RENDER[radiance_field] = dict(counts=out["counts"], skip=out["skip"])
-    if differentiable:
+    if want_rays:
+        planes = _TrainRenderRays.apply(out, rays.origins, rays.viewdirs, radiance_field.mlp_base.params, radiance_field.mlp_head.params,
+                                        radiance_field.mlp_sem.params)
+    elif differentiable:
         planes = _TrainRender.apply(out, radiance_field.mlp_base.params, radiance_field.mlp_head.params, radiance_field.mlp_sem.params)
     else:
         planes = (out["rgb"], out["acc"], out["depth"], out["sem"])

@@ -426,7 +426,7 @@ int mnf_ray_input_gradients(const float *d_positions, const float *d_directions,
  * NO stream synchronisation: the sample counts stay on the device.  counts_dev (DEVICE, 4 x int64): [0] marched samples, [1] surviving
  * samples (= the reference's n_rendering_samples), [2] samples of the longest ray, [3] status bits: 1 marched > max_marched, 2 a ray
  * longer than a scratch row (use the two-pass sampler), 4 surviving > max_kept, 8 a class id outside [0, C) (F.cross_entropy's device
- * assert), 16 no sample survived (the reference `continue`s, pipeline.py:491), 32 (mnf_train_render_backward only) a non-finite incoming gradient.  skip_dev (DEVICE int32): set to 0, then raised for
+ * assert), 16 no sample survived (the reference `continue`s, pipeline.py:491), 32 (mnf_train_render_backward / _backward_rays only) a non-finite incoming gradient.  skip_dev (DEVICE int32): set to 0, then raised for
  * every status bit: with it non-zero the gradients are zero / must not be applied (mnf_adam_step_guarded reads it).  The caller
  * bounds the sample counts (max_marched, max_kept), provides mnf_train_step_workspace_bytes(), reads counts_dev when it wants
  * to and retries with larger bounds after bits 1 / 4.
@@ -493,7 +493,8 @@ int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgr
  *
  * Contract: every bit of per-call state lives in `workspace` (mnf_train_step_workspace_bytes(f, n_rays, max_marched, max_kept) bytes, the same n_rays and
  * bounds in both calls).  Between a forward and its backward the workspace, the field's loaded weights (no mnf_field_set_params / optimizer step on `f`), the
- * options and — if used — the three floats behind opts->render_bkgd_dev must stay unchanged; the rays and the occupancy grid are not read again.  Other
+ * options and — if used — the three floats behind opts->render_bkgd_dev must stay unchanged; the occupancy grid and the ray origins are not read again, and the
+ * ray directions only by mnf_train_render_backward_rays (below), which is handed the forward's array again.  Other
  * forwards and backwards of the same field with OTHER workspaces may run in between (the deterministic mode's scratch on the field handle is only touched
  * inside a backward).  One backward per forward: the backward overwrites workspace state. */
 int mnf_train_render_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
@@ -505,6 +506,26 @@ int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mnf_train_opt
                               const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base, float *g_head, float *g_sem_params,
                               int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes,
                               mnf_stream_t stream);
+/* mnf_train_render_backward for a caller who differentiates with respect to the RAYS (a pose refiner: `loss.backward()`, pipeline.py:518, behind the train
+ * render of utils.py:63-219 with `rays.origins` / `rays.viewdirs` requiring a gradient): the same backward, then ONE more kernel that goes from what it left
+ * in the workspace — dX, the head's dZr1 rows, the kept samples' normalised positions, distances and per-ray runs — straight to
+ *   g_rays_o[r] = sum_s d_position[s],   g_rays_d[r] = sum_s (t_starts[s] + t_ends[s]) / 2 * d_position[s]  +  J_SH(rays_d[r])^T sum_s W1_head[:, 0:16]^T dZr1[s]
+ * over the kept samples s of ray r ([n_rays,3] fp32, OVERWRITTEN; one of the two may be NULL).  The per-sample arithmetic is mnf_field_backward_inputs', the sum
+ * mnf_ray_input_gradients' (one wave per ray, lane L the samples L, L + 64, ..., a fixed butterfly): no atomics, the same inputs give the same bits; rays
+ * without kept samples get exact zeros.  The sample set is a constant of the render (it does not move with the rays), t_starts / t_ends and the background
+ * colour get no gradient.  Profile label of the added kernel: "train_render_ray_grad".
+ * g_base / g_head / g_sem_params: all three given — exactly mnf_train_render_backward's launches, then the kernel; all three NULL — the parameters are FROZEN:
+ * nothing is filled, the output gradients and the backward-data kernel run, the weight gradients, the hash-table scatter and their side streams do not.
+ * rays_d [n_rays,3] is the array the forward was given, unchanged; it may be NULL only when g_rays_d is.  With the skip flag raised (the forward's verdict, or
+ * status bit 32 from a non-finite incoming gradient) the ray gradients are exact zeros, as the parameter gradients are.
+ * MNF_ERR_INVALID before any HIP call: both ray outputs NULL, one or two of the three parameter pointers NULL, g_rays_d without rays_d, opts->presampled set, a
+ * wrong struct_size, n_rays / max_marched / max_kept <= 0; MNF_ERR_WORKSPACE: a NULL or short workspace.  One backward per forward, as above.  Enqueues on
+ * `stream` and does not synchronise. */
+int mnf_train_render_backward_rays(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *rays_d, const float *g_rgb,
+                                   int64_t g_rgb_row_stride, int64_t g_rgb_col_stride, const float *g_acc, int64_t g_acc_row_stride, const float *g_depth,
+                                   int64_t g_depth_row_stride, const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base,
+                                   float *g_head, float *g_sem_params, float *g_rays_o, float *g_rays_d, int64_t *counts_dev, int32_t *skip_dev,
+                                   int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
 /* ---------------------------------------------------------------- fused test-mode renderers */
 

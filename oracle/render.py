@@ -168,14 +168,16 @@ def sem_rendering(field, rays_o, rays_d, t_starts, t_ends, ray_indices, n_rays, 
 
 
 def render_train(field, binaries, aabbs, occs_mean, rays_o, rays_d, near_planes, render_step_size=1e-3,
-                 render_bkgd=None, cone_angle=0.0, alpha_thre=0.0):
-    """utils.py:63-219, training branch (single chunk)."""
+                 render_bkgd=None, cone_angle=0.0, alpha_thre=0.0, far_plane=1e10, early_stop_eps=1e-4):
+    """utils.py:63-219, training branch (single chunk).  `early_stop_eps` is `sampling`'s own argument (occ_grid.py:94), which
+    utils.py leaves at its default; the fused step takes it as an option."""
     def sigma_fn(ts, te, ri):
         pos, _ = _positions(rays_o, rays_d, ts, te, ri)
         return field.query_density(pos).squeeze(-1)
 
     ri, ts, te, n_all = sampling(binaries, aabbs, occs_mean, rays_o, rays_d, sigma_fn, near_planes,
-                                 render_step_size=render_step_size, alpha_thre=alpha_thre, cone_angle=cone_angle)
+                                 far_plane=far_plane, render_step_size=render_step_size, early_stop_eps=early_stop_eps,
+                                 alpha_thre=alpha_thre, cone_angle=cone_angle)
     rgb, acc, depth, sem, extras = sem_rendering(field, rays_o, rays_d, ts, te, ri, rays_o.shape[0], render_bkgd)
     extras.update(ray_indices=ri, t_starts=ts, t_ends=te, n_all=n_all)
     return rgb, acc, depth, sem, ts.shape[0], extras
@@ -196,7 +198,7 @@ def _render_test_impl(max_samples, field, binaries, aabbs, rays_o, rays_d, near_
     rgb_var = torch.zeros(n_rays, 3)
     ray_mask = np.ones(n_rays, bool)
     min_samples = 1 if cone_angle == 0 else 4
-    iter_samples = total_samples = 0
+    iter_samples = total_samples = marched_samples = 0
     near_planes = np.full(n_rays, near_plane, np.float32)
     far_planes = np.full(n_rays, far_plane, np.float32)
     o_np, d_np = rays_o.numpy(), rays_d.numpy()
@@ -210,7 +212,7 @@ def _render_test_impl(max_samples, field, binaries, aabbs, rays_o, rays_d, near_
         t_sorted = cat
         t_indices = np.broadcast_to(np.arange(2 * n_grids, dtype=np.int64), (n_rays, 2 * n_grids)).copy()
     opc_thre = 1 - early_stop_eps
-    rounds = []
+    rounds, opacity_gap = [], float("inf")
     while iter_samples < max_samples:
         n_alive = int(ray_mask.sum())
         if n_alive == 0:
@@ -223,6 +225,7 @@ def _render_test_impl(max_samples, field, binaries, aabbs, rays_o, rays_d, near_
         t_ends = torch.from_numpy(iv.vals[iv.is_right])
         ray_indices = torch.from_numpy(sm.ray_indices[sm.is_valid])
         packed_info = sm.packed_info
+        marched_samples += int(ray_indices.shape[0])                 # in front of the alpha threshold: what the field is asked for
         if t_starts.shape[0]:
             pos = rays_o[ray_indices] + rays_d[ray_indices] * (t_starts[:, None] + t_ends[:, None]) / 2.0
             rgbs, sigmas, sems = field(pos, rays_d[ray_indices])
@@ -246,12 +249,16 @@ def _render_test_impl(max_samples, field, binaries, aabbs, rays_o, rays_d, near_
             accumulate_along_rays(weights, torch.pow((t_starts + t_ends)[:, None] / 2.0 - depth[ray_indices], 2),
                                   ray_indices, n_rays, out=depth_var)
         near_planes = term
-        ray_mask = np.logical_and(opacity.view(-1).numpy() <= opc_thre, packed_info[:, 1] == n_samples)
+        full = packed_info[:, 1] == n_samples
+        if full.any():      # how close a ray that could go on came to the other side of the retirement test: 0.0 is an exact tie
+            opacity_gap = min(opacity_gap, float(np.abs(opacity.view(-1).numpy()[full] - np.float32(opc_thre)).min()))
+        ray_mask = np.logical_and(opacity.view(-1).numpy() <= opc_thre, full)
         total_samples += int(ray_indices.shape[0])
         rounds.append((n_alive, n_samples))
     rgb = rgb + render_bkgd * (1.0 - opacity)
     depth = depth / opacity.clamp_min(torch.finfo(torch.float32).eps)
-    out = dict(rgb=rgb, acc=opacity, depth=depth, sem=sem, total_samples=total_samples, rounds=rounds)
+    out = dict(rgb=rgb, acc=opacity, depth=depth, sem=sem, total_samples=total_samples, marched_samples=marched_samples, rounds=rounds,
+               alive_at_end=int(ray_mask.sum()), opacity_gap=opacity_gap)                     # > 0: max_samples ended the render, not the rays
     if probabilistic:
         out.update(rgb_var=rgb_var, depth_var=depth_var)
     return out

@@ -20,6 +20,10 @@ What is captured (all from the reference's own, CPU-runnable code; nothing is re
                 (perception/models/radiance_fields/mlp.py:168-245)
   dataset.npz   Dataset.update_data + evaluation-mode fetch_data/preprocess on a tiny synthetic set
                 (perception/data_proc/habitat_to_data.py:89-272), same placeholder-module note as raygen.npz
+  glue_options.npz  (`glue_options`, after `glue_ngp`, whose scene, field, rays and background it shares) the reference's two test
+                renderers at the render options R1..R6 of tests/test_gpu_render_options.py, its sampler at T1..T6 of
+                tests/test_gpu_train_options.py and its train render (eval mode) at those of them its signature can express:
+                outputs, totals, round schedules (`ref_shim.ShimC.traverse_log`).  See gen_glue_options.
   raygen.npz    Dataset.generate_image_rays + the linspace sub-sampler
                 (perception/data_proc/habitat_to_data.py:274-301, :462-467).  The module imports
                 imageio / cv2 / skimage at top level (unused by this function, absent here); empty
@@ -516,6 +520,85 @@ def gen_glue_ngp():
                ml_acc=acc.numpy(), ml_depth=depth.numpy(), ml_depth_var=depth_var.numpy(), ml_sem=sem.numpy(), ml_total=np.int64(tot),
                ml_rounds=np.asarray(shim.traverse_log, np.int64))
     np.savez_compressed(os.path.join(OUT, "glue_ngp.npz"), **rec)
+
+
+# the render options of tests/test_gpu_render_options.py (R1..R6: options, max_samples) and tests/test_gpu_train_options.py (T1..T5), which the CPU test
+# compares with those modules' own tables
+_DEFAULTS = dict(near_plane=0.0, far_plane=1e10, render_step_size=5e-3, cone_angle=0.0, alpha_thre=0.0, early_stop_eps=1e-4)
+OPTION_CASES = {
+    "R1": (_DEFAULTS, 1024),
+    "R2": (dict(near_plane=0.05, render_step_size=4e-3, cone_angle=0.0, alpha_thre=0.0, early_stop_eps=0.0), 200),
+    "R3": (dict(near_plane=0.1, render_step_size=2e-3, cone_angle=0.004, alpha_thre=0.0, early_stop_eps=0.2), 1024),
+    "R4": (dict(near_plane=0.8, far_plane=3.0, render_step_size=2e-3, cone_angle=0.01, alpha_thre=0.05), 1024),
+    "R5": (dict(near_plane=0.1, render_step_size=2e-2, cone_angle=0.004, alpha_thre=0.3), 1024),
+    "R6": (GLUE_KW, 50),
+}
+TRAIN_OPTION_CASES = {
+    "T1": dict(near_plane=0.0, render_step_size=5e-3, cone_angle=0.0, alpha_thre=0.0, early_stop_eps=1e-4),
+    "T2": dict(near_plane=0.05, render_step_size=8e-3, cone_angle=0.0, alpha_thre=0.0, early_stop_eps=0.0),
+    "T3": dict(GLUE_KW, alpha_thre=0.0, early_stop_eps=0.2),
+    "T4": dict(near_plane=0.8, far_plane=3.0, render_step_size=2e-3, cone_angle=0.01, alpha_thre=0.05),
+    "T5": dict(GLUE_KW, alpha_thre=0.5),
+    "T6": dict(GLUE_KW, early_stop_eps=0.0),
+}
+
+
+def gen_glue_options():
+    """The reference's test renderers, train render and sampler away from GLUE_KW: utils.py:555-779 and :782-1032 at R1..R6, utils.py:63-219 (eval mode) at
+    T1, T4 and T5, occ_grid.py:80-238 at T1..T6.  Scene, field (the oracle's NGP field, parameter seed 0), rays (12 x 12 of pose 1) and background are
+    glue_ngp.npz's, which the tests read them from: this file holds the options and what the reference answered.
+    `render_image_with_occgrid_with_depth_guide` has no `early_stop_eps` argument (utils.py:63-80: `sampling` runs at its default 1e-4), so T2, T3 and T6 are
+    recorded for `OccGridEstimator.sampling` only, which has one (occ_grid.py:95)."""
+    import ref_shim
+    shim = ref_shim.enter_reference()
+    import utils as U
+    from datasets.utils import Rays
+    sc = _glue_scene()
+    est = _ref_estimator(sc)
+    (field,), _ = _ngp_fields(sc, [0], 14)
+    o, d = _view(sc, 1, 12, 12)
+    bk = torch.tensor([0.1, 0.3, 0.6])
+    g = np.load(os.path.join(OUT, "glue_ngp.npz"))
+    assert np.array_equal(g["rays_o"], o.numpy()) and np.array_equal(g["rays_d"], d.numpy()) and np.array_equal(g["bkgd"], bk.numpy())
+    assert np.array_equal(g["occ"], np.packbits(sc["occ"])) and np.array_equal(g["occs"], sc["occs"]) and int(g["param_seed"]) == 0
+    rec = {}
+
+    def options(tag, kw):
+        rec.update({f"{tag}_kw_{k}": np.float64(v) for k, v in kw.items()})
+
+    with torch.no_grad():
+        for tag, (kw, max_samples) in OPTION_CASES.items():
+            options(tag, kw)
+            rec[tag + "_max_samples"] = np.int64(max_samples)
+            shim.traverse_log.clear()
+            rgb, acc, depth, sem, tot = U.render_image_with_occgrid_test(max_samples, field, est, Rays(o, d), render_bkgd=bk, **kw)
+            det_rounds = np.asarray(shim.traverse_log, np.int64)
+            shim.traverse_log.clear()
+            p_rgb, rgb_var, p_acc, p_depth, depth_var, p_sem, p_tot = U.render_probablistic_image_with_occgrid_test(
+                max_samples, field, est, Rays(o, d), render_bkgd=bk, **kw)
+            # the two loops differ by the variances only: stored once
+            assert torch.equal(rgb, p_rgb) and torch.equal(acc, p_acc) and torch.equal(depth, p_depth) and torch.equal(sem, p_sem) and tot == p_tot
+            assert np.array_equal(det_rounds, np.asarray(shim.traverse_log, np.int64))
+            rec.update({f"{tag}_rgb": rgb.numpy(), f"{tag}_acc": acc.numpy(), f"{tag}_depth": depth.numpy(), f"{tag}_sem_every2": sem.numpy()[:, ::2],
+                        f"{tag}_rgb_var": rgb_var.numpy(), f"{tag}_depth_var": depth_var.numpy(), f"{tag}_total": np.int64(tot), f"{tag}_rounds": det_rounds})
+
+        def sigma_fn(ts, te, ri):
+            pos = o[ri] + d[ri] * (ts + te)[:, None] / 2.0
+            return field.query_density(pos).squeeze(-1)
+        for tag, kw in TRAIN_OPTION_CASES.items():
+            options(tag, kw)
+            ri, ts, te = est.sampling(o, d, sigma_fn=sigma_fn, stratified=False, **kw)
+            ri_all, _, _ = est.sampling(o, d, sigma_fn=None, stratified=False, **kw)
+            rec.update({f"{tag}_samp_cnt": np.bincount(ri.numpy(), minlength=len(o)).astype(np.int32), f"{tag}_samp_ts_sum": np.float64(ts.double().sum()),
+                        f"{tag}_samp_te_sum": np.float64(te.double().sum()), f"{tag}_samp_all_n": np.int64(len(ri_all))})
+            if "early_stop_eps" in kw and kw["early_stop_eps"] != 1e-4:
+                continue
+            kw = {k: v for k, v in kw.items() if k != "early_stop_eps"}
+            rgb, acc, depth, sem, n = U.render_image_with_occgrid_with_depth_guide(field, est, Rays(o, d), render_bkgd=bk, **kw)
+            assert n == len(ri)
+            rec.update({f"{tag}_tre_rgb": rgb.numpy(), f"{tag}_tre_acc": acc.numpy(), f"{tag}_tre_depth": depth.numpy(), f"{tag}_tre_sem_every4": sem.numpy()[:, ::4],
+                        f"{tag}_tre_n": np.int64(n)})
+    np.savez_compressed(os.path.join(OUT, "glue_options.npz"), **rec)
 
 
 def gen_scorer():

@@ -89,28 +89,46 @@ def test_field_backward_scatter_routes(lh, n):
 
 
 # ------------------------------------------------------------------ fused train step (mnf_train_step) of every shape
-def _fused_step_vs_oracle(neurons, layers, C, lh, hw, min_samples, field_kw=None, oracle_kw=None, loss_rtol=1e-4, rel=3e-2, cos=0.999, flip_kw=None):
+def _fused_step_vs_oracle(neurons, layers, C, lh, hw, min_samples, field_kw=None, oracle_kw=None, loss_rtol=1e-4, rel=3e-2, cos=0.999, flip_kw=None,
+                          options=None, scene_seed=0, pose=4, image=256):
     """test_config2_fused_train_step_64x4_matches_oracle_autograd's comparison at one shape: one `train_step(fused=True)` against the oracle's
     autograd on the same batch — sample count equal, loss to 1e-4 relative, every gradient group within the train-step tolerance.
     field_kw / oracle_kw: the field's precision mode and the oracle of the same mode; loss_rtol / rel / cos: that mode's bars; flip_kw: hip_field keywords of
-    the same step with the mode switch flipped, whose gradients must differ (the switch is really on)."""
+    the same step with the mode switch flipped, whose gradients must differ (the switch is really on).
+    options: None — the yaml's four (`H.RENDER_KW`) through `train_step`; a dict of render options (`far_plane` and `early_stop_eps` among them, which
+    `train_step` pins) — the same comparison through `fused_forward_backward`, with `est.occs` a constant 0.05 (so `occs.mean()` is 0.05), the marched count
+    compared too, and the oracle's render, the batch and both fields handed back in the result for further checks.  scene_seed / pose / image: the
+    parameters' seed, the view and its full size."""
     from apnrf_amd import render as RD
     from apnrf_amd.optim import FusedAdam
     from oracle import render as R
-    sc = H.make_scene("102344250", neurons=neurons, layers=layers, C=C, log2_hashmap_size=lh)
+    sc = H.make_scene("102344250", neurons=neurons, layers=layers, C=C, log2_hashmap_size=lh, seed=scene_seed)
     hip, orc, est = H.hip_field(sc, **(field_kw or {})), H.oracle_field(sc, requires_grad=True, **(oracle_kw or {})), H.hip_estimator(sc)
-    o, d = H.view_rays(sc, 4, width=256, height=256, h=hw, w=hw)
+    o, d = H.view_rays(sc, pose, width=image, height=image, h=hw, w=hw)
     n = o.shape[0]
     pix, dep, lab = _targets(n, C)
     bk = torch.tensor([0.5, 0.2, 0.9])
-    opt = FusedAdam(hip.parameters(), lr=1e-3, eps=1e-15).bind_field(hip)
     rays = RD.Rays(o.to(DEV), d.to(DEV))
-    out = RD.train_step(hip, est, opt, rays, pix.to(DEV), dep.to(DEV), lab.to(DEV), bk.to(DEV), step=1, fused=True, sync=True, stratified=False, **H.RENDER_KW)
-    assert not out["skipped"] and out["n_rendering_samples"] >= min_samples, out["n_rendering_samples"]
-    ref = R.render_train(orc, sc["occ"], est.aabbs.cpu().numpy(), float(est.occs.mean().item()), o, d, torch.full((n,), 0.1), render_bkgd=bk,
-                         render_step_size=1e-3, cone_angle=0.004, alpha_thre=0.01)
+    if options is None:
+        opt = FusedAdam(hip.parameters(), lr=1e-3, eps=1e-15).bind_field(hip)
+        out = RD.train_step(hip, est, opt, rays, pix.to(DEV), dep.to(DEV), lab.to(DEV), bk.to(DEV), step=1, fused=True, sync=True, stratified=False, **H.RENDER_KW)
+        assert not out["skipped"]
+        kw = dict(H.RENDER_KW)
+    else:
+        est.occs = torch.full_like(est.occs, 0.05)
+        out = RD.fused_forward_backward(hip.train(), est, rays, pix.to(DEV), dep.to(DEV), lab.to(DEV), bk.to(DEV), stratified=False, **options)
+        assert out is not None, "the fused route handed over"
+        assert int(out["skip"]) == 0 and int(out["counts"][3]) == 0, out["counts"].tolist()
+        kw = dict(options)
+    assert out["n_rendering_samples"] >= min_samples, out["n_rendering_samples"]
+    ref = R.render_train(orc, sc["occ"], est.aabbs.cpu().numpy(), float(est.occs.mean().item()), o, d, torch.full((n,), kw.pop("near_plane")), render_bkgd=bk, **kw)
     r_loss = _loss(ref[0], ref[2], ref[3], pix, dep, lab)
     r_loss.backward()
+    if options is not None:
+        print(f"fused step {neurons}x{layers} C={C} {field_kw or ''} {options}: kept {out['n_rendering_samples']} vs oracle {ref[4]}, marched {out['n_marched']} vs "
+              f"{ref[5]['n_all']}, longest ray {int(out['counts'][2])}, loss rel err {abs(float(out['loss']) / float(r_loss.detach()) - 1.0):.2e}")
+        assert out["n_marched"] == int(out["counts"][0]) == ref[5]["n_all"], (out["n_marched"], ref[5]["n_all"])
+        out.update(ref=ref, ref_loss=r_loss.detach(), orc=orc, hip=hip, est=est, sc=sc, rays=rays, targets=(pix, dep, lab), bk=bk)
     if field_kw:
         print(f"fused step {neurons}x{layers} C={C} T=2^{lh} {field_kw}: samples {out['n_rendering_samples']} vs oracle {ref[4]}, "
               f"loss rel err {abs(float(out['loss']) / float(r_loss.detach()) - 1.0):.2e}")

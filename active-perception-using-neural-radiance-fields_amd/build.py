@@ -22,13 +22,16 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + INCLUDE, "-I" + CSRC]
 # march.hip / render.hip hold the bit-exact marcher: no FMA contraction (see csrc/march_dev.h)
-# value: (source file, extra flags); field / train / inputgrad are built twice: fp16 and bf16 matrix-core operands (csrc/common.h)
+# value: (source file, extra flags); field / train / inputgrad are built twice: fp16 and bf16 matrix-core operands (csrc/common.h).  Everything else,
+# the backward's table-gradient scatter (scatter.hip) and the optimizer (adam.hip) included, touches no matrix-core operand and is built once.
 SOURCES = {
     "api.cpp": [],
     "march.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "field.hip": ["-fno-slp-vectorize"],   # packed-fp32 pairing of the compositing butterflies keeps their DPP operands from folding into the adds
     "train.hip": [],
+    "scatter.hip": [],
+    "adam.hip": [],
     "inputgrad.hip": [],
     "composite_train.hip": [],
     "occupancy.hip": ["-ffp-contract=off"],
@@ -44,7 +47,7 @@ SOURCES = {
     "inputgrad.hip@bf16": ["-DMNF_BF16"],
 }
 # translation units that read diagnostic knobs (csrc/common.h: diag_env): recompiled with -DMNF_DIAG for the diag library
-DIAG_UNITS = ("render.hip", "field.hip", "train.hip", "field.hip@bf16", "train.hip@bf16", "trainstep.hip")
+DIAG_UNITS = ("render.hip", "field.hip", "train.hip", "scatter.hip", "field.hip@bf16", "train.hip@bf16", "trainstep.hip")
 
 
 def _deps_mtime():

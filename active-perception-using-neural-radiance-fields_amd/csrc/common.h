@@ -9,9 +9,10 @@
 
 #include "mi355nerf.h"
 
-// The fused field kernels exist twice, once per matrix-core operand type: field.hip / train.hip are compiled as two
-// translation units (plain: fp16 operands, the reference's tcnn arithmetic; -DMNF_BF16: bf16 operands, BASELINE config 5) and
-// everything type-dependent lives in mnf::f16 / mnf::bf16.  The C entry points are compiled once and dispatch on the handle.
+// The fused field kernels exist twice, once per matrix-core operand type: field.hip, train.hip (dgrad, wgrad and the backward's host code) and
+// inputgrad.hip are compiled as two translation units each (plain: fp16 operands, the reference's tcnn arithmetic; -DMNF_BF16: bf16 operands,
+// BASELINE config 5) and everything type-dependent lives in mnf::f16 / mnf::bf16.  The C entry points are compiled once and dispatch on the handle;
+// every other unit — the backward's table-gradient scatter (scatter.hip) and the optimizer (adam.hip) among them — exists once, in mnf.
 #ifdef MNF_BF16
 #define MNF_DT bf16
 #else

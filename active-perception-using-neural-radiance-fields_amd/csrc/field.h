@@ -141,14 +141,32 @@ struct RayGradIO {
     float *g_o, *g_d;                             // [n_rays][3] each, overwritten; either may be NULL
 };
 
+// The train step's output gradients in factored form: d_rgb[s] = w[s] * g_rgb[ray[s]], d_sem[s][c] = w[s] * g_sem[ray[s]][c] — what sem_rendering's backward
+// (composite_train.hip) would write per sample, 128 bytes each at 29 classes, and the backward-data kernel would read back at a 116-byte lane stride.  Given the
+// factors the kernel forms the products itself (same fp32 multiplications): 12 bytes per sample plus per-ray vectors that stay in cache.
+struct FactoredGrad { const float *w; const int64_t *ray; const float *g_rgb, *g_sem; };
+
+// One call of the field's backward (train.hip)
+struct BackwardCall {
+    const float *positions;                      // [n][3]: world positions, or aabb-normalised ones (positions_normalized)
+    int64_t n; const int64_t *n_dev;             // samples, and optionally their count on the device (n = its upper bound)
+    const float *d_rgb, *d_density, *d_sem;      // output gradients [n][3], [n], [n][C]; d_rgb / d_sem are not read when `factored` is given
+    const float *rgb, *density;                  // forward outputs [n][3], [n]
+    void *workspace; int64_t workspace_bytes;    // the train workspace the forward filled (mnf_field_train_workspace_bytes)
+    float loss_scale;
+    float *g_base, *g_head, *g_sem;              // fp32 parameter gradients, added to; all three NULL: none (frozen parameters), the call stops behind dgrad
+    bool zero_grads, positions_normalized;       // zero the three vectors first; see `positions`
+    bool deterministic;                          // fixed-point table gradient, ordered weight-gradient partial sums
+    FactoredGrad factored;                       // all NULL: absent
+    hipStream_t stream;
+};
+
 // dispatchers on the handle's operand type (defined once, in the fp16 translation units)
 void free_train_state(mnf_field_t f);
 int launch_field(mnf_field_t f, const FieldIO &io, bool density_only, hipStream_t stream, const TrainBuf *train = nullptr);
-// training forward / backward with the sample count optionally on the device (io.n_dev64 / n_dev; n = upper bound)
+// training forward / backward
 int forward_train(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream, bool deterministic = false);
-int backward(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_dev, const float *d_rgb, const float *d_density,
-             const float *d_sem, const float *rgb, const float *density, void *workspace, int64_t workspace_bytes, float loss_scale,
-             float *g_base, float *g_head, float *g_sem, bool zero_grads, bool positions_normalized, bool deterministic, hipStream_t stream);
+int backward(mnf_field_t f, const BackwardCall &c);
 int train_render_ray_grad(mnf_field_t f, void *field_ws, const RayGradIO &io, hipStream_t stream);
 
 #define MNF_DECLARE_DT_IMPL(ns)                                                                                                      \
@@ -160,10 +178,7 @@ int train_render_ray_grad(mnf_field_t f, void *field_ws, const RayGradIO &io, hi
     int64_t train_workspace_bytes_impl(mnf_field_t f, int64_t n);                                                                    \
     int forward_train_impl(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream,          \
                            bool deterministic);                                                                                      \
-    int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_dev, const float *d_rgb,                  \
-                      const float *d_density, const float *d_sem, const float *rgb, const float *density, void *workspace,          \
-                      int64_t workspace_bytes, float loss_scale, float *g_base, float *g_head, float *g_sem, bool zero_grads,       \
-                      bool positions_normalized, bool deterministic, hipStream_t stream);                                           \
+    int backward_impl(mnf_field_t f, const BackwardCall &c);                                                                         \
     int input_grad_view_impl(mnf_field_t f, void *workspace, int64_t n, InputGradView &view);                                        \
     int field_input_grad_impl(mnf_field_t f, const InputGradView &view, const float *directions, int64_t n, float loss_scale,       \
                               float *d_positions, float *d_directions, hipStream_t stream);                                          \

@@ -1,4 +1,4 @@
-// Device-side building blocks of the fused field kernels (inference: field.hip, training: train.hip):
+// Device-side building blocks of the fused field kernels (inference: field.hip, training: train.hip, scatter.hip):
 // fp16 vector types, fragment-block bookkeeping, MFMA layer helpers, the lane<->lane+32 half exchange,
 // hash-level index math and degree-4 spherical harmonics.  See the header of field.hip for the data flow.
 #pragma once
@@ -26,6 +26,24 @@ constexpr int CT = 2;                            // 32-sample column tiles per w
 constexpr int kWavesPerBlock = 8;                // 512 samples per workgroup pass, two waves per SIMD
 constexpr int kThreads = kWavesPerBlock * 64;
 constexpr int kWaveSamples = 32 * CT;
+
+// The number of samples of a training step may live on the device (mnf_train_step never brings it to the host): `n` is then the
+// upper bound the launch was sized for and `n_dev` the actual count, read with one scalar load.
+__device__ __forceinline__ int64_t count_here(int64_t n_cap, const int64_t *n_dev) {
+    if (!n_dev) return n_cap;
+    typedef const int64_t __attribute__((address_space(4))) *CntPtr;
+    const int64_t nd = *(CntPtr)(uintptr_t)n_dev;
+    return nd < n_cap ? nd : n_cap;
+}
+
+// The backward's kernels (train.hip, scatter.hip) can be issued for one of `n_chunks` contiguous ranges of 64-sample tiles (whole tiles: dgrad's unit), so that the
+// hash-table scatter of a range starts behind the backward-data launch of THAT range while the next range is still in dgrad.  The ranges are
+// fractions of the actual (device-side) count.
+__device__ __forceinline__ void chunk_tiles(int64_t n, int chunk, int n_chunks, int64_t &t0, int64_t &t1) {
+    const int64_t n_tiles = (n + kWaveSamples - 1) / kWaveSamples;
+    t0 = n_chunks > 1 ? n_tiles * chunk / n_chunks : 0;
+    t1 = n_chunks > 1 ? n_tiles * (chunk + 1) / n_chunks : n_tiles;
+}
 
 // ------------------------------------------------------------------ fragment block bookkeeping
 template <int W, int NH>

@@ -1,5 +1,6 @@
 // Backward pass of the radiance field (the tiny-cuda-nn backward the reference reaches through
-// `loss.backward()`, scripts/pipeline.py:518; forward call sites perception/models/radiance_fields/ngp.py:171-238):
+// `loss.backward()`, scripts/pipeline.py:518; forward call sites perception/models/radiance_fields/ngp.py:171-238): the matrix-core half and the
+// host code that runs the whole of it (backward_impl).
 //
 //   dgrad_kernel   dL/d(rgb, sigma, sem) per sample -> pre-activation gradients of every layer (kept in MFMA
 //                  registers from layer to layer exactly like the forward chain, with the TRANSPOSED weight
@@ -8,27 +9,17 @@
 //   wgrad_kernel   dW[n][k] = sum_samples dOut^T[n][c] * In^T[k][c]: the contraction runs over samples, and with
 //                  feature-major fp16 activations both MFMA operands are plain 16-byte loads; split over sample
 //                  chunks, fp32 atomics into the flat parameter-gradient vectors.
-//   hash_bwd_walk_kernel  trilinear scatter of dL/d(features) into the dense fp32 table gradient (float atomics).
+//   scatter.hip    trilinear scatter of dL/d(features) into the dense fp32 table gradient, behind scatter.h.
 //
+// The optimizer that consumes the gradients is adam.hip.
 // Gradients of activations travel in fp16 scaled by `loss_scale` (tcnn does the same with its default scale of
 // 128); parameter gradients are accumulated and returned in fp32, un-scaled.
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "field_dev.h"
-
-namespace mnf {
-// The train step's output gradients in factored form: d_rgb[s] = w[s] * g_rgb[ray[s]], d_sem[s][c] = w[s] * g_sem[ray[s]][c] — what sem_rendering's backward
-// (composite_train.hip) would write per sample, 128 bytes each at 29 classes, and the backward-data kernel would read back at a 116-byte lane stride.  Given the
-// factors the kernel forms the products itself (same fp32 multiplications): 12 bytes per sample plus per-ray vectors that stay in cache.
-struct FactoredGrad { const float *w; const int64_t *ray; const float *g_rgb, *g_sem; };
-// set by trainstep.hip for the NEXT backward on this thread; taken (and cleared) by backward_impl
-void set_factored_output_gradient(const FactoredGrad &fg);
-bool take_factored_output_gradient(FactoredGrad &fg);
-}  // namespace mnf
+#include "scatter.h"
 
 MNF_DT_BEGIN
 
@@ -48,24 +39,6 @@ struct LayoutT {
     static constexpr int blocks = o_b1 + 2 * KSW;
 };
 
-// The number of samples of a training step may live on the device (mnf_train_step never brings it to the host): `n` is then the
-// upper bound the launch was sized for and `n_dev` the actual count, read with one scalar load.
-__device__ __forceinline__ int64_t count_here(int64_t n_cap, const int64_t *n_dev) {
-    if (!n_dev) return n_cap;
-    typedef const int64_t __attribute__((address_space(4))) *CntPtr;
-    const int64_t nd = *(CntPtr)(uintptr_t)n_dev;
-    return nd < n_cap ? nd : n_cap;
-}
-
-// The backward's kernels can be issued for one of `n_chunks` contiguous ranges of 64-sample tiles (whole tiles: dgrad's unit), so that the
-// hash-table scatter of a range starts behind the backward-data launch of THAT range while the next range is still in dgrad.  The ranges are
-// fractions of the actual (device-side) count.
-__device__ __forceinline__ void chunk_tiles(int64_t n, int chunk, int n_chunks, int64_t &t0, int64_t &t1) {
-    const int64_t n_tiles = (n + kWaveSamples - 1) / kWaveSamples;
-    t0 = n_chunks > 1 ? n_tiles * chunk / n_chunks : 0;
-    t1 = n_chunks > 1 ? n_tiles * (chunk + 1) / n_chunks : n_tiles;
-}
-
 struct BwdArgs {
     const half8 *fragsT;
     const float *d_rgb, *d_sigma, *d_sem;   // [N,3], [N], [N,C]
@@ -77,7 +50,7 @@ struct BwdArgs {
     float loss_scale;
     int chunk, n_chunks;
     TrainBuf train;
-    FactoredGrad fg;                        // fg.w != NULL: d_rgb / d_sem are not read, the products are formed here
+    FactoredGrad fg;                        // fg.w != NULL (field.h): d_rgb / d_sem are not read, the products are formed here
 };
 
 // fp32 -> fp16 with saturation at the largest finite half: a loss-scaled gradient that leaves the fp16 range is clipped
@@ -383,435 +356,6 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const WgradJob *__res
     g[jb.param_off + (int64_t)(jb.n0 + row) * jb.stride + col] = sum * inv_scale;   // every weight belongs to exactly one tile
 }
 
-// ------------------------------------------------------------------ hash-grid gradient scatter
-// Deterministic mode (mnf_train_opts.deterministic): the table gradient is accumulated in 64-bit fixed point (value * 2^56, integer
-// atomics: associative, so the result does not depend on the order in which the adds arrive), then converted to fp32 once.  The
-// memory-side atomic unit takes 8-byte integer adds at the request rate of 4-byte float adds (tools/atomic_bench.hip), so the mode
-// costs the wider zero-fill and the conversion pass, not scatter time.  Range +-128 (saturating), resolution 1.4e-17.
-constexpr float kFixScale = 72057594037927936.0f;        // 2^56
-constexpr double kFixInv = 1.0 / 72057594037927936.0;
-__device__ __forceinline__ unsigned long long to_fixed(float v) {
-    const float c = fminf(fmaxf(v, -127.99999f), 127.99999f);
-    return (unsigned long long)__float2ll_rn(c * kFixScale);              // NaN -> 0 (llrint of NaN is unspecified: guard below)
-}
-
-struct HashBwdArgs {
-    const float *positions;   // aabb-normalised positions xn = (x - aabb_min) / (aabb_max - aabb_min) [N,3] (normalize_kernel): the
-                              // three divisions are done once per sample, not once per sample, level and lane
-    const float *dX;      // [16][Np][4]
-    int64_t Np;
-    int chunk, n_chunks;  // this launch covers tile range `chunk` of `n_chunks` (chunk_tiles)
-    int level0;           // first level of this launch (experiments; 0 in production)
-    int n_walk_levels;    // levels level0 .. level0 + n_walk_levels - 1
-    float *repl;          // [kReplicas][repl_floats]: private copies of the coarsest levels' gradient (see below)
-    uint32_t repl_floats;
-    int repl_levels;
-    float *g_table;       // fp32 [entries][4]
-    int64_t n;
-    const int64_t *n_dev;
-    unsigned long long *flush_count;   // diagnostic build (MNF_SCATTER_COUNT=1): quad atomics issued per level, else NULL
-    unsigned long long *q_table, *q_repl;   // deterministic mode: fixed-point table gradient [entries][4] and replicas, else NULL
-    unsigned long long *q_bad;              // deterministic mode: number of non-finite contributions (they cannot be represented in fixed point)
-    float aabb[6];
-    LevelMeta levels[16];
-};
-
-// ngp.py:177-178 once per sample for the scatter below (the same expression as the forward kernel's fetch_sample)
-__global__ void __launch_bounds__(256) normalize_kernel(const float *__restrict__ pos, int64_t n_cap, const int64_t *n_dev, float a0, float a1, float a2,
-                                                        float a3, float a4, float a5, float *__restrict__ xn) {
-    const float lo[3] = {a0, a1, a2}, hi[3] = {a3, a4, a5};
-    const int64_t n = count_here(n_cap, n_dev);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * n; i += (int64_t)blockDim.x * gridDim.x) {
-        const int d = (int)(i % 3);
-        xn[i] = (pos[i] - lo[d]) / (hi[d] - lo[d]);
-    }
-}
-
-// Samples arrive sorted by ray and by distance along the ray, so consecutive samples usually sit in the same grid cell
-// of a level (always at the coarse levels, often at the fine ones).  A scattered float atomic is the slow operation
-// here (MI355X: ~17x below the contiguous rate) and the kernel is bound by the rate of memory-side read-modify-writes,
-// so everything below is about issuing fewer of them.  (History: one atomic per lane and corner 94 ms; runs of lanes in
-// one cell summed by a segmented lane scan, tails only 21 ms; LDS transpose to 16-byte quad atomics 3.7 ms; the walk
-// below with face sharing 3.4 ms.)
-// The coarsest dense levels have a few thousand entries that every ray of a camera crosses near its origin: their
-// atomics pile up on the same addresses (level 0 alone cost as much as the finest level).  Workgroups therefore add
-// into one of kReplicas private copies of those levels, which a small kernel folds into the gradient afterwards.
-constexpr int kReplicas = 16;
-constexpr uint32_t kReplMaxEntries = 131072;
-
-__global__ void __launch_bounds__(256) fold_replicas_fixed_kernel(const unsigned long long *__restrict__ repl, uint32_t repl_floats,
-                                                                  unsigned long long *__restrict__ q_table) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= repl_floats) return;
-    unsigned long long acc = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc += repl[(size_t)r * repl_floats + i];
-    if (acc) q_table[i] += acc;
-}
-
-// fixed point -> fp32 gradient (overwrites the table part of the gradient vector)
-__global__ void __launch_bounds__(256) fixed_to_float_kernel(const long long *__restrict__ q, float *__restrict__ g, int64_t n,
-                                                             const unsigned long long *__restrict__ bad) {
-    const bool poisoned = *bad != 0;     // a non-finite contribution was met: the gradient says so (the NaN guard of pipeline.py:520-529 sees it)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x)
-        g[i] = poisoned && i == 0 ? __builtin_nanf("") : (float)((double)q[i] * kFixInv);
-}
-
-__global__ void __launch_bounds__(256) fold_replicas_kernel(const float *__restrict__ repl, uint32_t repl_floats, float *__restrict__ g_table) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= repl_floats) return;
-    float acc = 0.f;
-#pragma unroll
-    for (int r = 0; r < kReplicas; ++r) acc += repl[(size_t)r * repl_floats + i];
-    if (acc != 0.f) g_table[i] += acc;
-}
-
-// The scatter as a WALK along the sample order.  A half-wave owns a chunk of kWalkChunk consecutive samples of one level;
-// its 32 lanes are the 8 corners x 4 features of a grid cell.  Samples are visited in order, every lane accumulating
-// w_corner * g_feature for the open cell in a register; when the cell changes the sums go out as quad-atomics (the four
-// features of a corner are 16 contiguous bytes).  What the lane-scan form cannot do: when the ray steps into a FACE
-// neighbour, the four corners on the shared face stay in registers (they move to the partner lanes, lane ^ 4 / 8 / 16)
-// and only the four corners left behind are flushed; edge and vertex neighbours are reached by two or three such
-// crossings (6 or 7 flushed corners instead of 8).  The kernel is bound by the rate of memory-side read-modify-writes.  Ray structure is not needed: runs are found by comparing
-// consecutive cells, and a chunk boundary only costs one extra flush.
-constexpr int kWalkChunk = 128;
-#ifndef MNF_EXP_SCATTER
-#define MNF_EXP_SCATTER 0
-#endif
-
-template <bool DET>
-__global__ void __launch_bounds__(256) hash_bwd_walk_kernel(const HashBwdArgs args) {
-    const int sub = threadIdx.x & 31;                 // lane inside the half-wave
-    const int corner = sub >> 2, feat = sub & 3;
-    const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
-    const int64_t n_cnt = count_here(args.n, args.n_dev);
-    int64_t rt0, rt1;
-    chunk_tiles(n_cnt, args.chunk, args.n_chunks, rt0, rt1);
-    const int64_t s_lo = rt0 * kWaveSamples, n_all = rt1 * kWaveSamples < n_cnt ? rt1 * kWaveSamples : n_cnt;       // samples [s_lo, n_all) of this launch
-    // A bounded number of workgroups walks all (level, chunk) pairs (level by level, so that the workgroups of the moment add into the same few
-    // megabytes): the kernel is bound by the atomic unit, not by waves in flight, and the wave slots it leaves are what lets the binned passes
-    // and the weight gradients run beside it instead of behind it.
-    const int64_t chunks = n_all > s_lo ? (n_all - s_lo + kWalkChunk - 1) / kWalkChunk : 0;
-    const int64_t items = chunks * args.n_walk_levels;
-    for (int64_t item = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5; item < items; item += ((int64_t)gridDim.x * blockDim.x) >> 5) {
-    const int64_t chunk = item % chunks;
-    const int l = (int)(item / chunks) + args.level0;
-    const int64_t i0 = s_lo + chunk * kWalkChunk;
-    const int64_t i1 = i0 + kWalkChunk < n_all ? i0 + kWalkChunk : n_all;
-    const LevelMeta m = args.levels[l];
-    const uint32_t replica = (uint32_t)((chunk >> 3) % kReplicas);
-    float *const g_dst = l < args.repl_levels ? args.repl + (size_t)replica * args.repl_floats : args.g_table;
-    unsigned long long *const q_dst = !DET ? nullptr : (l < args.repl_levels ? args.q_repl + (size_t)replica * args.repl_floats : args.q_table);
-    const float *gl = args.dX + ((int64_t)l * args.Np) * 4 + feat;
-
-    float acc = 0.0f;
-    bool open = false;
-    int cx = 0, cy = 0, cz = 0;                       // cell of the open run
-    auto flush = [&]() {                              // this lane's corner of the open cell
-        if (acc != 0.0f) {
-            const uint32_t px = (uint32_t)cx + bx, py = (uint32_t)cy + by, pz = (uint32_t)cz + bz;
-            uint32_t idx;
-            if (m.hashed) {
-                idx = (px ^ (py * 2654435761u) ^ (pz * 805459861u)) & (m.size - 1u);
-            } else {
-                idx = px + py * m.res + pz * m.res * m.res;
-                uint32_t q = __umulhi(m.div_magic, idx);
-                q = (((idx - q) >> 1) + q) >> m.div_shift;
-                idx -= q * m.size;
-            }
-#ifdef MNF_DIAG
-            if (args.flush_count && feat == 0) atomicAdd(&args.flush_count[l], 1ull);
-#endif
-#if MNF_EXP_SCATTER != 1      /* timing experiment: 1 = the walk without its atomics */
-            if (DET) {
-                // a contribution outside the fixed-point range would saturate silently into a wrong finite gradient: it poisons the
-                // step like a non-finite one
-                if (fabsf(acc) < 127.99999f) atomicAdd(q_dst + ((size_t)(m.offset + idx) << 2) + feat, to_fixed(acc));
-                else atomicAdd(args.q_bad, 1ull);          // too large / NaN / Inf: reported through the converted gradient (fixed_to_float_kernel)
-            }
-            else atomicAdd(g_dst + ((size_t)(m.offset + idx) << 2) + feat, acc);
-#else
-            if (acc == 123.456f) g_dst[0] = acc;
-#endif
-        }
-        acc = 0.0f;
-    };
-    constexpr int B = 8;                              // samples fetched ahead of the sequential part
-    for (int64_t i = i0; i < i1; i += B) {
-        float sx[B], sy[B], sz[B], g[B];
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-            const int64_t k = i + b < i1 ? i + b : i1 - 1;
-            sx[b] = args.positions[3 * k]; sy[b] = args.positions[3 * k + 1]; sz[b] = args.positions[3 * k + 2];
-            g[b] = gl[k * 4];
-        }
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-            if (i + b >= i1) break;
-            // position -> cell and fractions, exactly as hash_prep
-            const float x0 = __builtin_fmaf(m.scale, sx[b], 0.5f);
-            const float x1 = __builtin_fmaf(m.scale, sy[b], 0.5f);
-            const float x2 = __builtin_fmaf(m.scale, sz[b], 0.5f);
-            const float f0 = floorf(x0), f1 = floorf(x1), f2 = floorf(x2);
-            const int c0 = (int)f0, c1 = (int)f1, c2 = (int)f2;
-            const int dx = c0 - cx, dy = c1 - cy, dz = c2 - cz;
-            if (!open) {
-                open = true;
-                cx = c0; cy = c1; cz = c2;
-            } else if ((dx | dy | dz) != 0) {         // half-wave uniform
-                const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, az = dz < 0 ? -dz : dz;
-                if ((ax | ay | az) > 1) {
-                    flush();                           // a jump (new ray, or a step longer than a cell)
-                    cx = c0; cy = c1; cz = c2;
-                } else {
-                    // one face crossing per changed axis, through the intermediate cells: the corners on the far side of
-                    // the cell being left are the near side of the next one and stay in registers (partner lane)
-                    auto face_move = [&](int bit, int dir, int mask) {
-                        const bool stays_behind = dir > 0 ? bit == 0 : bit == 1;
-                        if (stays_behind) flush();
-                        const float moved = __shfl_xor(acc, mask, 64);
-                        acc = stays_behind ? moved : 0.0f;
-                    };
-                    if (dx) { face_move(bx, dx, 4); cx = c0; }
-                    if (dy) { face_move(by, dy, 8); cy = c1; }
-                    if (dz) { face_move(bz, dz, 16); cz = c2; }
-                }
-            }
-            const float fx = x0 - f0, fy = x1 - f1, fz = x2 - f2;
-            const float wx = bx ? fx : 1.0f - fx, wy = by ? fy : 1.0f - fy, wz = bz ? fz : 1.0f - fz;
-            acc += (((1.0f * wx) * wy) * wz) * g[b];
-        }
-    }
-    flush();
-    }
-}
-
-// ---- the large hashed levels: binned scatter -------------------------------------------------------------------------------------
-// The walk above is bound by the memory-side atomic unit (~21 G 64-byte requests/s whatever they carry, profiles/r03_atomic_microbench.txt),
-// and on the fine levels nearly every corner of every sample is a request of its own (hashed neighbours are not neighbours in memory).
-// Those levels go through memory instead: a level's table (2^k entries) is cut into bins of kBinEntries consecutive entries whose fp32
-// gradient fits in LDS.  Pass A (bin_items_kernel) writes one 16-byte item per (sample, corner) — the four feature gradients with the entry's
-// index inside its bin kept in their lowest mantissa bits — to the bin's list (slots reserved per workgroup: one returning atomic per bin
-// and workgroup).  Pass B (bin_accumulate_kernel), one workgroup per (level, bin), streams its list, adds into LDS and adds
-// the bin's sums to the gradient with plain 16-byte read-modify-writes: it is the only writer of those entries at that time.  The LDS sums
-// are DOUBLES: ds_add_f32 retires about one lane every 2.5 clocks per CU (4 x slower than the loads feed it), ds_add_f64 and the integer
-// adds run at the rate of the loads (tools/bin_bench.hip, profiles/r03_bin_bench.txt).  A list that
-// is full sends its items to the gradient with float atomics as before, so the bins only need to be sized for a uniform hash.
-#ifndef MNF_BIN_LOG2
-#define MNF_BIN_LOG2 12
-#endif
-constexpr int kBinEntriesLog2 = MNF_BIN_LOG2;
-constexpr uint32_t kBinEntries = 1u << kBinEntriesLog2;     // x 4 features x 8 bytes = 128 KB of LDS per workgroup of pass B
-constexpr int kMaxBins = 512;                                // per level: tables up to 2^21 entries
-constexpr int kBinThreadsB = MNF_BIN_LOG2 >= 12 ? 1024 : 512;
-
-struct BinArgs {
-    const float *positions;   // normalised positions [N,3]
-    const float *dX;          // [16][Np][4]
-    int64_t Np, n;
-    const int64_t *n_dev;
-    int chunk, n_chunks;      // pass A of this launch covers tile range `chunk` of `n_chunks` (chunk_tiles); pass B runs once, behind the last pass A
-    int level0, n_levels;     // levels level0 .. level0 + n_levels - 1, all hashed with size a multiple of kBinEntries
-    float4 *items;            // [n_levels][bins of that level][cap]: level k's lists start at item_base[k]
-    uint32_t *cursors;        // [n_levels][kMaxBins] items handed out per list (may exceed cap: the excess went to the atomics)
-    uint32_t cap;             // items per list
-    float *g_table;           // fp32 [entries][4]
-    LevelMeta levels[16];
-};
-
-// index bits into / out of the lowest 3 mantissa bits of each of the four values (round to nearest on the remaining 20 bits; a non-finite
-// value stays non-finite, so the NaN guard of the step still sees it)
-__device__ __forceinline__ float4 pack_item(const float v[4], uint32_t idx) {
-    float4 o;
-    float *po = &o.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t b = __builtin_bit_cast(uint32_t, v[k]);
-        if ((b & 0x7f800000u) != 0x7f800000u) b += 4u;          // (Inf / NaN: no carry out of the exponent)
-        b = (b & ~7u) | ((idx >> (3 * k)) & 7u);
-        po[k] = __builtin_bit_cast(float, b);
-    }
-    return o;
-}
-
-static_assert(kBinEntriesLog2 <= 12, "pack_item keeps 3 index bits per value");
-
-#ifndef MNF_BIN_CHUNK
-#define MNF_BIN_CHUNK 2
-#endif
-constexpr int kBinChunk = MNF_BIN_CHUNK;                     // sub-chunks of 256 samples per workgroup of pass A (experiment builds: -DMNF_BIN_CHUNK=1 / 4)
-constexpr int kBinStage = kBinChunk * 256 * 8;               // items staged in LDS per workgroup (64 KB)
-
-__global__ void __launch_bounds__(256) bin_items_kernel(const BinArgs args) {
-    __shared__ uint32_t s_cnt[kMaxBins], s_off[kMaxBins];
-    __shared__ float4 s_stage[kBinStage];
-    __shared__ uint16_t s_binof[kBinStage];
-    __shared__ uint32_t s_total;
-    // level fastest: neighbouring workgroups reserve in different levels' cursors
-    const int lk = (int)(blockIdx.x % (unsigned)args.n_levels), l = lk + args.level0;
-    const int64_t chunk = blockIdx.x / (unsigned)args.n_levels;
-    const LevelMeta m = args.levels[l];
-    const uint32_t nb = m.size >> kBinEntriesLog2;
-    const int64_t n_cnt = count_here(args.n, args.n_dev);
-    int64_t rt0, rt1;
-    chunk_tiles(n_cnt, args.chunk, args.n_chunks, rt0, rt1);
-    const int64_t n_all = rt1 * kWaveSamples < n_cnt ? rt1 * kWaveSamples : n_cnt;
-    const int64_t first = rt0 * kWaveSamples + chunk * (kBinChunk * 256);
-    if (first >= n_all) return;
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) s_cnt[b] = 0;
-    __syncthreads();
-    // 1. this thread's samples: entries, blend weights, gradient; rank of every item among the workgroup's items of its list
-    uint32_t idx[kBinChunk][8], rank[kBinChunk][8];
-    float w[kBinChunk][8];
-    float4 g[kBinChunk];
-#pragma unroll
-    for (int sc = 0; sc < kBinChunk; ++sc) {
-        const int64_t i = first + sc * 256 + threadIdx.x;
-        if (i < n_all) {
-            float xn[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) xn[d] = args.positions[3 * i + d];
-            LevelPrep p;
-            hash_prep(m, xn, p);
-            g[sc] = reinterpret_cast<const float4 *>(args.dX)[(int64_t)l * args.Np + i];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                idx[sc][c] = p.off[c] >> 3;                          // entry inside the level
-                w[sc][c] = ((c & 1) ? p.wxy[(c >> 1) & 1].y : p.wxy[(c >> 1) & 1].x) * p.wz[c >> 2];
-                rank[sc][c] = atomicAdd(&s_cnt[idx[sc][c] >> kBinEntriesLog2], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    // 2. where each list's run starts in the staging buffer (exclusive scan, one wave) ...
-    if (threadIdx.x < 64) {
-        uint32_t run = 0;
-        for (uint32_t b0 = 0; b0 < nb; b0 += 64) {
-            const uint32_t b = b0 + threadIdx.x;
-            const uint32_t c = b < nb ? s_cnt[b] : 0u;
-            uint32_t incl = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d, 64);
-                if ((int)threadIdx.x >= d) incl += t;
-            }
-            if (b < nb) s_off[b] = run + incl - c;
-            run += __shfl(incl, 63, 64);
-        }
-        if (threadIdx.x == 0) s_total = run;
-    }
-    __syncthreads();
-    // ... and in the list itself: one returning add per list and workgroup; s_cnt becomes (slot in the list) - (position in the staging buffer)
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) {
-        const uint32_t c = s_cnt[b];
-        const uint32_t base = c ? atomicAdd(&args.cursors[(size_t)lk * kMaxBins + b], c) : 0u;
-        s_cnt[b] = base - s_off[b];
-    }
-    // 3. items into the staging buffer, list by list
-#pragma unroll
-    for (int sc = 0; sc < kBinChunk; ++sc) {
-        const int64_t i = first + sc * 256 + threadIdx.x;
-        if (i < n_all) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t b = idx[sc][c] >> kBinEntriesLog2, pos = s_off[b] + rank[sc][c];
-                const float v[4] = {w[sc][c] * g[sc].x, w[sc][c] * g[sc].y, w[sc][c] * g[sc].z, w[sc][c] * g[sc].w};
-                s_stage[pos] = pack_item(v, idx[sc][c] & (kBinEntries - 1u));
-                s_binof[pos] = (uint16_t)b;
-            }
-        }
-    }
-    __syncthreads();
-    // 4. out: consecutive lanes write consecutive slots of a list
-    float4 *const lists = args.items + (size_t)lk * nb * args.cap;      // every binned level has the same size (2^k, checked by the host)
-    const uint32_t total = s_total;
-    for (uint32_t p = threadIdx.x; p < total; p += 256) {
-        const uint32_t b = s_binof[p], slot = s_cnt[b] + p;
-        const float4 it = s_stage[p];
-        if (slot < args.cap) {
-            lists[(size_t)b * args.cap + slot] = it;
-        } else {                                                 // the list is full: straight to the gradient
-            const uint32_t bits[4] = {__float_as_uint(it.x), __float_as_uint(it.y), __float_as_uint(it.z), __float_as_uint(it.w)};
-            const uint32_t e = (bits[0] & 7u) | ((bits[1] & 7u) << 3) | ((bits[2] & 7u) << 6) | ((bits[3] & 7u) << 9);
-            float *dst = args.g_table + ((size_t)(m.offset + b * kBinEntries + e) << 2);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float v = __uint_as_float(bits[k] & ~7u);
-                if (v != 0.f) atomicAdd(dst + k, v);
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kBinThreadsB) bin_accumulate_kernel(const BinArgs args) {
-    __shared__ double s_sum[kBinEntries * 4];
-    const int lk = blockIdx.y, l = lk + args.level0;
-    const LevelMeta m = args.levels[l];
-    const uint32_t nb = m.size >> kBinEntriesLog2, b = blockIdx.x;
-    if (b >= nb) return;
-    uint32_t count = args.cursors[(size_t)lk * kMaxBins + b];
-    if (count == 0) return;
-    if (count > args.cap) count = args.cap;
-    for (uint32_t e = threadIdx.x; e < kBinEntries * 4; e += kBinThreadsB) s_sum[e] = 0.0;
-    __syncthreads();
-    const float4 *list = args.items + ((size_t)lk * nb + b) * args.cap;
-    constexpr int U = 4;                                         // items in flight per lane
-    for (uint32_t i0 = threadIdx.x; i0 < count; i0 += kBinThreadsB * U) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        v4f it[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t i = i0 + u * kBinThreadsB;
-            it[u] = reinterpret_cast<const v4f *>(list)[i < count ? i : count - 1u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (i0 + u * kBinThreadsB >= count) break;
-            const float f0 = it[u][0], f1 = it[u][1], f2 = it[u][2], f3 = it[u][3];     // (__builtin_bit_cast straight from a vector element reads element 0)
-            const uint32_t b0 = __float_as_uint(f0), b1 = __float_as_uint(f1), b2 = __float_as_uint(f2), b3 = __float_as_uint(f3);
-            const uint32_t e = (b0 & 7u) | ((b1 & 7u) << 3) | ((b2 & 7u) << 6) | ((b3 & 7u) << 9);
-            double *dst = s_sum + e * 4;
-            atomicAdd(dst, (double)__uint_as_float(b0 & ~7u));
-            atomicAdd(dst + 1, (double)__uint_as_float(b1 & ~7u));
-            atomicAdd(dst + 2, (double)__uint_as_float(b2 & ~7u));
-            atomicAdd(dst + 3, (double)__uint_as_float(b3 & ~7u));
-        }
-    }
-    __syncthreads();
-    // this bin's sums into the gradient: plain read-modify-writes (nothing else touches these entries at this time)
-    float *const out = args.g_table + (((size_t)m.offset + (size_t)b * kBinEntries) << 2);
-    for (uint32_t i = threadIdx.x; i < kBinEntries * 4; i += kBinThreadsB) {
-        const float a = (float)s_sum[i];
-        if (a != 0.f) {
-            out[i] += a;
-        }
-    }
-}
-
-// Reference form of the scatter (MNF_HASH_BWD_SIMPLE=1, debugging and A/B timing): one lane per sample, one atomic per
-// corner and feature, no run merging.
-__global__ void __launch_bounds__(256) hash_bwd_simple_kernel(const HashBwdArgs args) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count_here(args.n, args.n_dev)) return;
-    float xn[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) xn[d] = args.positions[3 * i + d];
-    const int l = blockIdx.y + args.level0;
-    const LevelMeta m = args.levels[l];
-    float *const g_dst = l < args.repl_levels ? args.repl + (size_t)(blockIdx.x % kReplicas) * args.repl_floats : args.g_table;
-    LevelPrep p;
-    hash_prep(m, xn, p);
-    const float4 g = reinterpret_cast<const float4 *>(args.dX)[(int64_t)l * args.Np + i];
-#pragma unroll
-    for (int corner = 0; corner < 8; ++corner) {
-        const float w = ((corner & 1) ? p.wxy[(corner >> 1) & 1].y : p.wxy[(corner >> 1) & 1].x) * p.wz[corner >> 2];
-        float *dst = g_dst + (size_t)p.base * 4 + (p.off[corner] >> 1);   // byte offset of the fp16 entry / 2 == float index inside the level
-        const float v[4] = {w * g.x, w * g.y, w * g.z, w * g.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (v[k] != 0.f) atomicAdd(dst + k, v[k]);
-    }
-}
 
 // ------------------------------------------------------------------ host side: transposed fragments and job table
 enum KMapT { T_NATURAL, T_ACC };
@@ -929,14 +473,16 @@ static TrainTables build_tables(int C) {
     return tt;
 }
 
+// the instantiated shapes (neurons, hidden layers); tools/build_variants.sh builds one
+#ifdef MNF_DEV_ONLY_128x2
+#define MNF_SHAPES(X) X(128, 2)
+#else
+#define MNF_SHAPES(X) X(128, 1) X(128, 2) X(128, 3) X(128, 4) X(64, 1) X(64, 2) X(64, 3) X(64, 4)
+#endif
+
 static bool tables_for(int W, int NH, int C, TrainTables &tt) {
 #define MNF_CASE(w, nh) if (W == w && NH == nh) { tt = build_tables<w, nh>(C); return true; }
-#ifdef MNF_DEV_ONLY_128x2
-    MNF_CASE(128, 2)
-#else
-    MNF_CASE(128, 1) MNF_CASE(128, 2) MNF_CASE(128, 3) MNF_CASE(128, 4)
-    MNF_CASE(64, 1) MNF_CASE(64, 2) MNF_CASE(64, 3) MNF_CASE(64, 4)
-#endif
+    MNF_SHAPES(MNF_CASE)
 #undef MNF_CASE
     return false;
 }
@@ -965,7 +511,7 @@ struct TrainState {
     // the hash-table scatter (float atomics, memory-side) runs beside the weight-gradient GEMMs (matrix cores + streaming loads)
     // on a second stream of the handle: both only depend on the backward-data kernel
     hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_entry = nullptr;
+    hipEvent_t ev_join = nullptr, ev_entry = nullptr;
     hipEvent_t ev_chunk[4] = {nullptr, nullptr, nullptr, nullptr};      // behind each backward-data launch of the chunked pipeline
     // ... and the binned part of the scatter (streams through HBM and LDS) beside the walk (memory-side atomics) on a third
     hipStream_t side2 = nullptr;
@@ -1009,18 +555,15 @@ static int ensure_train_state(mnf_field_t f) {
     if (e == hipSuccess) e = hipMemcpy(ts->d_groups, ts->tt.groups.data(), ts->tt.groups.size() * sizeof(WgradGroup), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ts->d_fragT_src, ts->tt.fragT.data(), ts->tt.fragT.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ts->d_jobs, ts->tt.jobs.data(), ts->tt.jobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&ts->d_bin_cursors, (size_t)16 * kMaxBins * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&ts->d_bin_cursors, (size_t)kScatterCursors * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&ts->d_sh_slot, sh_slot.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(ts->d_sh_slot, sh_slot.data(), sh_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     // side streams: the process-wide ones (common.h shared_side_stream), not a pair per train state
     ts->side = shared_side_stream(0);
     ts->side2 = shared_side_stream(1);
     if (!ts->side || !ts->side2) { delete ts; return MNF_ERR_HIP; }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ts->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ts->ev_join, hipEventDisableTiming);
-    for (int c = 0; c < 4 && e == hipSuccess; ++c) e = hipEventCreateWithFlags(&ts->ev_chunk[c], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ts->ev_entry, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ts->ev_join2, hipEventDisableTiming);
+    for (hipEvent_t *ev : {&ts->ev_join, &ts->ev_entry, &ts->ev_join2, &ts->ev_chunk[0], &ts->ev_chunk[1], &ts->ev_chunk[2], &ts->ev_chunk[3]})
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         set_error("train: %s", hipGetErrorString(e));
         delete ts;
@@ -1033,46 +576,21 @@ static int ensure_train_state(mnf_field_t f) {
 void free_train_state_impl(mnf_field_t f) {
     TrainState *ts = reinterpret_cast<TrainState *>(f->train_state);
     if (!ts) return;
-    if (ts->d_fragT_src) (void)hipFree(ts->d_fragT_src);
-    if (ts->d_fragT) (void)hipFree(ts->d_fragT);
-    if (ts->d_jobs) (void)hipFree(ts->d_jobs);
-    if (ts->d_groups) (void)hipFree(ts->d_groups);
-    if (ts->d_qtable) (void)hipFree(ts->d_qtable);
-    if (ts->d_partials) (void)hipFree(ts->d_partials);
-    if (ts->d_bin_cursors) (void)hipFree(ts->d_bin_cursors);
-    if (ts->d_sh_slot) (void)hipFree(ts->d_sh_slot);
-    if (ts->ev_fork) (void)hipEventDestroy(ts->ev_fork);
-    if (ts->ev_join) (void)hipEventDestroy(ts->ev_join);
-    for (int c = 0; c < 4; ++c) if (ts->ev_chunk[c]) (void)hipEventDestroy(ts->ev_chunk[c]);
-    if (ts->ev_entry) (void)hipEventDestroy(ts->ev_entry);
-    if (ts->ev_join2) (void)hipEventDestroy(ts->ev_join2);
+    for (void *p : {(void *)ts->d_fragT_src, (void *)ts->d_fragT, (void *)ts->d_jobs, (void *)ts->d_groups, (void *)ts->d_qtable, (void *)ts->d_partials,
+                    (void *)ts->d_bin_cursors, (void *)ts->d_sh_slot})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : {ts->ev_join, ts->ev_entry, ts->ev_join2, ts->ev_chunk[0], ts->ev_chunk[1], ts->ev_chunk[2], ts->ev_chunk[3]})
+        if (ev) (void)hipEventDestroy(ev);
     delete ts;
     f->train_state = nullptr;
 }
 
 struct WsView {
     half_t *act; uint8_t *masks; float *dX, *xn, *repl;
-    float4 *bin_items;     // item lists of the binned scatter (levels kBinLevel0Default .. 15): part of the caller's workspace since round 4 (ADVICE r03:
-    size_t bin_items_n;    // they were ~720 B per sample of raw hipMalloc per train state, invisible to the caller's allocator and grown mid-step)
+    float4 *bin_items;     // item lists of the binned scatter: part of the caller's workspace since round 4 (they were ~720 B per sample of raw
+    size_t bin_items_n;    // hipMalloc per train state, invisible to the caller's allocator and grown mid-step)
     int64_t Np, bytes;
 };
-
-// the binned scatter's plan for an upper bound of n samples: levels [first, 16) (all hashed, one size, whole bins), lists per level, items per list
-constexpr int kBinLevel0Default = 12;      // measured: round 3 (tools/r03_bins_step.sh, profiles/r03_bins_step_*.txt) the step time was flat from 10 to 12, worse below and above (11 then);
-                                           // round 4, with wgrad's lighter traffic, 12 is 60 us ahead of 11 at 1.0 M samples (3.393 -> 3.327 ms, four alternations on one box) and equal at 0.25 M
-static void bin_plan(const mnf_field_s *f, int64_t n, int want, int &first_binned, uint32_t &nb, uint32_t &cap) {
-    first_binned = 16; nb = 0; cap = 0;
-    if (n < 8192) return;                    // small batches: the walk alone (pass B costs ~20 us whatever it is given)
-    for (int l = 15; l >= want && l >= 0; --l) {
-        const LevelMeta &lm = f->levels[l];
-        if (!lm.hashed || lm.size < kBinEntries || (lm.size & (lm.size - 1u)) || lm.size != f->levels[15].size || (lm.size >> kBinEntriesLog2) > (uint32_t)kMaxBins) break;
-        first_binned = l;
-    }
-    if (first_binned == 16) return;
-    nb = f->levels[15].size >> kBinEntriesLog2;
-    const uint64_t per_list = (uint64_t)n * 8 / nb;
-    cap = (uint32_t)(per_list + per_list / 8 + 2048);      // a uniform hash fills the lists evenly; the excess of a full one goes to the atomics
-}
 
 static WsView carve_train(const TrainTables &tt, const mnf_field_s *f, void *base, int64_t n) {
     WsView v;
@@ -1083,20 +601,12 @@ static WsView carve_train(const TrainTables &tt, const mnf_field_s *f, void *bas
     v.masks = (uint8_t *)take((size_t)v.Np * tt.mask_bytes);      // [tile][lane] records
     v.dX = (float *)take((size_t)v.Np * 64 * 4);
     v.xn = (float *)take((size_t)v.Np * 3 * 4);
-    v.repl = (float *)take((size_t)kReplicas * kReplMaxEntries * 4 * sizeof(float));   // private copies of the coarsest levels' gradient (scatter)
-    {
-        int first; uint32_t nb, cap;
-        bin_plan(f, n, kBinLevel0Default, first, nb, cap);
-        v.bin_items_n = (size_t)(16 - first) * nb * cap;
-        v.bin_items = (float4 *)take(v.bin_items_n * sizeof(float4));
-    }
+    const ScatterWorkspace sw = scatter_workspace(f, n);
+    v.repl = (float *)take(sw.repl_bytes);
+    v.bin_items_n = sw.bin_items;
+    v.bin_items = (float4 *)take(v.bin_items_n * sizeof(float4));
     v.bytes = (int64_t)off;
     return v;
-}
-
-template <int W, int NH>
-static void launch_dgrad(const BwdArgs &a, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((dgrad_kernel<W, NH>), dim3(grid), dim3(kThreads), 0, s, a);
 }
 
 int64_t train_workspace_bytes_impl(mnf_field_t f, int64_t n) {
@@ -1116,113 +626,105 @@ int input_grad_view_impl(mnf_field_t f, void *workspace, int64_t n, InputGradVie
     return MNF_OK;
 }
 
+// the handle's train state (built on first use) and the caller's workspace carved for n samples
+static int open_train(mnf_field_t f, const char *who, void *workspace, int64_t workspace_bytes, int64_t n, TrainState *&ts, WsView &v) {
+    if (const int rc = ensure_train_state(f)) return rc;
+    ts = reinterpret_cast<TrainState *>(f->train_state);
+    v = carve_train(ts->tt, f, workspace, n);
+    if (!workspace || workspace_bytes < v.bytes) {
+        set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)v.bytes);
+        return MNF_ERR_WORKSPACE;
+    }
+    return MNF_OK;
+}
+
 int forward_train_impl(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream, bool deterministic) {
     MNF_REQUIRE(f && f->params_loaded, "field_forward_train: parameters not loaded");
     MNF_REQUIRE(io.n >= 0, "field_forward_train: negative n");
     if (io.n == 0) return MNF_OK;
-    int rc = ensure_train_state(f);
-    if (rc) return rc;
-    TrainState *ts = reinterpret_cast<TrainState *>(f->train_state);
-    WsView v = carve_train(ts->tt, f, workspace, io.n);
-    if (!workspace || workspace_bytes < v.bytes) {
-        set_error("field_forward_train: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)v.bytes);
-        return MNF_ERR_WORKSPACE;
-    }
+    TrainState *ts = nullptr;
+    WsView v;
+    if (const int rc = open_train(f, "field_forward_train", workspace, workspace_bytes, io.n, ts, v)) return rc;
     TrainBuf tb = {v.act, v.masks, v.Np, ts->tt.rows};
     return launch_field_impl(f, io, false, stream, &tb);
 }
 
-int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_dev, const float *d_rgb, const float *d_density,
-                  const float *d_sem, const float *rgb, const float *density, void *workspace, int64_t workspace_bytes, float loss_scale,
-                  float *g_base, float *g_head, float *g_sem, bool zero_grads, bool positions_normalized, bool deterministic, hipStream_t s) {
-    FactoredGrad fg = {nullptr, nullptr, nullptr, nullptr};
-    const bool factored = take_factored_output_gradient(fg);      // first of all: taken (and cleared) on every path out of this call
+// ------------------------------------------------------------------ the backward, stage by stage (backward_impl runs them top to bottom)
+// no parameter gradients (the fused train render with frozen parameters, mnf_train_render_backward_rays): the output gradients and dgrad run as ever and leave dX
+// and the activation gradients in the workspace; no weight gradients, no hash scatter, no side stream
+static bool is_frozen(const BackwardCall &c) { return !c.g_base && !c.g_head && !c.g_sem; }
+
+static int bwd_check_and_zero(mnf_field_t f, const BackwardCall &c) {
     MNF_REQUIRE(f && f->params_loaded, "field_backward: parameters not loaded");
-    MNF_REQUIRE(n >= 0 && loss_scale > 0.f, "field_backward: bad arguments");
-    // all three NULL: no parameter gradients (the fused train render with frozen parameters, mnf_train_render_backward_rays): the output gradients and dgrad
-    // run as ever and leave dX and the activation gradients in the workspace; no weight gradients, no hash scatter, no side stream
-    const bool frozen = !g_base && !g_head && !g_sem;
-    MNF_REQUIRE(frozen || (g_base && g_head && g_sem), "field_backward: null gradient buffer");
-    if (zero_grads && !frozen) {
-        MNF_HIP(hipMemsetAsync(g_base, 0, (size_t)f->n_base * 4, s));
-        MNF_HIP(hipMemsetAsync(g_head, 0, (size_t)f->n_head * 4, s));
-        MNF_HIP(hipMemsetAsync(g_sem, 0, (size_t)f->n_sem * 4, s));
+    MNF_REQUIRE(c.n >= 0 && c.loss_scale > 0.f, "field_backward: bad arguments");
+    const bool frozen = is_frozen(c);
+    MNF_REQUIRE(frozen || (c.g_base && c.g_head && c.g_sem), "field_backward: null gradient buffer");
+    if (c.zero_grads && !frozen) {
+        MNF_HIP(hipMemsetAsync(c.g_base, 0, (size_t)f->n_base * 4, c.stream));
+        MNF_HIP(hipMemsetAsync(c.g_head, 0, (size_t)f->n_head * 4, c.stream));
+        MNF_HIP(hipMemsetAsync(c.g_sem, 0, (size_t)f->n_sem * 4, c.stream));
     }
-    if (n == 0) return MNF_OK;
-    MNF_REQUIRE(positions && d_density && rgb && density && (factored || (d_rgb && d_sem)), "field_backward: null pointer");
-    int rc = ensure_train_state(f);
-    if (rc) return rc;
-    TrainState *ts = reinterpret_cast<TrainState *>(f->train_state);
-    WsView v = carve_train(ts->tt, f, workspace, n);
-    if (!workspace || workspace_bytes < v.bytes) {
-        set_error("field_backward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)v.bytes);
-        return MNF_ERR_WORKSPACE;
-    }
-    // The scatter's replica buffers are zeroed on the side stream while the backward-data kernel runs (behind the caller's earlier work:
-    // the workspace may have served another call on this stream a moment ago), not between that kernel and the scatter.
-    uint32_t repl_entries = 0;
-    int repl_levels = 0;
-    for (int l = 0; l < 16; ++l) {   // the leading dense levels while they stay small
-        if (f->levels[l].hashed || f->levels[l].offset != repl_entries || repl_entries + f->levels[l].size > kReplMaxEntries) break;
-        repl_entries += f->levels[l].size;
-        repl_levels = l + 1;
-    }
-    if (!frozen) {
-        MNF_HIP(hipEventRecord(ts->ev_entry, s));
-        MNF_HIP(hipStreamWaitEvent(ts->side, ts->ev_entry, 0));
-    }
-    if (repl_levels && !deterministic && !frozen) MNF_HIP(hipMemsetAsync(v.repl, 0, (size_t)kReplicas * repl_entries * 4 * sizeof(float), ts->side));
+    MNF_REQUIRE(c.n == 0 || (c.positions && c.d_density && c.rgb && c.density && (c.factored.w || (c.d_rgb && c.d_sem))), "field_backward: null pointer");
+    return MNF_OK;
+}
+
+// The scatter's replica buffers are zeroed on the side stream while the backward-data kernel runs (behind the caller's earlier work:
+// the workspace may have served another call on this stream a moment ago), not between that kernel and the scatter.
+static int bwd_fork(mnf_field_t f, const BackwardCall &c, TrainState *ts, const WsView &v) {
+    MNF_HIP(hipEventRecord(ts->ev_entry, c.stream));
+    MNF_HIP(hipStreamWaitEvent(ts->side, ts->ev_entry, 0));
+    return scatter_begin(f, v.repl, c.deterministic, ts->side);
+}
+
+// Chunked pipeline (float-atomic mode, large batches): the backward-data kernel is launched for contiguous ranges of tiles and the scatter of a
+// range (walk on the side stream, pass A of the bins on the third) starts behind ITS launch, beside the next range's dgrad: dgrad writes activations
+// through the matrix cores and HBM stores, the scatter is bound by the memory-side atomic unit — the two overlap, and only the last range's scatter
+// (and the weight gradients, which read every range) is left behind the last dgrad.  One range = the old schedule (deterministic mode: its grouping
+// of partial sums must not change).
+static int dgrad_ranges(const BackwardCall &c) {
+    static const int chunks_env = diag_env("MNF_BWD_CHUNKS") ? atoi(diag_env("MNF_BWD_CHUNKS")) : 0;
+    if (c.deterministic || is_frozen(c)) return 1;      // (the ranges exist to start a scatter early: without one, one launch)
+    if (chunks_env >= 1 && chunks_env <= 4) return chunks_env;
+    return c.n >= ((int64_t)1 << 18) ? 2 : 1;           // measured (profiles/r04_bwd_chunks.txt): 5.77 / 5.52 / 5.60 ms per step with 1 / 2 / 4 ranges.
+}
+
+// gather_fragsT (which also clears the scatter's list cursors, in front of the fork points), the normalised positions, then dgrad range by range with
+// ev_chunk[k] recorded behind range k: its scatter may start (the weight gradients stay on the caller's stream)
+static int bwd_dgrad(mnf_field_t f, const BackwardCall &c, TrainState *ts, const WsView &v, int n_chunks) {
+    hipStream_t s = c.stream;
+    const int64_t n = c.n;
     // transposed fp16 weight fragments from the handle's forward fragments (the parameters of the last set_params)
     const int64_t n_frag = (int64_t)ts->tt.fragT.size();
-    hipLaunchKernelGGL(gather_fragsT_kernel, dim3((unsigned)ceil_div(n_frag > 16 * kMaxBins ? n_frag : (int64_t)16 * kMaxBins, 256)), dim3(256), 0, s, ts->d_fragT_src,
-                       reinterpret_cast<const half_t *>(f->d_frags), ts->d_fragT, n_frag, ts->d_bin_cursors, 16 * kMaxBins);
+    hipLaunchKernelGGL(gather_fragsT_kernel, dim3((unsigned)ceil_div(n_frag > kScatterCursors ? n_frag : (int64_t)kScatterCursors, 256)), dim3(256), 0, s, ts->d_fragT_src,
+                       reinterpret_cast<const half_t *>(f->d_frags), ts->d_fragT, n_frag, ts->d_bin_cursors, kScatterCursors);
     BwdArgs a;
-    a.fg = fg;
+    a.fg = c.factored;
     a.fragsT = reinterpret_cast<const half8 *>(ts->d_fragT);
-    a.d_rgb = d_rgb; a.d_sigma = d_density; a.d_sem = d_sem; a.rgb = rgb; a.sigma = density;
-    a.dX = v.dX; a.n = n; a.n_dev = n_dev; a.C = f->cfg.num_semantic_classes; a.loss_scale = loss_scale;
+    a.d_rgb = c.d_rgb; a.d_sigma = c.d_density; a.d_sem = c.d_sem; a.rgb = c.rgb; a.sigma = c.density;
+    a.dX = v.dX; a.n = n; a.n_dev = c.n_dev; a.C = f->cfg.num_semantic_classes; a.loss_scale = c.loss_scale;
     a.train = {v.act, v.masks, v.Np, ts->tt.rows};
-    // Chunked pipeline (float-atomic mode, large batches): the backward-data kernel is launched for four contiguous ranges of tiles and the scatter of a
-    // range (walk on the side stream, pass A of the bins on the third) starts behind ITS launch, beside the next range's dgrad: dgrad writes activations
-    // through the matrix cores and HBM stores, the scatter is bound by the memory-side atomic unit — the two overlap, and only the last range's scatter
-    // (and the weight gradients, which read every range) is left behind the last dgrad.  One range = the old schedule (deterministic mode: its grouping
-    // of partial sums must not change).
-    static const int chunks_env = diag_env("MNF_BWD_CHUNKS") ? atoi(diag_env("MNF_BWD_CHUNKS")) : 0;
-    // measured (profiles/r04_bwd_chunks.txt): 5.77 / 5.52 / 5.60 ms per step with 1 / 2 / 4 ranges.
-    int n_chunks = (!deterministic && n >= ((int64_t)1 << 18)) ? 2 : 1;
-    if (chunks_env >= 1 && chunks_env <= 4 && !deterministic) n_chunks = chunks_env;
-    if (frozen) n_chunks = 1;      // (the ranges exist to start a scatter early: without one, one launch)
-    if (!positions_normalized) {   // (the train step's forward hands over normalised positions already: FieldIO::xn_out)
-        const float *ab = f->cfg.aabb;
-        const int64_t blocks = ceil_div(3 * n, 256);
-        hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, positions, n, n_dev, ab[0], ab[1], ab[2],
-                           ab[3], ab[4], ab[5], v.xn);
-    }
-    int grid = 256;
+    if (!c.positions_normalized) scatter_normalize(f, c.positions, n, c.n_dev, v.xn, s);   // (the train step's forward hands over normalised positions already: FieldIO::xn_out)
     const int64_t chunk_tiles_max = ceil_div(ceil_div(n, kWaveSamples), n_chunks) + 1;      // tiles of one range, at most
-    const int64_t wgs = ceil_div(chunk_tiles_max, kWavesPerBlock);
-    if (wgs < grid) grid = (int)wgs;
+    const int grid = (int)std::min<int64_t>(256, ceil_div(chunk_tiles_max, kWavesPerBlock));
     const int W = f->cfg.neurons, NH = f->cfg.layers;
+    const bool frozen = is_frozen(c);
     bool ok = false;
     const int prof_dgrad = prof_start("dgrad", s);
-    for (int c = 0; c < n_chunks; ++c) {
-        a.chunk = c; a.n_chunks = n_chunks;
-#define MNF_CASE(w, nh) if (W == w && NH == nh) { launch_dgrad<w, nh>(a, grid, s); ok = true; }
-#ifdef MNF_DEV_ONLY_128x2
-        MNF_CASE(128, 2)
-#else
-        MNF_CASE(128, 1) MNF_CASE(128, 2) MNF_CASE(128, 3) MNF_CASE(128, 4)
-        MNF_CASE(64, 1) MNF_CASE(64, 2) MNF_CASE(64, 3) MNF_CASE(64, 4)
-#endif
+    for (int k = 0; k < n_chunks; ++k) {
+        a.chunk = k; a.n_chunks = n_chunks;
+#define MNF_CASE(w, nh) if (W == w && NH == nh) { hipLaunchKernelGGL((dgrad_kernel<w, nh>), dim3(grid), dim3(kThreads), 0, s, a); ok = true; }
+        MNF_SHAPES(MNF_CASE)
 #undef MNF_CASE
-        if (!frozen) MNF_HIP(hipEventRecord(ts->ev_chunk[c], s));      // ---- fork point of range c: its scatter may start (the weight gradients stay on the caller's stream)
+        if (!frozen) MNF_HIP(hipEventRecord(ts->ev_chunk[k], s));
     }
     prof_stop(prof_dgrad, s);
     MNF_REQUIRE(ok, "field_backward: unsupported shape");
-    rc = launch_status("dgrad_kernel");
-    if (rc || frozen) return rc;
-    hipStream_t ss = ts->side;
-    // weight gradients
+    return launch_status("dgrad_kernel");
+}
+
+static int bwd_wgrad(const BackwardCall &c, TrainState *ts, const WsView &v) {
+    hipStream_t s = c.stream;
+    const bool deterministic = c.deterministic;
     const int n_groups = (int)ts->tt.groups.size();
     // enough sample chunks to fill the chip with waves (the loop is load-latency bound; 2 x 2 blocking leaves room for
     // ~3 waves per SIMD), but at least 16 tiles per wave so the final atomics stay negligible (sized on the upper bound `n`)
@@ -1251,314 +753,53 @@ int backward_impl(mnf_field_t f, const float *positions, int64_t n, const int64_
     if (!no_wgrad) {
         ProfScope ps("wgrad", s);
         hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(ceil_div(n_groups, 4) * split)), dim3(256), 0, s, ts->d_jobs, ts->d_groups, n_groups,
-                           split, v.act, n, n_dev, ts->tt.rows, 1.0f / loss_scale, g_base, g_head, g_sem, partials);
+                           split, v.act, c.n, c.n_dev, ts->tt.rows, 1.0f / c.loss_scale, c.g_base, c.g_head, c.g_sem, partials);
         if (partials)
             hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div((int64_t)n_groups * 4 * 1024, 256)), dim3(256), 0, s, ts->d_jobs, ts->d_groups,
-                               n_groups, split, (const float *)partials, 1.0f / loss_scale, g_base, g_head, g_sem);
+                               n_groups, split, (const float *)partials, 1.0f / c.loss_scale, c.g_base, c.g_head, c.g_sem);
     }
-    rc = launch_status("wgrad_kernel");
-    if (rc) return rc;
-    // hash-table gradient (side stream)
-    HashBwdArgs hb;
-    hb.positions = positions_normalized ? positions : v.xn; hb.dX = v.dX; hb.Np = v.Np; hb.g_table = g_base + f->n_base_mlp; hb.n = n; hb.n_dev = n_dev;
-    std::memcpy(hb.aabb, f->cfg.aabb, sizeof(hb.aabb));
-    std::memcpy(hb.levels, f->levels, sizeof(hb.levels));
-    int n_levels = 16;
-    hb.level0 = 0; hb.chunk = 0; hb.n_chunks = 1;
-    if (const char *e = diag_env("MNF_HASH_BWD_LEVELS")) { int lo = 0, hi = 16; if (sscanf(e, "%d,%d", &lo, &hi) == 2) { hb.level0 = lo; n_levels = hi - lo; } }
-    // replicated coarse levels (their own region of the workspace, zeroed above)
-    hb.repl_levels = repl_levels;
-    hb.repl_floats = repl_entries * 4;
-    hb.repl = v.repl;
-    const size_t repl_bytes = (size_t)kReplicas * hb.repl_floats * sizeof(float);
-    hb.flush_count = nullptr;
-    hb.q_table = nullptr; hb.q_repl = nullptr; hb.q_bad = nullptr;
-    const size_t q_table_words = (size_t)f->table_entries * 4, q_repl_words = (size_t)kReplicas * kReplMaxEntries * 4;
-    if (deterministic) {
-        if (!ts->d_qtable) MNF_HIP(hipMalloc((void **)&ts->d_qtable, (q_table_words + q_repl_words + 8) * sizeof(unsigned long long)));
-        hb.q_table = ts->d_qtable; hb.q_repl = ts->d_qtable + q_table_words; hb.q_bad = hb.q_repl + q_repl_words;
-    }
-#ifdef MNF_DIAG
-    static unsigned long long *d_flush = nullptr;
-    if (diag_env("MNF_SCATTER_COUNT")) {
-        if (!d_flush) MNF_HIP(hipMalloc((void **)&d_flush, 16 * sizeof(unsigned long long)));
-        MNF_HIP(hipMemsetAsync(d_flush, 0, 16 * sizeof(unsigned long long), ss));
-        hb.flush_count = d_flush;
-    }
-#endif
-    static const bool simple = diag_env("MNF_HASH_BWD_SIMPLE") != nullptr;   // debugging aid: one atomic per lane, corner and feature
-    // levels [first_binned, 16): through the bins (all of them hashed tables of one size that whole bins tile); the rest: the walk
-    int first_binned = 16;
-    uint32_t nb_plan = 0, cap = 0;
-    if (!deterministic && !simple && n_levels == 16) {
-        int want = kBinLevel0Default;
-        if (const char *e = diag_env("MNF_BIN_LEVEL0")) want = atoi(e);
-        bin_plan(f, n, want, first_binned, nb_plan, cap);
-        if (const char *e = diag_env("MNF_BIN_CAP")) cap = (uint32_t)atoi(e);     // tests: force the full-list path
-        while (first_binned < 16 && (size_t)(16 - first_binned) * nb_plan * cap > v.bin_items_n) ++first_binned;      // (a diagnostic plan larger than the workspace's)
-    }
-    BinArgs ba;
-    const int n_binned = 16 - first_binned;
-    if (n_binned > 0) {
-        ba.chunk = 0; ba.n_chunks = 1;
-        ba.positions = hb.positions; ba.dX = hb.dX; ba.Np = hb.Np; ba.n = n; ba.n_dev = n_dev; ba.level0 = first_binned; ba.n_levels = n_binned;
-        ba.items = v.bin_items; ba.cursors = ts->d_bin_cursors; ba.cap = cap; ba.g_table = hb.g_table;
-        std::memcpy(ba.levels, f->levels, sizeof(ba.levels));
-        n_levels = first_binned;
-    }
-    MNF_HIP(hipStreamWaitEvent(ss, ts->ev_chunk[0], 0));
-    const int prof_scatter = prof_start("hash_scatter", ss);
-    hb.n_walk_levels = n_levels;
-    int walk_wgs = 8;                                                                   // workgroups per CU of the 256 (gfx950 only: as the field kernel)
-    if (const char *e = diag_env("MNF_WALK_WGS")) walk_wgs = atoi(e);
-    const int64_t range_samples = chunk_tiles_max * kWaveSamples;                        // samples of one range, at most
-    const int64_t walk_full = ceil_div(ceil_div(range_samples, kWalkChunk) * 32, 256) * (n_levels > 0 ? n_levels : 1);
-    const dim3 walk_grid((unsigned)(walk_wgs > 0 && walk_full > (int64_t)256 * walk_wgs ? (int64_t)256 * walk_wgs : (walk_full > 0 ? walk_full : 1)));
-    if (deterministic) {
-        MNF_HIP(hipStreamWaitEvent(ss, ts->ev_chunk[0], 0));
-        MNF_HIP(hipMemsetAsync(hb.q_table, 0, q_table_words * sizeof(unsigned long long), ss));
-        if (hb.repl_levels) MNF_HIP(hipMemsetAsync(hb.q_repl, 0, (size_t)kReplicas * hb.repl_floats * sizeof(unsigned long long), ss));
-        MNF_HIP(hipMemsetAsync(hb.q_bad, 0, sizeof(unsigned long long), ss));
-        hipLaunchKernelGGL(hash_bwd_walk_kernel<true>, walk_grid, dim3(256), 0, ss, hb);
-        if (hb.repl_levels)
-            hipLaunchKernelGGL(fold_replicas_fixed_kernel, dim3((hb.repl_floats + 255) / 256), dim3(256), 0, ss, (const unsigned long long *)hb.q_repl,
-                               hb.repl_floats, hb.q_table);
-        hipLaunchKernelGGL(fixed_to_float_kernel, dim3(4096), dim3(256), 0, ss, reinterpret_cast<const long long *>(hb.q_table), hb.g_table,
-                           (int64_t)q_table_words, (const unsigned long long *)hb.q_bad);
-    } else {
-        if (n_binned > 0) {
-            const uint32_t nb = f->levels[15].size >> kBinEntriesLog2;
-            static const bool same_stream = diag_env("MNF_BIN_SAME_STREAM") != nullptr;     // timing experiments: bins in front of the walk on one stream
-            hipStream_t s2 = same_stream ? ss : ts->side2;
-            MNF_HIP(hipStreamWaitEvent(s2, ts->ev_chunk[0], 0));
-            const int prof_bins = prof_start("hash_scatter_bins", s2);
-            // (list cursors: cleared by gather_fragsT_kernel, in front of the fork)
-            // (Measured and dropped, tools/r03_walk_wgs.sh: pass B level by level or half by half on a fourth stream under the next pass A — 5.8 and 5.6 ms
-            // per step against 5.55-5.6 for one launch each: walk, bins and wgrad together are bound by HBM, the order inside does not matter.)
-            for (int c = 0; c < n_chunks; ++c) {          // pass A range by range, each behind its dgrad; pass B once, behind the last
-                if (c) MNF_HIP(hipStreamWaitEvent(s2, ts->ev_chunk[c], 0));
-                ba.chunk = c; ba.n_chunks = n_chunks;
-                hipLaunchKernelGGL(bin_items_kernel, dim3((unsigned)(ceil_div(range_samples, kBinChunk * 256) * n_binned)), dim3(256), 0, s2, ba);
-            }
-            hipLaunchKernelGGL(bin_accumulate_kernel, dim3(nb, n_binned), dim3(kBinThreadsB), 0, s2, ba);
-            prof_stop(prof_bins, s2);
-            MNF_HIP(hipEventRecord(ts->ev_join2, s2));
-            MNF_HIP(hipStreamWaitEvent(s, ts->ev_join2, 0));
-        }
-        if (simple) {
-            MNF_HIP(hipStreamWaitEvent(ss, ts->ev_chunk[n_chunks - 1], 0));
-            hipLaunchKernelGGL(hash_bwd_simple_kernel, dim3((unsigned)ceil_div(n, 256), n_levels), dim3(256), 0, ss, hb);
-        } else {
-            for (int c = 0; c < n_chunks; ++c) {
-                MNF_HIP(hipStreamWaitEvent(ss, ts->ev_chunk[c], 0));
-                hb.chunk = c; hb.n_chunks = n_chunks;
-                if (n_levels > 0) hipLaunchKernelGGL(hash_bwd_walk_kernel<false>, walk_grid, dim3(256), 0, ss, hb);
-            }
-        }
-        if (hb.repl_levels)
-            hipLaunchKernelGGL(fold_replicas_kernel, dim3((hb.repl_floats + 255) / 256), dim3(256), 0, ss, hb.repl, hb.repl_floats, hb.g_table);
-    }
-    rc = launch_status("hash_bwd_walk_kernel");
-    if (rc) return rc;
-    prof_stop(prof_scatter, ss);
-    rc = launch_status("fold_replicas_kernel");
-#ifdef MNF_DIAG
-    if (hb.flush_count) {      // quad atomics per level of this backward (synchronises: diagnostic only)
-        unsigned long long h[16];
-        MNF_HIP(hipMemcpyAsync(h, hb.flush_count, sizeof(h), hipMemcpyDeviceToHost, ss));
-        MNF_HIP(hipStreamSynchronize(ss));
-        unsigned long long tot = 0;
-        fprintf(stderr, "[mnf scatter] quad atomics per level:");
-        for (int l = 0; l < 16; ++l) { fprintf(stderr, " %llu", h[l]); tot += h[l]; }
-        fprintf(stderr, "  total %llu (upper bound n = %lld samples)\n", tot, (long long)n);
-    }
-#endif
+    return launch_status("wgrad_kernel");
+}
+
+// hash-table gradient (side streams): the walk on `side`, the bins on `side2`
+static int bwd_scatter(mnf_field_t f, const BackwardCall &c, TrainState *ts, const WsView &v, int n_chunks) {
+    const ScatterCall sc = {f, v.dX, c.positions_normalized ? c.positions : v.xn, v.Np, c.n, c.n_dev, c.g_base + f->n_base_mlp, v.repl, v.bin_items, v.bin_items_n,
+                            n_chunks, c.deterministic, c.stream, ts->side, ts->side2, ts->ev_chunk, ts->ev_join2, &ts->d_qtable, ts->d_bin_cursors};
+    return scatter_run(sc);
+}
+
+int backward_impl(mnf_field_t f, const BackwardCall &c) {
+    int rc = bwd_check_and_zero(f, c);
+    if (rc || c.n == 0) return rc;
+    TrainState *ts = nullptr;
+    WsView v;
+    if ((rc = open_train(f, "field_backward", c.workspace, c.workspace_bytes, c.n, ts, v))) return rc;      // carve
+    const bool frozen = is_frozen(c);
+    if (!frozen && (rc = bwd_fork(f, c, ts, v))) return rc;
+    const int n_chunks = dgrad_ranges(c);
+    if ((rc = bwd_dgrad(f, c, ts, v, n_chunks)) || frozen) return rc;
+    if ((rc = bwd_wgrad(c, ts, v))) return rc;
+    if ((rc = bwd_scatter(f, c, ts, v, n_chunks))) return rc;
     // ---- join
-    MNF_HIP(hipEventRecord(ts->ev_join, ss));
-    MNF_HIP(hipStreamWaitEvent(s, ts->ev_join, 0));
+    MNF_HIP(hipEventRecord(ts->ev_join, ts->side));
+    MNF_HIP(hipStreamWaitEvent(c.stream, ts->ev_join, 0));
     return rc;
 }
 
 MNF_DT_END
 
 #ifndef MNF_BF16   // ---- operand-type independent: compiled once
+// fn of the handle's operand type
+#define MNF_BY_TYPE(f, fn, ...) ((f)->cfg.mfma_bf16 ? bf16::fn(__VA_ARGS__) : f16::fn(__VA_ARGS__))
 namespace mnf {
-static thread_local FactoredGrad t_factored = {nullptr, nullptr, nullptr, nullptr};
-void set_factored_output_gradient(const FactoredGrad &fg) { t_factored = fg; }
-bool take_factored_output_gradient(FactoredGrad &fg) {
-    fg = t_factored;
-    t_factored = FactoredGrad{nullptr, nullptr, nullptr, nullptr};
-    return fg.w != nullptr;
-}
-// ------------------------------------------------------------------ optimizer step (pipeline.py:173-178, :531)
-// torch.optim.Adam(lr, betas, eps, weight_decay=0, amsgrad=False) on one flat parameter vector in a single pass
-// (torch's foreach implementation is six passes over the 25 M table entries): lerp of the first moment, addcmul of the
-// second, bias-corrected step.  `any_nan` counts NaN gradients (the reference skips the whole iteration then).
-__global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, int64_t n, float beta1, float beta2, float eps,
-                                                   float step_size, float bc2_sqrt) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - beta1);
-        const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    }
-}
-
-// The same update for a training loop that never synchronises with the host: the step count lives on the device and the whole update is
-// skipped when `skip` is non-zero (non-finite gradients, pipeline.py:520-529; a step that overflowed its sample bounds or rendered
-// no sample, csrc/trainstep.hip).  adam_prepare_kernel advances the count and derives the bias corrections (in double, as the host
-// version does); adam_guarded_kernel optionally mirrors the new parameters from `half_from` on into the field handle's fp16 hash
-// table, so the per-step fp32 -> fp16 conversion pass over the 25 M entries disappears.
-__global__ void adam_prepare_kernel(float *__restrict__ step, const int32_t *__restrict__ skip, float lr, float beta1, float beta2, float *__restrict__ hyper) {
-    const bool sk = skip && *skip != 0;
-    float st = *step;
-    if (!sk) { st += 1.0f; *step = st; }
-    const double bc1 = 1.0 - pow((double)beta1, (double)st), bc2 = 1.0 - pow((double)beta2, (double)st);
-    hyper[0] = (float)((double)lr / bc1); hyper[1] = (float)sqrt(bc2); hyper[2] = sk ? 1.0f : 0.0f;
-}
-
-__global__ void __launch_bounds__(256) adam_guarded_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                           float *__restrict__ v, int64_t n, float beta1, float beta2, float eps,
-                                                           const float *__restrict__ hyper, _Float16 *__restrict__ half_out, int64_t half_from) {
-    const float step_size = hyper[0], bc2_sqrt = hyper[1];
-    if (hyper[2] != 0.0f) return;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - beta1);
-        const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float pn = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-        p[i] = pn;
-        if (half_out && i >= half_from) half_out[i - half_from] = (_Float16)pn;
-    }
-}
-
-// The three parameter vectors of a field in ONE launch each (guard, step counts, update): mnf_field_optimizer_step issued 3 + 3 + 3 launches, most of them ~5 us of nothing.
-struct Adam3 {
-    float *p[3]; const float *g[3]; float *m[3], *v[3]; float *step[3];
-    int64_t n[3];
-};
-// Both passes over the parameter vectors move 16 bytes per lane and access (one thread = one aligned quad of one vector; the up-to-three elements behind the last
-// quad of a vector one by one): with 4-byte accesses the update of the 12.6 M table parameters ran at 2.3 TB/s (167 us of the reference-yaml step's 1.29 ms).
-__device__ __forceinline__ bool quad_of(const Adam3 &a, int64_t q, int &k, int64_t &i0) {
-    const int64_t q0 = (a.n[0] + 3) >> 2, q1 = (a.n[1] + 3) >> 2, q2 = (a.n[2] + 3) >> 2;
-    if (q < q0) { k = 0; i0 = q << 2; return true; }
-    if (q < q0 + q1) { k = 1; i0 = (q - q0) << 2; return true; }
-    if (q < q0 + q1 + q2) { k = 2; i0 = (q - q0 - q1) << 2; return true; }
-    return false;
-}
-__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-__global__ void __launch_bounds__(256) count_nan3_kernel(const Adam3 a, int32_t *__restrict__ count) {
-    int local = 0;
-    const int64_t quads = ((a.n[0] + 3) >> 2) + ((a.n[1] + 3) >> 2) + ((a.n[2] + 3) >> 2);
-    const int64_t stride = (int64_t)blockDim.x * gridDim.x;
-    // four quads per trip, their loads issued together (one 16-byte load in flight per thread read the 50 MB of gradients at 2.3 TB/s)
-    for (int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q0 < quads; q0 += 4 * stride) {
-        float4 x[4];
-        bool fast[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t q = q0 + u * stride;
-            int k = 0; int64_t i0 = 0;
-            const bool in = q < quads && quad_of(a, q, k, i0);
-            const float *g = a.g[k] + i0;
-            fast[u] = in && i0 + 4 <= a.n[k] && aligned16(g);
-            x[u] = fast[u] ? *reinterpret_cast<const float4 *>(g) : float4{0.f, 0.f, 0.f, 0.f};
-            if (in && !fast[u])
-                for (int64_t i = i0; i < a.n[k] && i < i0 + 4; ++i) local += !(fabsf(a.g[k][i]) <= 3.4028234664e38f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            local += !(fabsf(x[u].x) <= 3.4028234664e38f) + !(fabsf(x[u].y) <= 3.4028234664e38f) + !(fabsf(x[u].z) <= 3.4028234664e38f) + !(fabsf(x[u].w) <= 3.4028234664e38f);
-    }
-    if (__ballot(local != 0) != 0ull && local) atomicAdd(count, local);
-}
-__global__ void adam_prepare3_kernel(const Adam3 a, const int32_t *__restrict__ skip, float lr, float beta1, float beta2, float *__restrict__ hyper,
-                                     const int64_t *__restrict__ counts, long long *__restrict__ report) {
-    const int k = threadIdx.x;
-    // the step's report to the host, written straight into pinned host memory: the train step's four counters and its FINAL skip flag (this launch runs behind
-    // the non-finite count).  Two device-to-host copies did this before; each cost the stream ~5 us of copy plus ~18 us of bubble around it.
-    if (report && k >= 3 && k < 8) {
-        report[k - 3] = k < 7 ? (counts ? (long long)counts[k - 3] : 0ll) : (long long)(skip ? *skip : 0);
-        __threadfence_system();
-    }
-    if (k >= 3) return;
-    const bool sk = skip && *skip != 0;
-    float st = *a.step[k];
-    if (!sk) { st += 1.0f; *a.step[k] = st; }
-    const double bc1 = 1.0 - pow((double)beta1, (double)st), bc2 = 1.0 - pow((double)beta2, (double)st);
-    hyper[4 * k] = (float)((double)lr / bc1); hyper[4 * k + 1] = (float)sqrt(bc2); hyper[4 * k + 2] = sk ? 1.0f : 0.0f;
-}
-__global__ void __launch_bounds__(256) adam_guarded3_kernel(const Adam3 a, float beta1, float beta2, float eps, const float *__restrict__ hyper,
-                                                            _Float16 *__restrict__ half_out, int64_t half_from) {
-    if (hyper[2] != 0.0f) return;
-    const int64_t quads = ((a.n[0] + 3) >> 2) + ((a.n[1] + 3) >> 2) + ((a.n[2] + 3) >> 2);
-    auto one = [&](float gi, float &mi, float &vi, float &pi, float step_size, float bc2_sqrt) {      // (the scalar kernel's arithmetic, operation for operation)
-        mi = mi + (gi - mi) * (1.0f - beta1);
-        vi = vi * beta2 + (1.0f - beta2) * gi * gi;
-        pi = pi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    };
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (int64_t)blockDim.x * gridDim.x) {
-        int k; int64_t i0;
-        quad_of(a, q, k, i0);
-        const float step_size = hyper[4 * k], bc2_sqrt = hyper[4 * k + 1];
-        const bool mirror = k == 0 && half_out && i0 >= half_from;
-        if (i0 + 4 <= a.n[k] && aligned16(a.g[k] + i0) && aligned16(a.m[k] + i0) && aligned16(a.v[k] + i0) && aligned16(a.p[k] + i0)) {
-            const float4 g = *reinterpret_cast<const float4 *>(a.g[k] + i0);
-            float4 m = *reinterpret_cast<const float4 *>(a.m[k] + i0), v = *reinterpret_cast<const float4 *>(a.v[k] + i0), p = *reinterpret_cast<const float4 *>(a.p[k] + i0);
-            one(g.x, m.x, v.x, p.x, step_size, bc2_sqrt); one(g.y, m.y, v.y, p.y, step_size, bc2_sqrt);
-            one(g.z, m.z, v.z, p.z, step_size, bc2_sqrt); one(g.w, m.w, v.w, p.w, step_size, bc2_sqrt);
-            *reinterpret_cast<float4 *>(a.m[k] + i0) = m; *reinterpret_cast<float4 *>(a.v[k] + i0) = v; *reinterpret_cast<float4 *>(a.p[k] + i0) = p;
-            if (k == 0 && half_out && i0 < half_from && i0 + 4 > half_from) {      // the quad the mirror starts inside
-                const float pe[4] = {p.x, p.y, p.z, p.w};
-                for (int e = 0; e < 4; ++e) if (i0 + e >= half_from) half_out[i0 + e - half_from] = (_Float16)pe[e];
-            }
-            if (mirror) {
-                _Float16 *h = half_out + (i0 - half_from);
-                if ((reinterpret_cast<uintptr_t>(h) & 7) == 0) {
-                    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                    h4 o; o[0] = (_Float16)p.x; o[1] = (_Float16)p.y; o[2] = (_Float16)p.z; o[3] = (_Float16)p.w;
-                    *reinterpret_cast<h4 *>(h) = o;
-                } else { h[0] = (_Float16)p.x; h[1] = (_Float16)p.y; h[2] = (_Float16)p.z; h[3] = (_Float16)p.w; }
-            }
-        } else {
-            for (int64_t i = i0; i < a.n[k] && i < i0 + 4; ++i) {
-                float mi = a.m[k][i], vi = a.v[k][i], pi = a.p[k][i];
-                one(a.g[k][i], mi, vi, pi, step_size, bc2_sqrt);
-                a.m[k][i] = mi; a.v[k][i] = vi; a.p[k][i] = pi;
-                if (k == 0 && half_out && i >= half_from) half_out[i - half_from] = (_Float16)pi;
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) count_nan_kernel(const float *__restrict__ g, int64_t n, int32_t *__restrict__ count) {
-    int local = 0;
-    // NaN as the reference's guard (pipeline.py:520-529), and +-Inf as well: an overflowed fp16 activation gradient shows up
-    // as Inf, which Adam would turn into NaN parameters one step later
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x) local += !(fabsf(g[i]) <= 3.4028234664e38f);
-    if (__ballot(local != 0) != 0ull && local) atomicAdd(count, local);
-}
-
-
-void free_train_state(mnf_field_t f) {
-    if (f->cfg.mfma_bf16) bf16::free_train_state_impl(f); else f16::free_train_state_impl(f);
-}
+void free_train_state(mnf_field_t f) { MNF_BY_TYPE(f, free_train_state_impl, f); }
 int forward_train(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream, bool deterministic) {
     MNF_REQUIRE(f, "field_forward_train: null handle");
-    return f->cfg.mfma_bf16 ? bf16::forward_train_impl(f, io, workspace, workspace_bytes, stream, deterministic)
-                            : f16::forward_train_impl(f, io, workspace, workspace_bytes, stream, deterministic);
+    return MNF_BY_TYPE(f, forward_train_impl, f, io, workspace, workspace_bytes, stream, deterministic);
 }
-int backward(mnf_field_t f, const float *positions, int64_t n, const int64_t *n_dev, const float *d_rgb, const float *d_density, const float *d_sem,
-             const float *rgb, const float *density, void *workspace, int64_t workspace_bytes, float loss_scale, float *g_base, float *g_head,
-             float *g_sem, bool zero_grads, bool positions_normalized, bool deterministic, hipStream_t stream) {
+int backward(mnf_field_t f, const BackwardCall &c) {
     MNF_REQUIRE(f, "field_backward: null handle");
-    return f->cfg.mfma_bf16 ? bf16::backward_impl(f, positions, n, n_dev, d_rgb, d_density, d_sem, rgb, density, workspace, workspace_bytes, loss_scale,
-                                                  g_base, g_head, g_sem, zero_grads, positions_normalized, deterministic, stream)
-                            : f16::backward_impl(f, positions, n, n_dev, d_rgb, d_density, d_sem, rgb, density, workspace, workspace_bytes, loss_scale,
-                                                 g_base, g_head, g_sem, zero_grads, positions_normalized, deterministic, stream);
+    return MNF_BY_TYPE(f, backward_impl, f, c);
 }
 }  // namespace mnf
 
@@ -1566,7 +807,7 @@ using namespace mnf;
 
 extern "C" int64_t mnf_field_train_workspace_bytes(mnf_field_t f, int64_t n) {
     if (!f) return -1;
-    return f->cfg.mfma_bf16 ? bf16::train_workspace_bytes_impl(f, n) : f16::train_workspace_bytes_impl(f, n);
+    return MNF_BY_TYPE(f, train_workspace_bytes_impl, f, n);
 }
 
 extern "C" int mnf_field_forward_train(mnf_field_t f, const float *positions, const float *directions, int64_t n,
@@ -1577,8 +818,7 @@ extern "C" int mnf_field_forward_train(mnf_field_t f, const float *positions, co
     FieldIO io = {};
     io.mode = 0; io.positions = positions; io.directions = directions; io.n = n;
     io.rgb = rgb; io.density = density; io.sem = sem;
-    return f->cfg.mfma_bf16 ? bf16::forward_train_impl(f, io, workspace, workspace_bytes, as_stream(stream), false)
-                            : f16::forward_train_impl(f, io, workspace, workspace_bytes, as_stream(stream), false);
+    return MNF_BY_TYPE(f, forward_train_impl, f, io, workspace, workspace_bytes, as_stream(stream), false);
 }
 
 extern "C" int mnf_field_forward_train_samples(mnf_field_t f, const float *rays_o, const float *rays_d, const int64_t *ray_indices,
@@ -1591,8 +831,7 @@ extern "C" int mnf_field_forward_train_samples(mnf_field_t f, const float *rays_
     FieldIO io = {};
     io.mode = 1; io.rays_o = rays_o; io.rays_d = rays_d; io.ray_idx64 = ray_indices; io.t_starts = t_starts; io.t_ends = t_ends; io.n = n;
     io.rgb = rgb; io.density = density; io.sem = sem; io.positions_out = positions_out;
-    return f->cfg.mfma_bf16 ? bf16::forward_train_impl(f, io, workspace, workspace_bytes, as_stream(stream), false)
-                            : f16::forward_train_impl(f, io, workspace, workspace_bytes, as_stream(stream), false);
+    return MNF_BY_TYPE(f, forward_train_impl, f, io, workspace, workspace_bytes, as_stream(stream), false);
 }
 
 extern "C" int mnf_field_backward(mnf_field_t f, const float *positions, int64_t n,
@@ -1602,88 +841,10 @@ extern "C" int mnf_field_backward(mnf_field_t f, const float *positions, int64_t
                                   float *g_base, float *g_head, float *g_sem, mnf_stream_t stream) {
     MNF_REQUIRE(f, "field_backward: null handle");
     MNF_REQUIRE(g_base && g_head && g_sem, "field_backward: null gradient buffer");
-    return backward(f, positions, n, nullptr, d_rgb, d_density, d_sem, rgb, density, workspace, workspace_bytes, loss_scale, g_base, g_head, g_sem, true,
-                    false, false, as_stream(stream));
+    BackwardCall c = {};
+    c.positions = positions; c.n = n; c.d_rgb = d_rgb; c.d_density = d_density; c.d_sem = d_sem; c.rgb = rgb; c.density = density; c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes; c.loss_scale = loss_scale; c.g_base = g_base; c.g_head = g_head; c.g_sem = g_sem; c.zero_grads = true; c.stream = as_stream(stream);
+    return backward(f, c);
 }
 
-extern "C" int mnf_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
-                             float beta2, float eps, int32_t step, mnf_stream_t stream) {
-    if (n == 0) return MNF_OK;
-    MNF_REQUIRE(params && grads && exp_avg && exp_avg_sq && step >= 1, "adam_step: bad arguments");
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    const int64_t blocks = ceil_div(n, 256 * 4);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(blocks < 8192 ? (blocks < 1 ? 1 : blocks) : 8192)), dim3(256), 0, as_stream(stream), params,
-                       grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, (float)((double)lr / bc1), (float)std::sqrt(bc2));
-    return launch_status("adam_kernel");
-}
-
-extern "C" int mnf_adam_step_guarded(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
-                                     float beta2, float eps, float *step_dev, const int32_t *skip_dev, float *hyper_dev, void *half_out,
-                                     int64_t half_from, mnf_stream_t stream) {
-    if (n == 0) return MNF_OK;
-    MNF_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_dev && hyper_dev, "adam_step_guarded: bad arguments");
-    MNF_REQUIRE(!half_out || (half_from >= 0 && half_from <= n), "adam_step_guarded: bad fp16 mirror range");
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, step_dev, skip_dev, lr, beta1, beta2, hyper_dev);
-    const int64_t blocks = ceil_div(n, 256 * 4);
-    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)(blocks < 8192 ? (blocks < 1 ? 1 : blocks) : 8192)), dim3(256), 0, s, params, grads, exp_avg,
-                       exp_avg_sq, n, beta1, beta2, eps, (const float *)hyper_dev, reinterpret_cast<_Float16 *>(half_out), half_from);
-    return launch_status("adam_guarded_kernel");
-}
-
-// pipeline.py:520-532 for one model as ONE call: the non-finite-gradient guard over the three parameter vectors, the three Adam updates
-// (skipped on the device when the flag is raised) with the fp16 table mirror, and the handle's MLP fragments re-derived.
-static int optimizer_step_impl(mnf_field_t f, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
-                               float *const *exp_avg_sq_host, float *const *step_dev_host, float lr, float beta1, float beta2, float eps,
-                               int32_t *skip_dev, int32_t count_nonfinite, float *hyper_dev, const int64_t *counts_dev, int64_t *report_host, mnf_stream_t stream) {
-    MNF_REQUIRE(f && params_host && grads_host && exp_avg_host && exp_avg_sq_host && step_dev_host && hyper_dev, "field_optimizer_step: null argument");
-    MNF_REQUIRE(f->params_loaded, "field_optimizer_step: the handle holds no parameters yet (mnf_field_set_params)");
-    const int64_t n[3] = {f->n_base, f->n_head, f->n_sem};
-    Adam3 a;
-    for (int k = 0; k < 3; ++k) {
-        MNF_REQUIRE(n[k] == 0 || (params_host[k] && grads_host[k] && exp_avg_host[k] && exp_avg_sq_host[k] && step_dev_host[k]), "field_optimizer_step: null pointer");
-        a.p[k] = params_host[k]; a.g[k] = grads_host[k]; a.m[k] = exp_avg_host[k]; a.v[k] = exp_avg_sq_host[k]; a.step[k] = step_dev_host[k]; a.n[k] = n[k];
-    }
-    MNF_REQUIRE(n[0] > 0 && n[1] > 0 && n[2] > 0, "field_optimizer_step: empty parameter vector");
-    hipStream_t s = as_stream(stream);
-    const int64_t total = n[0] + n[1] + n[2];
-    if (count_nonfinite) {
-        MNF_REQUIRE(skip_dev, "field_optimizer_step: counting non-finite gradients needs the skip flag");
-        const int64_t blocks = ceil_div(total, 256 * 4 * 4);
-        hipLaunchKernelGGL(count_nan3_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, a, skip_dev);
-    }
-    hipLaunchKernelGGL(adam_prepare3_kernel, dim3(1), dim3(64), 0, s, a, (const int32_t *)skip_dev, lr, beta1, beta2, hyper_dev, counts_dev,
-                       reinterpret_cast<long long *>(report_host));
-    const int64_t blocks = ceil_div(total, 256 * 4 * 2);
-    hipLaunchKernelGGL(adam_guarded3_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, a, beta1, beta2, eps, (const float *)hyper_dev,
-                       reinterpret_cast<_Float16 *>(f->d_table), (int64_t)f->n_base_mlp);
-    int rc = launch_status("adam_guarded3_kernel");
-    if (rc) return rc;
-    return mnf_field_refresh_weights(f, params_host[0], params_host[1], params_host[2], stream);
-}
-
-extern "C" int mnf_field_optimizer_step(mnf_field_t f, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
-                                        float *const *exp_avg_sq_host, float *const *step_dev_host, float lr, float beta1, float beta2, float eps,
-                                        int32_t *skip_dev, int32_t count_nonfinite, float *hyper_dev, mnf_stream_t stream) {
-    return optimizer_step_impl(f, params_host, grads_host, exp_avg_host, exp_avg_sq_host, step_dev_host, lr, beta1, beta2, eps, skip_dev, count_nonfinite, hyper_dev,
-                               nullptr, nullptr, stream);
-}
-
-extern "C" int mnf_field_optimizer_step_report(mnf_field_t f, float *const *params_host, const float *const *grads_host, float *const *exp_avg_host,
-                                               float *const *exp_avg_sq_host, float *const *step_dev_host, float lr, float beta1, float beta2, float eps,
-                                               int32_t *skip_dev, int32_t count_nonfinite, float *hyper_dev, const int64_t *counts_dev, int64_t *report_host,
-                                               mnf_stream_t stream) {
-    MNF_REQUIRE(report_host, "field_optimizer_step_report: null report buffer");
-    return optimizer_step_impl(f, params_host, grads_host, exp_avg_host, exp_avg_sq_host, step_dev_host, lr, beta1, beta2, eps, skip_dev, count_nonfinite, hyper_dev,
-                               counts_dev, report_host, stream);
-}
-
-extern "C" int mnf_count_nan(const float *values, int64_t n, int32_t *count, mnf_stream_t stream) {
-    if (n == 0) return MNF_OK;
-    MNF_REQUIRE(values && count, "count_nan: null pointer");
-    const int64_t blocks = ceil_div(n, 256 * 8);
-    hipLaunchKernelGGL(count_nan_kernel, dim3((unsigned)(blocks < 4096 ? (blocks < 1 ? 1 : blocks) : 4096)), dim3(256), 0, as_stream(stream),
-                       values, n, count);
-    return launch_status("count_nan_kernel");
-}
 #endif  // MNF_BF16

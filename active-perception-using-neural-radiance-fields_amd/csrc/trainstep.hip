@@ -40,9 +40,6 @@ struct mnf_presample_s {
 };
 
 namespace mnf {
-// train.hip: the next backward on this thread forms its per-sample output gradients from these factors (w[s] * g[ray[s]]) instead of reading them
-struct FactoredGrad { const float *w; const int64_t *ray; const float *g_rgb, *g_sem; };
-void set_factored_output_gradient(const FactoredGrad &fg);
 // composite_train.hip: the public entry points with the logits class-major, sems[class * sem_stride + sample] (0: [sample][C])
 int composite_train_forward_impl(const int64_t *chunk_starts, const int64_t *chunk_cnts, int32_t n_rays, const float *t_starts, const float *t_ends, const float *sigmas,
                                  const float *rgbs, const float *sems, int64_t sem_stride, int32_t n_classes, int64_t n_samples, const float *bkgd, float *out_rgb,
@@ -649,9 +646,12 @@ int step_backward(mnf_field_t f, const StepWs &w, int32_t n_rays, const mnf_trai
     int rc = composite_train_backward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.k_w, w.k_tr, w.o_acc,
                                            w.o_dep, w.g_rgb, g_acc, w.g_dep, w.g_sem, w.k_dsig, factored ? nullptr : w.k_drgb, factored ? nullptr : w.k_dsem, stream);
     if (rc) return rc;
-    if (factored) set_factored_output_gradient(FactoredGrad{w.k_w, w.k_ray, w.g_rgb, w.g_sem});
-    return backward(f, w.k_pos, max_kept, eff + 1, w.k_drgb, w.k_dsig, w.k_dsem, w.k_rgb, w.k_sigma, w.field_ws, w.field_ws_bytes, opts->loss_scale, g_base,
-                    g_head, g_sem, false, true, opts->deterministic != 0, as_stream(stream));
+    BackwardCall c = {};
+    c.positions = w.k_pos; c.n = max_kept; c.n_dev = eff + 1; c.d_rgb = w.k_drgb; c.d_density = w.k_dsig; c.d_sem = w.k_dsem; c.rgb = w.k_rgb; c.density = w.k_sigma;
+    c.workspace = w.field_ws; c.workspace_bytes = w.field_ws_bytes; c.loss_scale = opts->loss_scale; c.g_base = g_base; c.g_head = g_head; c.g_sem = g_sem;
+    c.positions_normalized = true; c.deterministic = opts->deterministic != 0; c.stream = as_stream(stream);
+    if (factored) c.factored = FactoredGrad{w.k_w, w.k_ray, w.g_rgb, w.g_sem};
+    return backward(f, c);
 }
 }  // namespace
 }  // namespace mnf

@@ -1,7 +1,7 @@
 """Optimizer for the field's three flat parameter vectors.
 
 `FusedAdam` is `torch.optim.Adam(params, lr, betas, eps)` as the reference constructs it (scripts/pipeline.py:173-178:
-weight_decay 0, amsgrad off) with the update of a parameter done by ONE HIP kernel (csrc/train.hip adam_guarded_kernel) instead
+weight_decay 0, amsgrad off) with the update of a parameter done by ONE HIP kernel (csrc/adam.hip adam_guarded_kernel) instead
 of the six foreach passes over the 25 M hash-table entries.  State keys (`step`, `exp_avg`, `exp_avg_sq`) and
 `state_dict()` layout are torch's, so checkpoints written through either optimizer load into the other
 (pipeline.py:630-635 saves `optimizer.state_dict()`).

@@ -417,7 +417,7 @@ def test_results_do_not_depend_on_stale_workspace_contents():
 
 
 def test_binned_scatter_equals_walk():
-    """The table gradient of the fine hashed levels goes through per-bin item lists and LDS sums (csrc/train.hip bin_items_kernel /
+    """The table gradient of the fine hashed levels goes through per-bin item lists and LDS sums (csrc/scatter.hip bin_items_kernel /
     bin_accumulate_kernel) instead of memory-side float atomics.  Same contributions, 21 significant bits per item, another summation order: the
     result equals the walk's to 2e-6 relative L2, also when the lists are made so short that nearly every item takes the full-list route.  The knobs
     that select the routes exist only in the diag build: child process (tests/diag_bins.py)."""

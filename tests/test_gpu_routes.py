@@ -18,7 +18,7 @@ def _cu(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
-# ------------------------------------------------------------------ field backward (csrc/train.hip dgrad_kernel<W,NH>, wgrad, scatter)
+# ------------------------------------------------------------------ field backward (csrc/train.hip dgrad_kernel<W,NH>, wgrad; csrc/scatter.hip)
 def _backward_vs_oracle(neurons, layers, C, lh, n, seed, field_kw=None, oracle_kw=None, rel=2e-2, cos=0.9995, fwd_atol=1e-3, flip_kw=None):
     """test_field_backward_matches_oracle's comparison at one shape: train forward == inference forward, every gradient group within 2e-2 relative L2
     and cosine > 0.9995, untouched table entries exactly zero.  Returns (hip, orc, n_mlp) for further checks.

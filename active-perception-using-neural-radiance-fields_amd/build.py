@@ -28,6 +28,7 @@ SOURCES = {
     "api.cpp": [],
     "march.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
+    "score.hip": ["-ffp-contract=off"],
     "field.hip": ["-fno-slp-vectorize"],   # packed-fp32 pairing of the compositing butterflies keeps their DPP operands from folding into the adds
     "train.hip": [],
     "scatter.hip": [],

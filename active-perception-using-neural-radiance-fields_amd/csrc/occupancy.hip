@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "field.h"
+#include "workspace.h"
 
 namespace mnf {
 namespace {
@@ -252,19 +253,18 @@ inline int64_t list_capacity(int64_t cells, int32_t step, int32_t warmup_steps) 
 
 OccWs carve_occ(char *base, int64_t cells, bool fused) {
     OccWs w;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += (b + 255) & ~(size_t)255; return p; };
-    w.owner = (int32_t *)take((size_t)cells * 4);
-    w.prefix = (int32_t *)take((size_t)((cells + 31) / 32) * 4);
-    w.part_sum = (double *)take(kReduceBlocks * 8);
-    w.part_cnt = (int64_t *)take(kReduceBlocks * 8);
+    Carver c(base);
+    w.owner = c.take<int32_t>((size_t)cells);
+    w.prefix = c.take<int32_t>((size_t)((cells + 31) / 32));
+    w.part_sum = c.take<double>(kReduceBlocks);
+    w.part_cnt = c.take<int64_t>(kReduceBlocks);
     w.idx = nullptr; w.pts = nullptr; w.vals = nullptr;
     if (fused) {
-        w.idx = (int64_t *)take((size_t)cells * 8);
-        w.pts = (float *)take((size_t)cells * 12);
-        w.vals = (float *)take((size_t)cells * 4);
+        w.idx = c.take<int64_t>((size_t)cells);
+        w.pts = c.take<float>((size_t)cells * 3);
+        w.vals = c.take<float>((size_t)cells);
     }
-    w.bytes = (int64_t)off;
+    w.bytes = c.bytes();
     return w;
 }
 

@@ -1,8 +1,7 @@
-// Fused test-mode renderers and the predictive-information scorer.
+// Fused test-mode renderers (the predictive-information scorer that reads their outputs: score.hip).
 //
 //   mnf_render_test  <- perception/models/utils.py:555-779 (render_image_with_occgrid_test) and
 //                       utils.py:782-1032 (render_probablistic_image_with_occgrid_test)
-//   mnf_score_views  <- scripts/pipeline.py:727-781
 //
 // The reference runs <=256 host-synchronised rounds per call (utils.py:666-757): count alive rays
 // (`.item()`), march <= n_samples new samples per alive ray, query the field, composite with the
@@ -17,6 +16,7 @@
 
 #include "field.h"
 #include "march_dev.h"
+#include "workspace.h"
 
 namespace mnf {
 
@@ -60,45 +60,40 @@ static hipEvent_t *log_events() {
 }
 static bool round_log() { static const bool on = diag_env("MNF_ROUND_LOG") != nullptr; return on; }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // A view's rays are marched by its own ceil(rays_per_view / kMarchThreads) workgroups (the last one partly idle when the
 // size is not a multiple): every marching ray of a workgroup then has the same per-ray budget n_samples[view], which is what
 // bounds the columns a round can allocate (below).
 static inline int64_t march_blocks_per_view(int32_t rays_per_view) { return (rays_per_view + kMarchThreads - 1) / kMarchThreads; }
 
-static int64_t carve(RenderWs *ws, char *base, int64_t n_rays, int32_t rays_per_view) {
+static int64_t carve(RenderWs &ws, char *base, int64_t n_rays, int32_t rays_per_view) {
     const int64_t n_views = n_rays / rays_per_view;
     // columns of one round: a tile of 64 holds floor(64/stride) rays of `stride` columns, so it is at least half
     // used; n_alive*stride <= max(R, 4*n_alive) <= 4R (utils.py:670) -> <= 8R, plus one partial tile per workgroup
     // (a march workgroup never mixes views: march_blocks_per_view() workgroups per view, so `stride` is the view's budget)
     int64_t col_cap = 8 * n_rays + 64 * (n_views * march_blocks_per_view(rays_per_view) + 2);
     if (const char *e = diag_env("MNF_MIN_SAMPLES")) col_cap = (int64_t)(2 * atoi(e) > 8 ? 2 * atoi(e) : 8) * n_rays + 64 * (n_views * march_blocks_per_view(rays_per_view) + 2);   // diagnostic schedule
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    char *p;
-    p = take(n_rays * 4); if (ws) ws->near_plane = (float *)p;
-    p = take(n_rays * 4); if (ws) ws->t_min = (float *)p;
-    p = take(n_rays * 4); if (ws) ws->t_max = (float *)p;
-    p = take(n_rays * 4); if (ws) ws->col0 = (int32_t *)p;
-    p = take(n_rays * 4); if (ws) ws->cnt = (int32_t *)p;
-    p = take(n_rays); if (ws) ws->alive = (uint8_t *)p;
-    p = take(n_rays); if (ws) ws->hit = (uint8_t *)p;
-    p = take(2 * n_views * 4); if (ws) ws->alive_count = (int32_t *)p;
-    p = take(n_views * 4); if (ws) ws->n_samples = (int32_t *)p;
-    p = take(2 * n_views * 4); if (ws) ws->iter_samples = (int32_t *)p;
-    p = take(n_views * 4); if (ws) ws->active = (int32_t *)p;
-    p = take(256); if (ws) { ws->n_cols = (int32_t *)p; ws->any_active = (int32_t *)p + 2; ws->overflow = (int32_t *)p + 4; }   // n_cols[2] | any_active[2] | overflow | ... | words 8..10: the round log's tile counters (FusedRender::diag_counts)
-    p = take(512); if (ws) ws->tickets = (uint32_t *)p;
-    p = take(kMaxGridWords * 4); if (ws) ws->bitgrid = (uint32_t *)p;
-    p = take(col_cap * 4); if (ws) ws->col_ray = (int32_t *)p;
-    p = take(col_cap * 4); if (ws) ws->col_ts = (float *)p;
-    p = take(col_cap * 4); if (ws) ws->col_te = (float *)p;
-    p = take(col_cap / 64 * 4); if (ws) ws->tile_hdr = (int32_t *)p;
-    if (split_field()) { p = take((col_cap / 64 + 1) * 8192); if (ws) ws->enc = p; }   // two-launch path: 128 B per column
-    else if (ws) ws->enc = nullptr;
-    if (ws) ws->col_cap = col_cap;
-    return (int64_t)off;
+    Carver c(base);
+    ws.near_plane = c.take<float>(n_rays);
+    ws.t_min = c.take<float>(n_rays);
+    ws.t_max = c.take<float>(n_rays);
+    ws.col0 = c.take<int32_t>(n_rays);
+    ws.cnt = c.take<int32_t>(n_rays);
+    ws.alive = c.take<uint8_t>(n_rays);
+    ws.hit = c.take<uint8_t>(n_rays);
+    ws.alive_count = c.take<int32_t>(2 * n_views);
+    ws.n_samples = c.take<int32_t>(n_views);
+    ws.iter_samples = c.take<int32_t>(2 * n_views);
+    ws.active = c.take<int32_t>(n_views);
+    ws.n_cols = c.take<int32_t>(64); ws.any_active = ws.n_cols + 2; ws.overflow = ws.n_cols + 4;   // n_cols[2] | any_active[2] | overflow | ... | words 8..10: the round log's tile counters (FusedRender::diag_counts)
+    ws.tickets = c.take<uint32_t>(128);
+    ws.bitgrid = c.take<uint32_t>(kMaxGridWords);
+    ws.col_ray = c.take<int32_t>(col_cap);
+    ws.col_ts = c.take<float>(col_cap);
+    ws.col_te = c.take<float>(col_cap);
+    ws.tile_hdr = c.take<int32_t>(col_cap / 64);
+    ws.enc = split_field() ? c.take((col_cap / 64 + 1) * 8192) : nullptr;   // two-launch path: 128 B per column
+    ws.col_cap = col_cap;
+    return c.bytes();
 }
 
 struct RenderOut {
@@ -332,129 +327,14 @@ __global__ void __launch_bounds__(kRayThreads) finalize_kernel(int64_t n_rays, f
     out.depth[r] = out.depth[r] / fmaxf(op, 1.1920928955078125e-07f);   // torch.finfo(float32).eps
 }
 
-// ------------------------------------------------------------------ scorer (pipeline.py:727-781), one block per view
-__device__ __forceinline__ double block_sum(double v, double *s_buf) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_buf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_buf[w];
-    return t;
-}
-
-constexpr int kScoreMaxM = 4;             // ensemble sizes the array-free form of the semantic term is unrolled for (the reference's ensemble has two members)
-constexpr int kScoreThreads = 1024;      // 16 waves per view: the 4096 pixels of a view are ~220 double-precision exp / log each; four waves per view left three of four issue slots to their latencies (1.07 ms per 256 views)
-template <bool SMALL_M>      // SMALL_M: M <= kScoreMaxM (checked by the host)
-__global__ void __launch_bounds__(kScoreThreads) score_kernel(const float *__restrict__ rgb_var, const float *__restrict__ depth_var,
-                                                    const float *__restrict__ acc, const float *__restrict__ sem,
-                                                    int M, int V, int P, int C, double *__restrict__ terms) {
-    __shared__ double s_buf[kScoreThreads / 64];
-    const int v = blockIdx.x;
-    const double k2pie = 2.0 * 3.14159265358979323846 * 2.71828182845904523536;
-    double s_rgb = 0.0, s_dep = 0.0, s_sem = 0.0, s_occ = 0.0;
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        // rgb / depth: entropy of the summed variance minus mean member entropy (pipeline.py:727-746)
-        for (int ch = 0; ch < 3; ++ch) {
-            double sum_var = 0.0, mean_ce = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const double x = rgb_var[(((int64_t)m * V + v) * P + p) * 3 + ch];
-                sum_var += x;
-                mean_ce += log(k2pie * x + 1e-4) / 2.0;
-            }
-            s_rgb += log(k2pie * (sum_var / 2.0) + 1e-4) / 2.0 - mean_ce / M;
-        }
-        {
-            double sum_var = 0.0, mean_ce = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const double x = depth_var[((int64_t)m * V + v) * P + p];
-                sum_var += x;
-                mean_ce += log(k2pie * x + 1e-4) / 2.0;
-            }
-            s_dep += log(k2pie * (sum_var / 2.0) + 1e-4) / 2.0 - mean_ce / M;
-        }
-        // semantics (pipeline.py:748-760)
-        if constexpr (SMALL_M) {
-            // class by class with the members' max / denominator worked out first: the same sums in the same order as the general form below, without its
-            // per-class array (dynamically indexed -> 272 bytes of scratch per lane, which was most of this kernel's time)
-            double mx[kScoreMaxM], den[kScoreMaxM], ce[kScoreMaxM];
-#pragma unroll
-            for (int m = 0; m < kScoreMaxM; ++m) {
-                mx[m] = -1e300; den[m] = 0.0; ce[m] = 0.0;
-                if (m < M) {
-                    const float *lg = sem + (((int64_t)m * V + v) * P + p) * C;
-                    for (int k = 0; k < C; ++k) mx[m] = fmax(mx[m], (double)lg[k]);
-                    for (int k = 0; k < C; ++k) den[m] += exp((double)lg[k] - mx[m]);
-                }
-            }
-            double ent = 0.0;
-            for (int k = 0; k < C; ++k) {
-                double pe = 0.0;
-#pragma unroll
-                for (int m = 0; m < kScoreMaxM; ++m)
-                    if (m < M) {
-                        const double pk = exp((double)sem[(((int64_t)m * V + v) * P + p) * C + k] - mx[m]) / den[m];
-                        pe += pk;
-                        ce[m] -= (pk + 1e-4) * log(pk + 1e-4);
-                    }
-                pe /= M;
-                ent -= (pe + 1e-4) * log(pe + 1e-4);
-            }
-            double mean_ce = 0.0;
-#pragma unroll
-            for (int m = 0; m < kScoreMaxM; ++m) if (m < M) mean_ce += ce[m];
-            s_sem += ent - mean_ce / M;
-        } else {
-            double p_ens[32];
-            for (int k = 0; k < C; ++k) p_ens[k] = 0.0;
-            double mean_ce = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const float *lg = sem + (((int64_t)m * V + v) * P + p) * C;
-                double mx = -1e300;
-                for (int k = 0; k < C; ++k) mx = fmax(mx, (double)lg[k]);
-                double den = 0.0;
-                for (int k = 0; k < C; ++k) den += exp((double)lg[k] - mx);
-                double ce = 0.0;
-                for (int k = 0; k < C; ++k) {
-                    const double pk = exp((double)lg[k] - mx) / den;
-                    p_ens[k] += pk;
-                    ce -= (pk + 1e-4) * log(pk + 1e-4);
-                }
-                mean_ce += ce;
-            }
-            double ent = 0.0;
-            for (int k = 0; k < C; ++k) { const double pk = p_ens[k] / M; ent -= (pk + 1e-4) * log(pk + 1e-4); }
-            s_sem += ent - mean_ce / M;
-        }
-        // occupancy (pipeline.py:762-773)
-        {
-            double a_ens = 0.0, mean_ce = 0.0;
-            for (int m = 0; m < M; ++m) {
-                const double a = acc[((int64_t)m * V + v) * P + p];
-                a_ens += a;
-                mean_ce += -(a + 1e-4) * log(a + 1e-4) - (1.0 - a + 1e-4) * log(1.0 - a + 1e-4);
-            }
-            a_ens /= M;
-            s_occ += -(a_ens + 1e-4) * log(a_ens + 1e-4) - (1.0 - a_ens + 1e-4) * log(1.0 - a_ens + 1e-4) - mean_ce / M;
-        }
-    }
-    const double t0 = block_sum(s_rgb, s_buf), t1 = block_sum(s_dep, s_buf), t2 = block_sum(s_sem, s_buf), t3 = block_sum(s_occ, s_buf);
-    if (threadIdx.x == 0) {
-        terms[4 * v + 0] = t0 / (3.0 * P);
-        terms[4 * v + 1] = t1 / P;
-        terms[4 * v + 2] = t2 / P;
-        terms[4 * v + 3] = t3 / P;
-    }
-}
-
 }  // namespace mnf
 
 using namespace mnf;
 
 extern "C" int64_t mnf_render_workspace_bytes(int64_t n_rays, int32_t rays_per_view) {
     if (n_rays <= 0 || rays_per_view <= 0 || n_rays % rays_per_view) return -1;
-    return carve(nullptr, nullptr, n_rays, rays_per_view);
+    RenderWs size_only;
+    return carve(size_only, nullptr, n_rays, rays_per_view);
 }
 
 // ------------------------------------------------------------------ render jobs
@@ -535,13 +415,8 @@ int job_begin(RenderJob &j, mnf_field_t f, const uint8_t *binaries, int32_t res_
     MNF_REQUIRE(binaries && rays_o && rays_d && rgb && acc && depth && sem && total_samples, "render_test: null buffer");
     MNF_REQUIRE(!opts->probabilistic || (rgb_var && depth_var), "render_test: probabilistic needs rgb_var and depth_var");
     MNF_REQUIRE(opts->max_samples > 0 && opts->render_step_size > 0.f, "render_test: max_samples and render_step_size must be > 0");
-    const int64_t need = carve(nullptr, nullptr, n_rays, opts->rays_per_view);
-    if (!workspace || workspace_bytes < need) {
-        set_error("render_test: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
-        return MNF_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("render_test", workspace, workspace_bytes, carve(j.ws, (char *)workspace, n_rays, opts->rays_per_view))) return rc;
     j.f = f; j.binaries = binaries; j.rays_o = rays_o; j.rays_d = rays_d; j.n_rays = n_rays; j.opts = *opts; j.s = s; j.res = res;
-    carve(&j.ws, (char *)workspace, n_rays, opts->rays_per_view);
     j.out = {rgb, acc, depth, sem, opts->probabilistic ? rgb_var : nullptr, opts->probabilistic ? depth_var : nullptr, total_samples};
     j.n_views = (int32_t)(n_rays / opts->rays_per_view);
     j.C = f->cfg.num_semantic_classes;
@@ -784,18 +659,4 @@ extern "C" int mnf_render_jobs(const mnf_render_job *jobs_host, int32_t n_jobs, 
     for (auto &j : jobs)
         if (j.s != s0) { (void)hipEventRecord(j.res->ev_join, j.s); (void)hipStreamWaitEvent(s0, j.res->ev_join, 0); }
     return rc;
-}
-
-extern "C" int mnf_score_views(const float *rgb_var, const float *depth_var, const float *acc, const float *sem,
-                               int32_t n_members, int32_t n_views, int32_t n_pix, int32_t n_classes, double *terms, mnf_stream_t stream) {
-    MNF_REQUIRE(n_members >= 1 && n_views >= 0 && n_pix > 0 && n_classes >= 1 && n_classes <= 32, "score_views: bad sizes");
-    if (n_views == 0) return MNF_OK;
-    MNF_REQUIRE(rgb_var && depth_var && acc && sem && terms, "score_views: null pointer");
-    if (n_members <= kScoreMaxM)
-        hipLaunchKernelGGL(score_kernel<true>, dim3(n_views), dim3(kScoreThreads), 0, as_stream(stream), rgb_var, depth_var, acc, sem, n_members, n_views,
-                           n_pix, n_classes, terms);
-    else
-        hipLaunchKernelGGL(score_kernel<false>, dim3(n_views), dim3(kScoreThreads), 0, as_stream(stream), rgb_var, depth_var, acc, sem, n_members, n_views,
-                           n_pix, n_classes, terms);
-    return launch_status("score_kernel");
 }

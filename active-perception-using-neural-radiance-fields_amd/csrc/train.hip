@@ -20,6 +20,7 @@
 
 #include "field_dev.h"
 #include "scatter.h"
+#include "workspace.h"
 
 MNF_DT_BEGIN
 
@@ -595,17 +596,16 @@ struct WsView {
 static WsView carve_train(const TrainTables &tt, const mnf_field_s *f, void *base, int64_t n) {
     WsView v;
     v.Np = ceil_div(n, 64) * 64;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? (char *)base + off : nullptr; off += (b + 255) & ~(size_t)255; return p; };
-    v.act = (half_t *)take((size_t)tt.rows * v.Np * 2);
-    v.masks = (uint8_t *)take((size_t)v.Np * tt.mask_bytes);      // [tile][lane] records
-    v.dX = (float *)take((size_t)v.Np * 64 * 4);
-    v.xn = (float *)take((size_t)v.Np * 3 * 4);
+    Carver c(base);
+    v.act = c.take<half_t>((size_t)tt.rows * v.Np);
+    v.masks = c.take<uint8_t>((size_t)v.Np * tt.mask_bytes);      // [tile][lane] records
+    v.dX = c.take<float>((size_t)v.Np * 64);
+    v.xn = c.take<float>((size_t)v.Np * 3);
     const ScatterWorkspace sw = scatter_workspace(f, n);
-    v.repl = (float *)take(sw.repl_bytes);
+    v.repl = (float *)c.take(sw.repl_bytes);
     v.bin_items_n = sw.bin_items;
-    v.bin_items = (float4 *)take(v.bin_items_n * sizeof(float4));
-    v.bytes = (int64_t)off;
+    v.bin_items = c.take<float4>(v.bin_items_n);
+    v.bytes = c.bytes();
     return v;
 }
 
@@ -631,11 +631,7 @@ static int open_train(mnf_field_t f, const char *who, void *workspace, int64_t w
     if (const int rc = ensure_train_state(f)) return rc;
     ts = reinterpret_cast<TrainState *>(f->train_state);
     v = carve_train(ts->tt, f, workspace, n);
-    if (!workspace || workspace_bytes < v.bytes) {
-        set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)workspace_bytes, (long long)v.bytes);
-        return MNF_ERR_WORKSPACE;
-    }
-    return MNF_OK;
+    return check_workspace(who, workspace, workspace_bytes, v.bytes);
 }
 
 int forward_train_impl(mnf_field_t f, const FieldIO &io, void *workspace, int64_t workspace_bytes, hipStream_t stream, bool deterministic) {

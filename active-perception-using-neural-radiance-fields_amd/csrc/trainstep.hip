@@ -1,4 +1,4 @@
-// One training iteration's forward + loss + backward as ONE C call, and candidate-view scoring from poses as one C call.
+// One training iteration's forward + loss + backward as ONE C call.
 //
 //   mnf_train_step    scripts/pipeline.py:472-518 for one model: `render_image_with_occgrid_with_depth_guide`
 //                     (perception/models/utils.py:63-219: occupancy sampling with the density pre-pass and the visibility
@@ -9,10 +9,8 @@
 //   mnf_train_render_forward / mnf_train_render_backward
 //                     the same step cut at its loss: pipeline.py:472-489 now, `loss.backward()` (pipeline.py:518) later with whatever gradients the caller's own
 //                     loss produced for the four rendered planes.  Same kernels in the same order on either side of the cut (step_forward / step_backward).
-//   mnf_score_poses   pipeline.py:674-781 for one trajectory: poses -> sub-sampled rays -> probabilistic renders of every
-//                     ensemble member -> per-view predictive-information terms.
 //
-// Both are compositions of the library's own entry points plus the small kernels below (stratified near planes, visibility
+// All of them are compositions of the library's own entry points plus the small kernels below (stratified near planes, visibility
 // filter with compaction, loss + its gradient).  mnf_train_step never synchronises with the host: the marched and the
 // surviving sample counts stay on the device (every launch is sized for the caller's upper bounds and reads the actual
 // count from device memory), overflow of a bound is detected on the device (the step then yields zero gradients and a
@@ -21,10 +19,10 @@
 //
 // Build with -ffp-contract=off (the marcher's near planes feed bit-exact t values).
 #include <cmath>
-#include <cstring>
-#include <vector>
+#include <cstddef>
 
 #include "field.h"
+#include "workspace.h"
 
 // mnf_train_presample's handle: what was marched, for which rays / options, and the two events that order it
 struct mnf_presample_s {
@@ -49,8 +47,6 @@ int composite_train_backward_impl(const int64_t *chunk_starts, const int64_t *ch
                                   const float *trans, const float *out_acc, const float *out_depth, const float *g_rgb, const float *g_acc, const float *g_depth,
                                   const float *g_sem, float *d_sigmas, float *d_rgbs, float *d_sems, mnf_stream_t stream);
 namespace {
-
-constexpr float kEps = 1.1920928955078125e-07f;
 
 struct U4 { uint32_t x, y, z, w; };
 __device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
@@ -348,46 +344,82 @@ __global__ void __launch_bounds__(256) gradients_in_kernel(int32_t n_rays, int32
     }
 }
 
-struct StepWs {
-    float *nearp, *farp, *scratch_ts, *scratch_te, *alpha_thre;
-    int64_t *counts, *starts, *kept_cnts, *kept_starts, *totals, *scan;
-    float *ts, *te, *sigma;          // marched
-    int64_t *ray;
+// The two small blocks of a workspace, word by word.  The asserts pin every position: an adopting step reads a presample's blocks, a render backward the forward's.
+struct StepWords {                        // `totals`: 256 int64 words
+    int64_t marched, kept, longest, spare3;      // [0..2] the totals of the two scans, and the longest ray (max_kernel)
+    int64_t eff[2], spare6;                      // [4..5] marched, kept: the counts the kernels behind the guards work on
+    int32_t ray_counter, spare7;          // [7] the pre-pass's work counter
+    double mean_part[128], spare136[24];         // [8..135] the occupancy mean's partial sums
+    int64_t pre_report[4], spare164[36];         // [160..163] a presample's report: its guard's four counters, which the adopting step's planes_kernel copies
+    uint32_t ticket, verdict;             // [200] mnf_train_render_*'s block ticket and, in the 32 bits behind it, the forward's verdict
+    int64_t spare201[55];
+};
+struct StepScalars {                      // `alpha_thre`: 64 floats
+    float alpha_thre, spare1[7];          // [0] the visibility filter's threshold (mean_final_kernel)
+    float bkgd[3], spare11[5];            // [8..10] a by-value background colour (set3_kernel)
+    float render_losses[4], spare20[44];  // [16..19] the loss terms planes_kernel zeroes for a mnf_train_render_forward (nobody reads them)
+};
+static_assert(sizeof(StepWords) == 2048 && offsetof(StepWords, marched) == 0 && offsetof(StepWords, kept) == 8 && offsetof(StepWords, longest) == 16 &&
+              offsetof(StepWords, eff) == 32 && offsetof(StepWords, ray_counter) == 56 && offsetof(StepWords, mean_part) == 64 &&
+              offsetof(StepWords, pre_report) == 1280 && offsetof(StepWords, ticket) == 1600 && offsetof(StepWords, verdict) == 1604, "StepWords: a word has moved");
+static_assert(sizeof(StepScalars) == 256 && offsetof(StepScalars, alpha_thre) == 0 && offsetof(StepScalars, bkgd) == 32 &&
+              offsetof(StepScalars, render_losses) == 64, "StepScalars: a word has moved");
+
+// What the parameter-independent head of a step leaves behind (mnf_train_presample), and the same part of a step's own workspace: the part the march fills.
+struct SampleWs {
+    float *nearp, *farp, *scratch_ts, *scratch_te;
+    StepScalars *scalars; StepWords *words;      // the two small blocks
+    int64_t *counts, *starts, *scan;
+    float *ts, *te; int64_t *ray;      // the packed samples
+    int64_t bytes;                     // of the workspace it was carved from, whole
+};
+
+struct StepWs : SampleWs {
+    int64_t *kept_cnts, *kept_starts;
+    int64_t *kept_scan;                // the step's own scan buffer.  After an adoption `scan` is the presample's; the kept-sample scan never writes there
+    float *sigma;                      // marched
     float *k_ts, *k_te, *k_rgb, *k_sigma, *k_sem, *k_pos, *k_w, *k_tr, *k_dsig, *k_drgb, *k_dsem;   // kept
     int64_t *k_ray;
     void *rows; int64_t *k_src;        // the pre-pass's feature rows [max_marched][64] x 16 bit and every surviving sample's row (field_rows_supported)
     float *o_rgb, *o_acc, *o_dep, *o_sem, *g_rgb, *g_dep, *g_sem;   // per ray
     float *g_acc;                      // per ray: the caller's opacity gradient (mnf_train_render_backward; the step's own loss has none)
     void *field_ws;
-    int64_t field_ws_bytes, bytes;
+    int64_t field_ws_bytes;
 };
 
-// The two small blocks' words.  `alpha_thre` (64 floats): [0] the threshold, [8..10] a by-value background colour (set3_kernel), [16..19] the loss terms of a
-// mnf_train_render_forward (render_losses).  `totals` (256 int64): [0..2] marched, kept, longest ray, [4..5] `eff`, the counts the kernels behind the guards work
-// on, [7] the pre-pass's work counter, [8..135] the occupancy mean's partial sums, [160..163] a presample's report (kPreReport), [200] mnf_train_render_*'s
-// block ticket (low half) and forward verdict (high half) (render_ticket).  A new user takes words not listed here, and lists them.
-StepWs carve_step(char *base, mnf_field_t f, int64_t R, int32_t cap, int64_t max_marched, int64_t max_kept) {
+SampleWs carve_sample(void *base, int64_t R, int32_t cap, int64_t max_marched) {
+    SampleWs w;
+    Carver c(base);
+    w.nearp = c.take<float>(R); w.farp = c.take<float>(R); w.scalars = c.take<StepScalars>(1);
+    w.counts = c.take<int64_t>(R); w.starts = c.take<int64_t>(R);
+    w.words = c.take<StepWords>(1); w.scan = (int64_t *)c.take((size_t)mnf_scan_workspace_bytes(R));
+    w.scratch_ts = c.take<float>((size_t)R * cap); w.scratch_te = c.take<float>((size_t)R * cap);
+    w.ts = c.take<float>(max_marched); w.te = c.take<float>(max_marched); w.ray = c.take<int64_t>(max_marched);
+    w.bytes = c.bytes();
+    return w;
+}
+
+StepWs carve_step(void *base, mnf_field_t f, int64_t R, int32_t cap, int64_t max_marched, int64_t max_kept) {
     StepWs w;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += (b + 255) & ~(size_t)255; return p; };
-    const int C = f->cfg.num_semantic_classes;
-    w.nearp = (float *)take(R * 4); w.farp = (float *)take(R * 4); w.alpha_thre = (float *)take(256);
-    w.counts = (int64_t *)take(R * 8); w.starts = (int64_t *)take(R * 8); w.kept_cnts = (int64_t *)take(R * 8); w.kept_starts = (int64_t *)take(R * 8);
-    w.totals = (int64_t *)take(2048); w.scan = (int64_t *)take((size_t)mnf_scan_workspace_bytes(R));
-    w.scratch_ts = (float *)take((size_t)R * cap * 4); w.scratch_te = (float *)take((size_t)R * cap * 4);
-    w.ts = (float *)take(max_marched * 4); w.te = (float *)take(max_marched * 4); w.sigma = (float *)take(max_marched * 4); w.ray = (int64_t *)take(max_marched * 8);
-    w.k_ts = (float *)take(max_kept * 4); w.k_te = (float *)take(max_kept * 4); w.k_ray = (int64_t *)take(max_kept * 8);
-    w.k_rgb = (float *)take(max_kept * 12); w.k_sigma = (float *)take(max_kept * 4); w.k_sem = (float *)take((size_t)max_kept * C * 4);
-    w.k_pos = (float *)take(max_kept * 12); w.k_w = (float *)take(max_kept * 4); w.k_tr = (float *)take(max_kept * 4);
-    w.k_dsig = (float *)take(max_kept * 4); w.k_drgb = (float *)take(max_kept * 12); w.k_dsem = (float *)take((size_t)max_kept * C * 4);
-    w.o_rgb = (float *)take(R * 12); w.o_acc = (float *)take(R * 4); w.o_dep = (float *)take(R * 4); w.o_sem = (float *)take((size_t)R * C * 4);
-    w.g_rgb = (float *)take(R * 12); w.g_dep = (float *)take(R * 4); w.g_sem = (float *)take((size_t)R * C * 4);
+    Carver c(base);
+    const size_t C = f->cfg.num_semantic_classes;
+    w.nearp = c.take<float>(R); w.farp = c.take<float>(R); w.scalars = c.take<StepScalars>(1);
+    w.counts = c.take<int64_t>(R); w.starts = c.take<int64_t>(R); w.kept_cnts = c.take<int64_t>(R); w.kept_starts = c.take<int64_t>(R);
+    w.words = c.take<StepWords>(1); w.kept_scan = w.scan = (int64_t *)c.take((size_t)mnf_scan_workspace_bytes(R));
+    w.scratch_ts = c.take<float>((size_t)R * cap); w.scratch_te = c.take<float>((size_t)R * cap);
+    w.ts = c.take<float>(max_marched); w.te = c.take<float>(max_marched); w.sigma = c.take<float>(max_marched); w.ray = c.take<int64_t>(max_marched);
+    w.k_ts = c.take<float>(max_kept); w.k_te = c.take<float>(max_kept); w.k_ray = c.take<int64_t>(max_kept);
+    w.k_rgb = c.take<float>(max_kept * 3); w.k_sigma = c.take<float>(max_kept); w.k_sem = c.take<float>(max_kept * C);
+    w.k_pos = c.take<float>(max_kept * 3); w.k_w = c.take<float>(max_kept); w.k_tr = c.take<float>(max_kept);
+    w.k_dsig = c.take<float>(max_kept); w.k_drgb = c.take<float>(max_kept * 3); w.k_dsem = c.take<float>(max_kept * C);
+    w.o_rgb = c.take<float>(R * 3); w.o_acc = c.take<float>(R); w.o_dep = c.take<float>(R); w.o_sem = c.take<float>(R * C);
+    w.g_rgb = c.take<float>(R * 3); w.g_dep = c.take<float>(R); w.g_sem = c.take<float>(R * C);
     w.rows = nullptr; w.k_src = nullptr;
-    if (field_rows_supported(f)) { w.rows = take((size_t)max_marched * 128); w.k_src = (int64_t *)take(max_kept * 8); }
+    if (field_rows_supported(f)) { w.rows = c.take((size_t)max_marched * 128); w.k_src = c.take<int64_t>(max_kept); }
     w.field_ws_bytes = mnf_field_train_workspace_bytes(f, max_kept);
-    w.field_ws = take((size_t)w.field_ws_bytes);
-    w.g_acc = (float *)take(R * 4);      // (behind everything else: every other offset is what it was)
-    w.bytes = (int64_t)off;
+    w.field_ws = c.take((size_t)w.field_ws_bytes);
+    w.g_acc = c.take<float>(R);      // (behind everything else: every other offset is what it was)
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -396,52 +428,62 @@ inline int32_t scratch_cap(int32_t n_rays) {
     return (int32_t)(c < 64 ? 64 : (c > 2048 ? 2048 : c));
 }
 
-// What the parameter-independent head of a step leaves behind (mnf_train_presample): the part of StepWs the march fills.
-struct SampleWs {
-    float *nearp, *farp, *alpha_thre, *scratch_ts, *scratch_te;
-    int64_t *counts, *starts, *totals, *scan;
-    int64_t bytes;
-    float *ts, *te; int64_t *ray;      // a presample's packed samples (max_marched > 0)
-};
+inline int64_t *eff_counts(const SampleWs &w) { return w.words->eff; }      // [0] marched, [1] kept samples the kernels behind the guards work on
 
-SampleWs carve_sample(char *base, int64_t R, int32_t cap, int64_t max_marched = 0) {
-    SampleWs w;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += (b + 255) & ~(size_t)255; return p; };
-    w.nearp = (float *)take(R * 4); w.farp = (float *)take(R * 4); w.alpha_thre = (float *)take(256);
-    w.counts = (int64_t *)take(R * 8); w.starts = (int64_t *)take(R * 8);
-    w.totals = (int64_t *)take(2048); w.scan = (int64_t *)take((size_t)mnf_scan_workspace_bytes(R));
-    w.scratch_ts = (float *)take((size_t)R * cap * 4); w.scratch_te = (float *)take((size_t)R * cap * 4);
-    w.ts = w.te = nullptr; w.ray = nullptr;
-    if (max_marched > 0) { w.ts = (float *)take(max_marched * 4); w.te = (float *)take(max_marched * 4); w.ray = (int64_t *)take(max_marched * 8); }
-    w.bytes = (int64_t)off;
-    return w;
+// The background both sides of the loss composite over: the caller's device colour, else the by-value one where not black (step_forward leaves it in `w`), else none
+inline const float *background(const SampleWs &w, const mnf_train_opts *opts) {
+    if (opts->render_bkgd_dev) return opts->render_bkgd_dev;
+    return opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f ? w.scalars->bkgd : nullptr;
 }
-
-constexpr int kPreReport = 160;      // int64 words into a presample's `totals` block (2048 bytes: counters 0-7, 128 doubles of the mean from word 8): its guard's four counters
 
 inline int fill_blocks(int rblocks) { return rblocks > 2048 ? rblocks : 2048; }      // enough threads for the 50 MB gradient fill (16 bytes per thread and pass)
 
-// near planes, alpha threshold, march, per-ray offsets, longest ray: everything of a step that reads the rays and the occupancy grid but not the parameters
-int sample_stage(const SampleWs &w, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y, int32_t res_z,
-                 const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays, const mnf_train_opts *opts, float *losses,
-                 int64_t *counts_dev, int32_t *skip_dev, const StepFills &fills, hipStream_t s) {
-    const int64_t cells = (int64_t)res_x * res_y * res_z;
-    const int rblocks = (n_rays + 255) / 256;
-    const int32_t cap = scratch_cap(n_rays);
-    hipLaunchKernelGGL(planes_kernel, dim3(losses ? fill_blocks(rblocks) : rblocks), dim3(256), 0, s, n_rays, opts->near_plane, opts->far_plane, opts->render_step_size,
-                       opts->stratified, (uint32_t)opts->seed, (uint32_t)(opts->seed >> 32), w.nearp, w.farp, losses, counts_dev, skip_dev, fills);
-    double *mean_part = reinterpret_cast<double *>(w.totals + 8);          // 128 doubles behind the counters
-    const int n_levels = opts->n_levels > 1 ? opts->n_levels : 1;
-    hipLaunchKernelGGL(mean_partial_kernel, dim3(128), dim3(256), 0, s, occs, cells * n_levels, mean_part);          // occ_grid.py:192: the mean over every level
-    hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(64), 0, s, (const double *)mean_part, 128, cells * n_levels, opts->alpha_thre, w.alpha_thre);
-    int rc = mnf_sample_rays_levels(rays_o, rays_d, n_rays, binaries, n_levels, res_x, res_y, res_z, aabb_host, w.nearp, w.farp, opts->render_step_size,
-                                    opts->cone_angle, cap, w.scratch_ts, w.scratch_te, w.counts, bitgrid, (mnf_stream_t)s);
-    if (rc) return rc;
-    rc = mnf_exclusive_scan_i64(w.counts, n_rays, w.starts, w.totals, w.scan, mnf_scan_workspace_bytes(n_rays), (mnf_stream_t)s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(max_kernel, dim3(1), dim3(1024), 0, s, w.counts, (int64_t)n_rays, w.totals + 2);
-    return launch_status("sample_stage");
+// What an entry point hands down unchanged, in BackwardCall's manner (the backward entry points have no grid and no rays, a presample no max_kept and no report words)
+struct StepCall {
+    const uint8_t *binaries; const uint32_t *bitgrid; const float *occs; int32_t res_x, res_y, res_z;
+    const float *aabb_host, *rays_o, *rays_d; int32_t n_rays;
+    const mnf_train_opts *opts;
+    int64_t max_marched, max_kept;
+    int64_t *counts_dev; int32_t *skip_dev;
+    hipStream_t stream;
+};
+
+// The argument checks the entry points share, under the entry point's name: handle and options and the options' size, in front of an entry point's own checks ...
+int check_args(const char *who, bool handles, const mnf_train_opts *opts) {
+    MNF_REQUIRE(handles && opts, "%s: bad handle or options", who);
+    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "%s: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)", who,
+                opts->struct_size, sizeof(mnf_train_opts));
+    return MNF_OK;
+}
+// ... and behind them: positive sizes (`option`: the option that has to be positive too), the carve, the workspace's size (check_workspace)
+int open_step(const char *who, mnf_field_t f, const StepCall &c, float option, void *workspace, int64_t workspace_bytes, StepWs &w) {
+    MNF_REQUIRE(c.n_rays > 0 && c.max_marched > 0 && c.max_kept > 0 && option > 0.f, "%s: bad sizes", who);
+    w = carve_step(workspace, f, c.n_rays, scratch_cap(c.n_rays), c.max_marched, c.max_kept);
+    return check_workspace(who, workspace, workspace_bytes, w.bytes);
+}
+
+// near planes, alpha threshold, march, offsets, longest ray, bound check (its counters and flag: `report`, `skip`), packing: what reads rays and grid but no parameter
+int sample_stage(const StepCall &c, const SampleWs &w, float *losses, const StepFills &fills, int64_t *report, int32_t *skip) {
+    const int64_t cells = (int64_t)c.res_x * c.res_y * c.res_z;
+    const int rblocks = (c.n_rays + 255) / 256;
+    const int32_t cap = scratch_cap(c.n_rays);
+    hipLaunchKernelGGL(planes_kernel, dim3(losses ? fill_blocks(rblocks) : rblocks), dim3(256), 0, c.stream, c.n_rays, c.opts->near_plane, c.opts->far_plane,
+                       c.opts->render_step_size, c.opts->stratified, (uint32_t)c.opts->seed, (uint32_t)(c.opts->seed >> 32), w.nearp, w.farp, losses, c.counts_dev, c.skip_dev, fills);
+    const int n_levels = c.opts->n_levels > 1 ? c.opts->n_levels : 1;
+    hipLaunchKernelGGL(mean_partial_kernel, dim3(128), dim3(256), 0, c.stream, c.occs, cells * n_levels, w.words->mean_part);          // occ_grid.py:192: the mean over every level
+    hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(64), 0, c.stream, (const double *)w.words->mean_part, 128, cells * n_levels, c.opts->alpha_thre,
+                       &w.scalars->alpha_thre);
+    if (const int rc = mnf_sample_rays_levels(c.rays_o, c.rays_d, c.n_rays, c.binaries, n_levels, c.res_x, c.res_y, c.res_z, c.aabb_host, w.nearp, w.farp, c.opts->render_step_size,
+                                    c.opts->cone_angle, cap, w.scratch_ts, w.scratch_te, w.counts, c.bitgrid, (mnf_stream_t)c.stream))
+        return rc;
+    if (const int rc = mnf_exclusive_scan_i64(w.counts, c.n_rays, w.starts, &w.words->marched, w.scan, mnf_scan_workspace_bytes(c.n_rays), (mnf_stream_t)c.stream)) return rc;
+    hipLaunchKernelGGL(max_kernel, dim3(1), dim3(1024), 0, c.stream, w.counts, (int64_t)c.n_rays, &w.words->longest);
+    // a ray longer than its scratch row would have been truncated (the rows hold `cap` samples; the reference configurations stay far
+    // below) and more marched samples than `max_marched` would not fit the packed arrays: both end the step here, on the device
+    hipLaunchKernelGGL(guard_marched_kernel, dim3(rblocks), dim3(256), 0, c.stream, c.n_rays, w.counts, w.starts, (const int64_t *)&w.words->marched, c.max_marched,
+                       (int64_t)cap, eff_counts(w), report, skip);
+    if (const int rc = launch_status("sample_stage")) return rc;
+    return mnf_compact_samples(w.scratch_ts, w.scratch_te, cap, w.starts, w.counts, c.n_rays, w.ts, w.te, w.ray, (mnf_stream_t)c.stream);
 }
 
 }  // namespace
@@ -507,26 +549,22 @@ extern "C" int mnf_train_presample(mnf_presample_t p, const uint8_t *binaries, c
                                    int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
                                    const mnf_train_opts *opts, int64_t max_marched, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
     MNF_REQUIRE(p && binaries && occs && aabb_host && rays_o && rays_d && opts && workspace, "train_presample: null pointer");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_presample: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && opts->render_step_size > 0.f, "train_presample: bad sizes");
+    if (const int rc = check_args("train_presample", true, opts)) return rc;
+    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && opts->render_step_size > 0.f, "train_presample: bad sizes");      // (a presample filters nothing: no max_kept)
     const int n_levels = opts->n_levels > 1 ? opts->n_levels : 1;
     MNF_REQUIRE(n_levels <= 4, "train_presample: at most 4 occupancy levels");
-    const int32_t cap = scratch_cap(n_rays);
-    const SampleWs w = carve_sample((char *)workspace, n_rays, cap, max_marched);
-    if (workspace_bytes < w.bytes) { set_error("train_presample: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    const SampleWs w = carve_sample(workspace, n_rays, scratch_cap(n_rays), max_marched);
+    if (const int rc = check_workspace("train_presample", workspace, workspace_bytes, w.bytes)) return rc;
     hipStream_t s = as_stream(stream), ss = shared_side_stream(2);
     if (!ss) return MNF_ERR_HIP;
+    StepCall c = {};      // (its stream: the side stream the march runs on)
+    c.binaries = binaries; c.bitgrid = bitgrid; c.occs = occs; c.res_x = res_x; c.res_y = res_y; c.res_z = res_z; c.aabb_host = aabb_host;
+    c.rays_o = rays_o; c.rays_d = rays_d; c.n_rays = n_rays; c.opts = opts; c.max_marched = max_marched; c.stream = ss;
     p->valid = 0;
     // fork: the side stream continues from the caller's stream as it is NOW — in front of whatever the caller enqueues next (the step this march is to hide behind)
     MNF_HIP(hipEventRecord(p->ev_ready, s));
     MNF_HIP(hipStreamWaitEvent(ss, p->ev_ready, 0));
-    int rc = sample_stage(w, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, nullptr, nullptr, nullptr, StepFills{}, ss);
-    if (!rc) {      // the bound check of the step (its four counters go to the handle's own words: the adopting step copies them) and the packing of the scratch rows
-        hipLaunchKernelGGL(guard_marched_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, ss, n_rays, w.counts, w.starts, (const int64_t *)w.totals, max_marched,
-                           (int64_t)cap, w.totals + 4, w.totals + kPreReport, (int32_t *)nullptr);
-        rc = mnf_compact_samples(w.scratch_ts, w.scratch_te, cap, w.starts, w.counts, n_rays, w.ts, w.te, w.ray, (mnf_stream_t)ss);
-    }
+    const int rc = sample_stage(c, w, nullptr, StepFills{}, w.words->pre_report, nullptr);      // (the bound check's counters go to the handle's own words: the adopting step copies them)
     MNF_HIP(hipEventRecord(p->ev_done, ss));
     p->launched = 1;
     if (rc) return rc;
@@ -541,117 +579,99 @@ namespace mnf {
 namespace {
 // A step in front of its loss — planes and fills, alpha threshold, march, guards, compaction, ray-major density pre-pass leaving its feature rows, visibility filter,
 // forward_train reading the rows, compositing forward — and behind it.  mnf_train_step is the two with loss_kernel in between; mnf_train_render_forward /
-// _backward are the same two with the caller's own loss in between.  Whatever the second half reads of the first lies in the workspace `w` was carved from.
-int step_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y, int32_t res_z,
-                 const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays, const mnf_train_opts *opts, StepFills fills, float *losses,
-                 int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, StepWs &w, int64_t *&eff, const float *&bk, mnf_stream_t stream) {
-    hipStream_t s = as_stream(stream);
-    const int32_t cap = scratch_cap(n_rays);
+// _backward are the same two with the caller's own loss in between.  Whatever the second half reads of the first lies in `w` (its march's part: see kept_scan).
+int step_forward(mnf_field_t f, const StepCall &c, StepWs &w, StepFills fills, float *losses) {
     const int C = f->cfg.num_semantic_classes;
-    const int rblocks = (n_rays + 255) / 256;
+    const int rblocks = (c.n_rays + 255) / 256;
     // (losses, counters, skip flag, the three gradient vectors, the pre-pass's density array and work counter: zeroed by planes_kernel)
-    eff = w.totals + 4;                                                    // [0] marched, [1] kept samples the kernels behind the guards work on
     // ---- occupancy sampling (occ_grid.py:80-238): march, density pre-pass, visibility filter
-    const int n_levels = opts->n_levels > 1 ? opts->n_levels : 1;
+    const int n_levels = c.opts->n_levels > 1 ? c.opts->n_levels : 1;
     MNF_REQUIRE(n_levels <= 4, "train_step: at most 4 occupancy levels");
-    int rc = 0;
-    if (const mnf_presample_s *pre = opts->presampled) {
+    if (const mnf_presample_s *pre = c.opts->presampled) {
         // the march of THIS batch ran earlier, on a side stream beside the previous step (mnf_train_presample): adopt what it left, after its last kernel
-        MNF_REQUIRE(pre->valid && pre->rays_o == rays_o && pre->rays_d == rays_d && pre->n_rays == n_rays && pre->binaries == binaries && pre->seed == opts->seed &&
-                    pre->stratified == opts->stratified && pre->n_levels == n_levels && pre->near_plane == opts->near_plane && pre->far_plane == opts->far_plane &&
-                    pre->step == opts->render_step_size && pre->cone == opts->cone_angle && pre->alpha_thre == opts->alpha_thre &&
-                    pre->res[0] == res_x && pre->res[1] == res_y && pre->res[2] == res_z && pre->max_marched == max_marched,
+        MNF_REQUIRE(pre->valid && pre->rays_o == c.rays_o && pre->rays_d == c.rays_d && pre->n_rays == c.n_rays && pre->binaries == c.binaries && pre->seed == c.opts->seed &&
+                    pre->stratified == c.opts->stratified && pre->n_levels == n_levels && pre->near_plane == c.opts->near_plane && pre->far_plane == c.opts->far_plane &&
+                    pre->step == c.opts->render_step_size && pre->cone == c.opts->cone_angle && pre->alpha_thre == c.opts->alpha_thre &&
+                    pre->res[0] == c.res_x && pre->res[1] == c.res_y && pre->res[2] == c.res_z && pre->max_marched == c.max_marched,
                     "train_step: opts->presampled was made for other rays, options, sample bound or another grid");
-        if (hipEventQuery(pre->ev_done) != hipSuccess) MNF_HIP(hipStreamWaitEvent(s, pre->ev_done, 0));      // (a wait on another queue costs the stream ~18 us even when the event is long done)
-        const SampleWs sw = carve_sample((char *)pre->ws, n_rays, cap, max_marched);
-        w.nearp = sw.nearp; w.farp = sw.farp; w.alpha_thre = sw.alpha_thre; w.counts = sw.counts; w.starts = sw.starts; w.totals = sw.totals;
-        w.scratch_ts = sw.scratch_ts; w.scratch_te = sw.scratch_te; w.ts = sw.ts; w.te = sw.te; w.ray = sw.ray;
-        eff = w.totals + 4;
+        if (hipEventQuery(pre->ev_done) != hipSuccess) MNF_HIP(hipStreamWaitEvent(c.stream, pre->ev_done, 0));      // (a wait on another queue costs the stream ~18 us even when the event is long done)
+        static_cast<SampleWs &>(w) = carve_sample(pre->ws, c.n_rays, scratch_cap(c.n_rays), c.max_marched);      // (the two small blocks included: every word of this step is the presample's)
         const_cast<mnf_presample_s *>(pre)->valid = 0;      // (the guards below may clear its counts: one use)
-        fills.ray_counter = reinterpret_cast<int32_t *>(w.totals + 7);
-        fills.adopt = w.totals + kPreReport;
-        hipLaunchKernelGGL(planes_kernel, dim3(fill_blocks(rblocks)), dim3(256), 0, s, 0, 0.f, 0.f, 0.f, 0, 0u, 0u, (float *)nullptr, (float *)nullptr, losses, counts_dev,
-                           skip_dev, fills);
-    } else {
-        const SampleWs sw = {w.nearp, w.farp, w.alpha_thre, w.scratch_ts, w.scratch_te, w.counts, w.starts, w.totals, w.scan, 0};
-        fills.ray_counter = reinterpret_cast<int32_t *>(w.totals + 7);
-        rc = sample_stage(sw, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, losses, counts_dev, skip_dev, fills, s);
-        if (rc) return rc;
+        fills.ray_counter = &w.words->ray_counter;
+        fills.adopt = w.words->pre_report;
+        hipLaunchKernelGGL(planes_kernel, dim3(fill_blocks(rblocks)), dim3(256), 0, c.stream, 0, 0.f, 0.f, 0.f, 0, 0u, 0u, (float *)nullptr, (float *)nullptr, losses, c.counts_dev,
+                           c.skip_dev, fills);
+    } else {      // (a presample has done all three)
+        fills.ray_counter = &w.words->ray_counter;
+        if (const int rc = sample_stage(c, w, losses, fills, c.counts_dev, c.skip_dev)) return rc;
     }
-    if (!opts->presampled) {      // (a presample has done both)
-        // a ray longer than its scratch row would have been truncated (the rows hold `cap` samples; the reference configurations stay far
-        // below) and more marched samples than `max_marched` would not fit the packed arrays: both end the step here, on the device
-        hipLaunchKernelGGL(guard_marched_kernel, dim3(rblocks), dim3(256), 0, s, n_rays, w.counts, w.starts, (const int64_t *)w.totals, max_marched,
-                           (int64_t)cap, eff, counts_dev, skip_dev);
-        rc = mnf_compact_samples(w.scratch_ts, w.scratch_te, cap, w.starts, w.counts, n_rays, w.ts, w.te, w.ray, stream);
-        if (rc) return rc;
-    }
+    int64_t *eff = eff_counts(w);
     bool use_rows = false;
+    FieldIO pp = {};      // the density pre-pass over the marched samples
+    pp.rays_o = c.rays_o; pp.rays_d = c.rays_d; pp.ray_idx64 = w.ray; pp.t_starts = w.ts; pp.t_ends = w.te; pp.n = c.max_marched; pp.density = w.sigma;
     static const bool prepass_flat = diag_env("MNF_PREPASS_FLAT") != nullptr;    // experiment: every marched sample, full lanes, no early termination
     if (prepass_flat) {
-        FieldIO io = {};
-        io.mode = 1; io.rays_o = rays_o; io.rays_d = rays_d; io.ray_idx64 = w.ray; io.t_starts = w.ts; io.t_ends = w.te;
-        io.n = max_marched; io.n_dev64 = eff; io.density = w.sigma;
-        rc = launch_field(f, io, true, s);
+        pp.mode = 1; pp.n_dev64 = eff;
     } else {
         // mnf_field_density_rays without its two memsets (density array, work counter: planes_kernel's fills): ray-major, skips what lies behind T < eps / 2
-        FieldIO io = {};
-        io.mode = 3; io.rays_o = rays_o; io.rays_d = rays_d; io.ray_idx64 = w.ray; io.t_starts = w.ts; io.t_ends = w.te; io.n = max_marched;
-        io.chunk_starts = w.starts; io.chunk_cnts = w.counts; io.n_rays = n_rays; io.ray_counter = fills.ray_counter;
-        io.sdt_stop = opts->early_stop_eps > 0.0f ? -logf(opts->early_stop_eps) + 0.6931472f : INFINITY;
-        io.density = w.sigma;
+        pp.mode = 3; pp.chunk_starts = w.starts; pp.chunk_cnts = w.counts; pp.n_rays = c.n_rays; pp.ray_counter = fills.ray_counter;
+        pp.sdt_stop = c.opts->early_stop_eps > 0.0f ? -logf(c.opts->early_stop_eps) + 0.6931472f : INFINITY;
         static const bool no_rows = diag_env("MNF_NO_ROWS") != nullptr;      // A/B timing: both passes gather
         use_rows = w.rows != nullptr && !no_rows;
-        io.rows_out = use_rows ? w.rows : nullptr;       // (NULL where the rows are not built: the forward then gathers for itself)
-        rc = launch_field(f, io, true, s);
+        pp.rows_out = use_rows ? w.rows : nullptr;       // (NULL where the rows are not built: the forward then gathers for itself)
     }
-    if (rc) return rc;
-    const int vgrid = n_rays < 65535 ? n_rays : 65535;
-    hipLaunchKernelGGL(visibility_kernel<false>, dim3(vgrid), dim3(64), 0, s, n_rays, w.starts, w.counts, w.ts, w.te, w.sigma, opts->early_stop_eps,
-                       w.alpha_thre, w.kept_cnts, (const int64_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
-    rc = mnf_exclusive_scan_i64(w.kept_cnts, n_rays, w.kept_starts, w.totals + 1, w.scan, mnf_scan_workspace_bytes(n_rays), stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(guard_kept_kernel, dim3(rblocks), dim3(256), 0, s, n_rays, w.kept_cnts, w.kept_starts, (const int64_t *)w.totals, max_kept, eff,
-                       counts_dev, skip_dev);
-    hipLaunchKernelGGL(visibility_kernel<true>, dim3(vgrid), dim3(64), 0, s, n_rays, w.starts, w.counts, w.ts, w.te, w.sigma, opts->early_stop_eps,
-                       w.alpha_thre, (int64_t *)nullptr, w.kept_starts, w.k_ts, w.k_te, w.k_ray, use_rows ? w.k_src : (int64_t *)nullptr);
+    if (const int rc = launch_field(f, pp, true, c.stream)) return rc;
+    const int vgrid = c.n_rays < 65535 ? c.n_rays : 65535;
+    hipLaunchKernelGGL(visibility_kernel<false>, dim3(vgrid), dim3(64), 0, c.stream, c.n_rays, w.starts, w.counts, w.ts, w.te, w.sigma, c.opts->early_stop_eps,
+                       &w.scalars->alpha_thre, w.kept_cnts, (const int64_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
+    if (const int rc = mnf_exclusive_scan_i64(w.kept_cnts, c.n_rays, w.kept_starts, &w.words->kept, w.kept_scan, mnf_scan_workspace_bytes(c.n_rays), (mnf_stream_t)c.stream)) return rc;
+    hipLaunchKernelGGL(guard_kept_kernel, dim3(rblocks), dim3(256), 0, c.stream, c.n_rays, w.kept_cnts, w.kept_starts, (const int64_t *)&w.words->marched, c.max_kept, eff,
+                       c.counts_dev, c.skip_dev);
+    hipLaunchKernelGGL(visibility_kernel<true>, dim3(vgrid), dim3(64), 0, c.stream, c.n_rays, w.starts, w.counts, w.ts, w.te, w.sigma, c.opts->early_stop_eps,
+                       &w.scalars->alpha_thre, (int64_t *)nullptr, w.kept_starts, w.k_ts, w.k_te, w.k_ray, use_rows ? w.k_src : (int64_t *)nullptr);
     // ---- sem_rendering (utils.py:362-461): field with saved activations, compositing
     {
         FieldIO io = {};
-        io.mode = 1; io.rays_o = rays_o; io.rays_d = rays_d; io.ray_idx64 = w.k_ray; io.t_starts = w.k_ts; io.t_ends = w.k_te;
-        io.n = max_kept; io.n_dev64 = eff + 1;
+        io.mode = 1; io.rays_o = c.rays_o; io.rays_d = c.rays_d; io.ray_idx64 = w.k_ray; io.t_starts = w.k_ts; io.t_ends = w.k_te;
+        io.n = c.max_kept; io.n_dev64 = &eff[1];
         io.rgb = w.k_rgb; io.density = w.k_sigma; io.sem = w.k_sem; io.xn_out = w.k_pos;        // aabb-normalised: what the backward's scatter reads
-        io.sem_stride = max_kept;                                                                // the step's own logit buffer is class-major: w.k_sem[class * max_kept + sample]
+        io.sem_stride = c.max_kept;                                                                // the step's own logit buffer is class-major: w.k_sem[class * max_kept + sample]
         if (use_rows) { io.rows_in = w.rows; io.rows_src = w.k_src; }                            // every survivor's features: the row the pre-pass left, not 128 gathers
-        rc = forward_train(f, io, w.field_ws, w.field_ws_bytes, s, opts->deterministic != 0);
-        if (rc) return rc;
+        if (const int rc = forward_train(f, io, w.field_ws, w.field_ws_bytes, c.stream, c.opts->deterministic != 0)) return rc;
     }
-    bk = opts->render_bkgd_dev;                                            // the caller's device colour, or the by-value one
-    if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) {
-        float *bkd = w.alpha_thre + 8;                                     // three floats of the small scalar block
-        hipLaunchKernelGGL(set3_kernel, dim3(1), dim3(1), 0, s, bkd, opts->render_bkgd[0], opts->render_bkgd[1], opts->render_bkgd[2]);
-        bk = bkd;
-    }
-    return composite_train_forward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.o_rgb, w.o_acc,
-                                        w.o_dep, w.o_sem, w.k_w, w.k_tr, nullptr, stream);
+    const float *bk = background(w, c.opts);
+    if (bk && !c.opts->render_bkgd_dev)      // the by-value colour, into its three floats of the small scalar block
+        hipLaunchKernelGGL(set3_kernel, dim3(1), dim3(1), 0, c.stream, w.scalars->bkgd, c.opts->render_bkgd[0], c.opts->render_bkgd[1], c.opts->render_bkgd[2]);
+    return composite_train_forward_impl(w.kept_starts, w.kept_cnts, c.n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, c.max_kept, C, c.max_kept, bk, w.o_rgb, w.o_acc,
+                                        w.o_dep, w.o_sem, w.k_w, w.k_tr, nullptr, (mnf_stream_t)c.stream);
 }
 
 // composite_train_backward (g_acc: the caller's opacity gradient, or NULL), the factored output gradient, the field's backward
-int step_backward(mnf_field_t f, const StepWs &w, int32_t n_rays, const mnf_train_opts *opts, const float *bk, const float *g_acc, int64_t *eff, int64_t max_kept,
-                  float *g_base, float *g_head, float *g_sem, mnf_stream_t stream) {
+int step_backward(mnf_field_t f, const StepCall &sc, const StepWs &w, const float *g_acc, float *g_base, float *g_head, float *g_sem) {
     const int C = f->cfg.num_semantic_classes;
     // the rgb / semantic output gradients of a sample are its weight times its ray's loss gradient: the split backward forms them itself from (k_w, k_ray, g_rgb, g_sem)
     // — 12 bytes per sample and cached per-ray vectors instead of 128 bytes written here and read there; the fused backward (mode 2) reads the per-sample arrays
     const bool factored = C > 0;
-    int rc = composite_train_backward_impl(w.kept_starts, w.kept_cnts, n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, max_kept, C, max_kept, bk, w.k_w, w.k_tr, w.o_acc,
-                                           w.o_dep, w.g_rgb, g_acc, w.g_dep, w.g_sem, w.k_dsig, factored ? nullptr : w.k_drgb, factored ? nullptr : w.k_dsem, stream);
+    int rc = composite_train_backward_impl(w.kept_starts, w.kept_cnts, sc.n_rays, w.k_ts, w.k_te, w.k_sigma, w.k_rgb, w.k_sem, sc.max_kept, C, sc.max_kept, background(w, sc.opts),
+                                           w.k_w, w.k_tr, w.o_acc, w.o_dep, w.g_rgb, g_acc, w.g_dep, w.g_sem, w.k_dsig, factored ? nullptr : w.k_drgb,
+                                           factored ? nullptr : w.k_dsem, (mnf_stream_t)sc.stream);
     if (rc) return rc;
     BackwardCall c = {};
-    c.positions = w.k_pos; c.n = max_kept; c.n_dev = eff + 1; c.d_rgb = w.k_drgb; c.d_density = w.k_dsig; c.d_sem = w.k_dsem; c.rgb = w.k_rgb; c.density = w.k_sigma;
-    c.workspace = w.field_ws; c.workspace_bytes = w.field_ws_bytes; c.loss_scale = opts->loss_scale; c.g_base = g_base; c.g_head = g_head; c.g_sem = g_sem;
-    c.positions_normalized = true; c.deterministic = opts->deterministic != 0; c.stream = as_stream(stream);
+    c.positions = w.k_pos; c.n = sc.max_kept; c.n_dev = &eff_counts(w)[1]; c.d_rgb = w.k_drgb; c.d_density = w.k_dsig; c.d_sem = w.k_dsem; c.rgb = w.k_rgb; c.density = w.k_sigma;
+    c.workspace = w.field_ws; c.workspace_bytes = w.field_ws_bytes; c.loss_scale = sc.opts->loss_scale; c.g_base = g_base; c.g_head = g_head; c.g_sem = g_sem;
+    c.positions_normalized = true; c.deterministic = sc.opts->deterministic != 0; c.stream = sc.stream;
     if (factored) c.factored = FactoredGrad{w.k_w, w.k_ray, w.g_rgb, w.g_sem};
     return backward(f, c);
+}
+
+// What the two backward entry points share behind their argument checks: the head (gradients_in_kernel) and step_backward
+int render_backward(mnf_field_t f, const StepCall &c, const StepWs &w, const GradIn &i_rgb, const GradIn &i_acc, const GradIn &i_dep, const GradIn &i_sem, float *g_base,
+                    float *g_head, float *g_sem_params) {
+    const GradFills z = {g_base, g_head, g_sem_params, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem};
+    hipLaunchKernelGGL(gradients_in_kernel, dim3(fill_blocks((c.n_rays + 255) / 256)), dim3(256), 0, c.stream, c.n_rays, f->cfg.num_semantic_classes, i_rgb, i_acc,
+                       i_dep, i_sem, w.g_rgb, w.g_acc, w.g_dep, w.g_sem, z, c.counts_dev, c.skip_dev, eff_counts(w), &w.words->ticket);
+    if (const int rc = launch_status("gradients_in_kernel")) return rc;
+    return step_backward(f, c, w, w.g_acc, g_base, g_head, g_sem_params);
 }
 }  // namespace
 }  // namespace mnf
@@ -661,76 +681,46 @@ extern "C" int mnf_train_step(mnf_field_t f, const uint8_t *binaries, const uint
                               const float *target_rgb, const float *target_depth, const int64_t *target_sem, const mnf_train_opts *opts,
                               float *g_base, float *g_head, float *g_sem, float *losses, int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched,
                               int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MNF_REQUIRE(f && f->params_loaded && opts && aabb_host && counts_dev && skip_dev, "train_step: bad handle or options");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_step: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
+    if (const int rc = check_args("train_step", f && f->params_loaded && aabb_host && counts_dev && skip_dev, opts)) return rc;
     MNF_REQUIRE(binaries && occs && rays_o && rays_d && target_rgb && target_depth && target_sem && g_base && g_head && g_sem && losses && workspace,
                 "train_step: null pointer");
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->render_step_size > 0.f, "train_step: bad sizes");
-    hipStream_t s = as_stream(stream);
-    StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
-    if (workspace_bytes < w.bytes) { set_error("train_step: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    StepCall c = {};
+    c.binaries = binaries; c.bitgrid = bitgrid; c.occs = occs; c.res_x = res_x; c.res_y = res_y; c.res_z = res_z; c.aabb_host = aabb_host; c.rays_o = rays_o; c.rays_d = rays_d;
+    c.n_rays = n_rays; c.opts = opts; c.max_marched = max_marched; c.max_kept = max_kept; c.counts_dev = counts_dev; c.skip_dev = skip_dev; c.stream = as_stream(stream);
+    StepWs w;
+    if (const int rc = open_step("train_step", f, c, opts->render_step_size, workspace, workspace_bytes, w)) return rc;
     const StepFills fills = {g_base, g_head, g_sem, w.sigma, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem, max_marched, nullptr, nullptr};
-    int64_t *eff = nullptr;
-    const float *bk = nullptr;
-    int rc = step_forward(f, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, fills, losses, counts_dev, skip_dev, max_marched, max_kept,
-                          w, eff, bk, stream);
-    if (rc) return rc;
+    if (const int rc = step_forward(f, c, w, fills, losses)) return rc;
     // ---- loss (pipeline.py:506-511) and backward (pipeline.py:518)
-    hipLaunchKernelGGL(loss_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, s, n_rays, f->cfg.num_semantic_classes, w.o_rgb, w.o_dep, w.o_sem, target_rgb, target_depth,
-                       target_sem, w.g_rgb, w.g_dep, w.g_sem, losses, counts_dev + 3, skip_dev);
-    rc = launch_status("loss_kernel");
-    if (rc) return rc;
-    return step_backward(f, w, n_rays, opts, bk, nullptr, eff, max_kept, g_base, g_head, g_sem, stream);
+    hipLaunchKernelGGL(loss_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c.stream, n_rays, f->cfg.num_semantic_classes, w.o_rgb, w.o_dep, w.o_sem, target_rgb,
+                       target_depth, target_sem, w.g_rgb, w.g_dep, w.g_sem, losses, counts_dev + 3, skip_dev);
+    if (const int rc = launch_status("loss_kernel")) return rc;
+    return step_backward(f, c, w, nullptr, g_base, g_head, g_sem);
 }
 
-// The step cut at its loss (include/mi355nerf.h): step_forward now, step_backward later with the caller's gradients.  The words of the workspace's small blocks that
-// only this pair uses (the blocks' map is at carve_step): four floats for the loss terms planes_kernel zeroes (nobody reads them), the head kernel's block ticket
-// and, in the 32 bits behind it, the forward's verdict.
-static inline float *render_losses(const StepWs &w) { return w.alpha_thre + 16; }
-static inline uint32_t *render_ticket(const StepWs &w) { return reinterpret_cast<uint32_t *>(w.totals + 200); }
-
+// The step cut at its loss (include/mi355nerf.h): step_forward now, step_backward later with the caller's gradients, from the same workspace
 extern "C" int mnf_train_render_forward(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y,
                                         int32_t res_z, const float *aabb_host, const float *rays_o, const float *rays_d, int32_t n_rays,
                                         const mnf_train_opts *opts, float *rgb, float *acc, float *depth, float *sem, int64_t *counts_dev, int32_t *skip_dev,
                                         int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MNF_REQUIRE(f && f->params_loaded && opts && aabb_host && counts_dev && skip_dev, "train_render_forward: bad handle or options");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_forward: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
+    if (const int rc = check_args("train_render_forward", f && f->params_loaded && aabb_host && counts_dev && skip_dev, opts)) return rc;
     MNF_REQUIRE(!opts->presampled, "train_render_forward: opts->presampled must be NULL (a presampled march is adopted by mnf_train_step only)");
     MNF_REQUIRE(binaries && occs && rays_o && rays_d && rgb && acc && depth && workspace, "train_render_forward: null pointer");
     MNF_REQUIRE(sem || f->cfg.num_semantic_classes == 0, "train_render_forward: null pointer (sem may be NULL only for a field without semantic classes)");
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->render_step_size > 0.f, "train_render_forward: bad sizes");
     MNF_REQUIRE(opts->n_levels <= 4, "train_render_forward: at most 4 occupancy levels");
-    StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
-    if (workspace_bytes < w.bytes) { set_error("train_render_forward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
+    StepCall c = {};
+    c.binaries = binaries; c.bitgrid = bitgrid; c.occs = occs; c.res_x = res_x; c.res_y = res_y; c.res_z = res_z; c.aabb_host = aabb_host; c.rays_o = rays_o; c.rays_d = rays_d;
+    c.n_rays = n_rays; c.opts = opts; c.max_marched = max_marched; c.max_kept = max_kept; c.counts_dev = counts_dev; c.skip_dev = skip_dev; c.stream = as_stream(stream);
+    StepWs w;
+    if (const int rc = open_step("train_render_forward", f, c, opts->render_step_size, workspace, workspace_bytes, w)) return rc;
     const StepFills fills = {nullptr, nullptr, nullptr, w.sigma, 0, 0, 0, max_marched, nullptr, nullptr};      // (no gradient vector is touched here)
-    int64_t *eff = nullptr;
-    const float *bk = nullptr;
-    int rc = step_forward(f, binaries, bitgrid, occs, res_x, res_y, res_z, aabb_host, rays_o, rays_d, n_rays, opts, fills, render_losses(w), counts_dev, skip_dev, max_marched,
-                          max_kept, w, eff, bk, stream);
-    if (rc) return rc;
+    if (const int rc = step_forward(f, c, w, fills, w.scalars->render_losses)) return rc;
     // (a guard that fired has cleared every per-ray count: the compositing then wrote the background colour and zeros, never what the workspace held before)
     const int C = f->cfg.num_semantic_classes;
     const int64_t widest = (int64_t)n_rays * (C > 3 ? C : 3);
-    hipLaunchKernelGGL(outputs_kernel, dim3((unsigned)((widest + 255) / 256)), dim3(256), 0, as_stream(stream), (int64_t)n_rays, C, w.o_rgb, w.o_acc, w.o_dep, w.o_sem,
-                       rgb, acc, depth, sem, skip_dev, render_ticket(w));
+    hipLaunchKernelGGL(outputs_kernel, dim3((unsigned)((widest + 255) / 256)), dim3(256), 0, c.stream, (int64_t)n_rays, C, w.o_rgb, w.o_acc, w.o_dep, w.o_sem,
+                       rgb, acc, depth, sem, skip_dev, &w.words->ticket);
     return launch_status("outputs_kernel");
-}
-
-// What the two backward entry points share behind their argument checks: the head (gradients_in_kernel) and step_backward
-static int render_backward(mnf_field_t f, const StepWs &w, int32_t n_rays, const mnf_train_opts *opts, const GradIn &i_rgb, const GradIn &i_acc, const GradIn &i_dep,
-                           const GradIn &i_sem, float *g_base, float *g_head, float *g_sem_params, int64_t *counts_dev, int32_t *skip_dev, int64_t max_kept,
-                           mnf_stream_t stream) {
-    int64_t *eff = w.totals + 4;
-    const float *bk = opts->render_bkgd_dev;      // as the forward chose it: the caller's device colour, or the by-value one the forward left in the workspace
-    if (!bk && (opts->render_bkgd[0] != 0.f || opts->render_bkgd[1] != 0.f || opts->render_bkgd[2] != 0.f)) bk = w.alpha_thre + 8;
-    const GradFills z = {g_base, g_head, g_sem_params, (int64_t)f->n_base, (int64_t)f->n_head, (int64_t)f->n_sem};
-    hipLaunchKernelGGL(gradients_in_kernel, dim3(fill_blocks((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), n_rays, f->cfg.num_semantic_classes, i_rgb, i_acc,
-                       i_dep, i_sem, w.g_rgb, w.g_acc, w.g_dep, w.g_sem, z, counts_dev, skip_dev, eff, render_ticket(w));
-    int rc = launch_status("gradients_in_kernel");
-    if (rc) return rc;
-    return step_backward(f, w, n_rays, opts, bk, w.g_acc, eff, max_kept, g_base, g_head, g_sem_params, stream);
 }
 
 extern "C" int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mnf_train_opts *opts, const float *g_rgb, int64_t g_rgb_row_stride,
@@ -738,16 +728,15 @@ extern "C" int mnf_train_render_backward(mnf_field_t f, int32_t n_rays, const mn
                                          const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base, float *g_head, float *g_sem_params,
                                          int64_t *counts_dev, int32_t *skip_dev, int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes,
                                          mnf_stream_t stream) {
-    MNF_REQUIRE(f && f->params_loaded && opts && counts_dev && skip_dev, "train_render_backward: bad handle or options");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_backward: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
+    if (const int rc = check_args("train_render_backward", f && f->params_loaded && counts_dev && skip_dev, opts)) return rc;
     MNF_REQUIRE(!opts->presampled, "train_render_backward: opts->presampled must be NULL");
     MNF_REQUIRE(g_base && g_head && g_sem_params && workspace, "train_render_backward: null pointer");
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0, "train_render_backward: bad sizes");
-    const StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
-    if (workspace_bytes < w.bytes) { set_error("train_render_backward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes); return MNF_ERR_WORKSPACE; }
-    return render_backward(f, w, n_rays, opts, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
-                           GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params, counts_dev, skip_dev, max_kept, stream);
+    StepCall c = {};
+    c.n_rays = n_rays; c.opts = opts; c.max_marched = max_marched; c.max_kept = max_kept; c.counts_dev = counts_dev; c.skip_dev = skip_dev; c.stream = as_stream(stream);
+    StepWs w;
+    if (const int rc = open_step("train_render_backward", f, c, 1.f, workspace, workspace_bytes, w)) return rc;      // (no option of its own has to be positive)
+    return render_backward(f, c, w, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
+                           GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params);
 }
 
 // mnf_train_render_backward, then the ray gradients from what it left in the workspace (inputgrad.hip).  The three parameter pointers all NULL: the parameters are
@@ -757,138 +746,22 @@ extern "C" int mnf_train_render_backward_rays(mnf_field_t f, int32_t n_rays, con
                                               int64_t g_depth_row_stride, const float *g_sem, int64_t g_sem_row_stride, int64_t g_sem_col_stride, float *g_base,
                                               float *g_head, float *g_sem_params, float *g_rays_o, float *g_rays_d, int64_t *counts_dev, int32_t *skip_dev,
                                               int64_t max_marched, int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MNF_REQUIRE(f && f->params_loaded && opts && counts_dev && skip_dev, "train_render_backward_rays: bad handle or options");
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_train_opts), "train_render_backward_rays: opts->struct_size is %u, this library's mnf_train_opts has %zu bytes (MNF_INIT)",
-                opts->struct_size, sizeof(mnf_train_opts));
+    if (const int rc = check_args("train_render_backward_rays", f && f->params_loaded && counts_dev && skip_dev, opts)) return rc;
     MNF_REQUIRE(!opts->presampled, "train_render_backward_rays: opts->presampled must be NULL");
     MNF_REQUIRE(g_rays_o || g_rays_d, "train_render_backward_rays: no ray gradient asked for (mnf_train_render_backward is the call without)");
     MNF_REQUIRE(!g_rays_d || rays_d, "train_render_backward_rays: g_rays_d needs rays_d, the directions the forward was given");
     const bool frozen = !g_base && !g_head && !g_sem_params;
     MNF_REQUIRE(frozen || (g_base && g_head && g_sem_params), "train_render_backward_rays: the three parameter gradients are given together, or all NULL (frozen)");
-    MNF_REQUIRE(n_rays > 0 && max_marched > 0 && max_kept > 0 && opts->loss_scale > 0.f, "train_render_backward_rays: bad sizes");
-    const StepWs w = carve_step((char *)workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept);
-    if (!workspace || workspace_bytes < w.bytes) {
-        set_error("train_render_backward_rays: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes);
-        return MNF_ERR_WORKSPACE;
-    }
-    int rc = render_backward(f, w, n_rays, opts, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
-                             GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params, counts_dev, skip_dev, max_kept, stream);
-    if (rc) return rc;
+    StepCall c = {};
+    c.n_rays = n_rays; c.opts = opts; c.max_marched = max_marched; c.max_kept = max_kept; c.counts_dev = counts_dev; c.skip_dev = skip_dev; c.stream = as_stream(stream);
+    StepWs w;
+    if (const int rc = open_step("train_render_backward_rays", f, c, opts->loss_scale, workspace, workspace_bytes, w)) return rc;
+    if (const int rc = render_backward(f, c, w, GradIn{g_rgb, g_rgb_row_stride, g_rgb_col_stride}, GradIn{g_acc, g_acc_row_stride, 0}, GradIn{g_depth, g_depth_row_stride, 0},
+                                       GradIn{g_sem, g_sem_row_stride, g_sem_col_stride}, g_base, g_head, g_sem_params))
+        return rc;
     RayGradIO io = {};
     io.xn = w.k_pos; io.t_starts = w.k_ts; io.t_ends = w.k_te; io.kept_starts = w.kept_starts; io.kept_cnts = w.kept_cnts;
-    io.n_dev = w.totals + 5; io.skip = skip_dev; io.rays_d = rays_d; io.n_rays = n_rays; io.n = max_kept; io.loss_scale = opts->loss_scale;
+    io.n_dev = &eff_counts(w)[1]; io.skip = skip_dev; io.rays_d = rays_d; io.n_rays = n_rays; io.n = max_kept; io.loss_scale = opts->loss_scale;
     io.g_o = g_rays_o; io.g_d = g_rays_d;
-    return train_render_ray_grad(f, w.field_ws, io, as_stream(stream));
-}
-
-// view groups per member of a scoring call.  FOUR render jobs in flight (the caller's stream + the three shared side streams) is the measured optimum for
-// these small views (profiles/r03_hw_queues.txt: 256 views x 2 members 101.1 ms with 4 jobs, 107.0 with 2; 32 views 21.3 against 22.6; more jobs than
-// streams: worse): two members -> two halves of the pose list each, one member -> four quarters; one half's marcher runs beside another's field kernel.
-// (profiles/r03_split_experiment.txt had two as the optimum: measured when every job still had a stream of its own, see common.h shared_side_stream.)
-static inline int score_groups(int32_t n_views, int32_t n_members = 1) {
-    int g = 4 / (n_members > 0 ? n_members : 1);
-    if (g < 1) g = 1;
-    return g > n_views ? (n_views > 0 ? n_views : 1) : g;
-}
-static inline int32_t group_lo(int32_t n_views, int g, int G) { return (int32_t)((int64_t)n_views * g / G); }
-
-extern "C" int64_t mnf_score_poses_workspace_bytes(int32_t n_members, int32_t n_views, int32_t n_pix, int32_t n_classes) {
-    if (n_members <= 0 || n_views <= 0 || n_pix <= 0 || n_classes <= 0) return -1;
-    const int64_t R = (int64_t)n_views * n_pix;
-    const int64_t per_member = R * (3 + 1 + 1 + n_classes + 3 + 1) * 4 + 8 * 256;
-    const int G = score_groups(n_views, n_members);
-    int64_t render = 0;
-    for (int g = 0; g < G; ++g) render += mnf_render_workspace_bytes((int64_t)(group_lo(n_views, g + 1, G) - group_lo(n_views, g, G)) * n_pix, n_pix) + 256;
-    return R * 24 + 512 + n_members * (per_member + render + 64 * G + 256) + 4096;
-}
-
-// What mnf_score_poses and mnf_score_trajectory share: c2w -> the sub-sampled rays of every view -> every member's render as jobs of ONE mnf_render_jobs call,
-// the outputs the scorer reads laid out member-major in the workspace.  probabilistic: rgb_var / depth_var / acc / sem are member-major and the plain rgb / depth
-// go to per-member scratch; otherwise rgb / depth / acc / sem are member-major and no variance is rendered.
-struct MemberStacks { float *rgb_var, *depth_var, *rgb, *depth, *acc, *sem; int C; char *tail; int64_t tail_bytes; };      // tail: the workspace past every job's
-
-static int render_members(const char *what, const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
-                          int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w, int32_t n_views,
-                          int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix, const mnf_render_opts *opts, bool probabilistic,
-                          const void *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream, MemberStacks *st) {
-    MNF_REQUIRE(fields_host && binaries_host && aabb_host && c2w && opts && terms && workspace && pix_idx, "%s: null pointer", what);
-    MNF_REQUIRE(opts->struct_size == sizeof(mnf_render_opts), "%s: opts->struct_size is %u, this library's mnf_render_opts has %zu bytes (MNF_INIT)", what,
-                opts->struct_size, sizeof(mnf_render_opts));
-    MNF_REQUIRE(n_members >= 1 && n_members <= 16 && n_views >= 1 && n_pix >= 1, "%s: bad sizes", what);
-    const int C = fields_host[0]->cfg.num_semantic_classes;
-    for (int m = 1; m < n_members; ++m) MNF_REQUIRE(fields_host[m]->cfg.num_semantic_classes == C, "%s: members disagree on the class count", what);
-    const int64_t need = probabilistic ? mnf_score_poses_workspace_bytes(n_members, n_views, (int32_t)n_pix, C)
-                                       : mnf_score_trajectory_workspace_bytes(n_members, n_views, (int32_t)n_pix, C);
-    if (workspace_bytes < need) { set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)need); return MNF_ERR_WORKSPACE; }
-    const int64_t R = (int64_t)n_views * n_pix;
-    char *base = (char *)workspace;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base + off; off += (b + 255) & ~(size_t)255; return p; };
-    float *o = (float *)take(R * 12), *d = (float *)take(R * 12);
-    // member-major stacks, exactly what mnf_score_views / mnf_score_ensemble_views read
-    float *wide = (float *)take((size_t)n_members * R * 12), *narrow = (float *)take((size_t)n_members * R * 4);
-    float *acc = (float *)take((size_t)n_members * R * 4), *sem = (float *)take((size_t)n_members * R * C * 4);
-    int rc = mnf_generate_rays(c2w, n_views, width, height, focal, pix_idx, n_pix, o, d, stream);
-    if (rc) return rc;
-    mnf_render_opts ro = *opts;
-    ro.probabilistic = probabilistic ? 1 : 0; ro.rays_per_view = (int32_t)n_pix; ro.bitgrid = nullptr;      // (the caller's view_order, if any, applies to every view)
-    if (!probabilistic) ro.render_bkgd[0] = ro.render_bkgd[1] = ro.render_bkgd[2] = 0.f;
-    // every (member, half of the pose list) is a render job of its own: they advance side by side (mnf_render_jobs)
-    const int G = score_groups(n_views, n_members);
-    std::vector<mnf_render_job> jobs;
-    for (int m = 0; m < n_members; ++m) {
-        float *rgb = nullptr, *depth = nullptr;
-        if (probabilistic) { rgb = (float *)take(R * 12); depth = (float *)take(R * 4); }          // outputs the scorer does not read
-        else { rgb = wide + (size_t)m * R * 3; depth = narrow + (size_t)m * R; }
-        for (int g = 0; g < G; ++g) {
-            const int64_t r0 = (int64_t)group_lo(n_views, g, G) * n_pix, r1 = (int64_t)group_lo(n_views, g + 1, G) * n_pix;
-            mnf_render_job j = {};
-            j.struct_size = (uint32_t)sizeof(j);
-            j.field = fields_host[m]; j.binaries = binaries_host[m]; j.bitgrid = bitgrids_host ? bitgrids_host[m] : nullptr;
-            j.rays_o = o + 3 * r0; j.rays_d = d + 3 * r0; j.n_rays = r1 - r0;
-            j.rgb = rgb + 3 * r0; j.depth = depth + r0;
-            j.acc = acc + (size_t)m * R + r0; j.sem = sem + ((size_t)m * R + r0) * C;
-            if (probabilistic) { j.rgb_var = wide + ((size_t)m * R + r0) * 3; j.depth_var = narrow + (size_t)m * R + r0; }
-            j.total_samples = (int64_t *)take(64);
-            j.workspace_bytes = mnf_render_workspace_bytes(r1 - r0, (int32_t)n_pix);
-            j.workspace = take((size_t)j.workspace_bytes);
-            jobs.push_back(j);
-        }
-    }
-    MNF_REQUIRE((int64_t)off <= workspace_bytes, "%s: internal workspace accounting error", what);
-    *st = MemberStacks{probabilistic ? wide : nullptr, probabilistic ? narrow : nullptr, probabilistic ? nullptr : wide, probabilistic ? nullptr : narrow, acc, sem, C,
-                       base + off, workspace_bytes - (int64_t)off};
-    return mnf_render_jobs(jobs.data(), (int32_t)jobs.size(), res_x, res_y, res_z, aabb_host, &ro, stream);
-}
-
-extern "C" int mnf_score_poses(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
-                               int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
-                               int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
-                               const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MemberStacks st;
-    int rc = render_members("score_poses", fields_host, binaries_host, bitgrids_host, n_members, res_x, res_y, res_z, aabb_host, c2w, n_views, width, height, focal,
-                            pix_idx, n_pix, opts, true, terms, workspace, workspace_bytes, stream, &st);
-    if (rc) return rc;
-    return mnf_score_views(st.rgb_var, st.depth_var, st.acc, st.sem, n_members, n_views, (int32_t)n_pix, st.C, terms, stream);
-}
-
-extern "C" int64_t mnf_score_trajectory_workspace_bytes(int32_t n_members, int32_t n_views, int32_t n_pix, int32_t n_classes) {
-    if (n_members <= 0 || n_views <= 0 || n_pix <= 0 || n_classes <= 0) return -1;
-    const int64_t R = (int64_t)n_views * n_pix;
-    const int64_t per_member = R * (3 + 1 + 1 + n_classes) * 4 + 4 * 256;
-    const int G = score_groups(n_views, n_members);
-    int64_t render = 0;
-    for (int g = 0; g < G; ++g) render += mnf_render_workspace_bytes((int64_t)(group_lo(n_views, g + 1, G) - group_lo(n_views, g, G)) * n_pix, n_pix) + 256;
-    return R * 24 + 512 + n_members * (per_member + render + 64 * G + 256) + 4096 + mnf_score_ensemble_views_workspace_bytes(n_views, n_pix, n_classes) + 256;
-}
-
-extern "C" int mnf_score_trajectory(const mnf_field_t *fields_host, const uint8_t *const *binaries_host, const uint32_t *const *bitgrids_host,
-                                    int32_t n_members, int32_t res_x, int32_t res_y, int32_t res_z, const float *aabb_host, const float *c2w,
-                                    int32_t n_views, int32_t width, int32_t height, float focal, const int64_t *pix_idx, int64_t n_pix,
-                                    const mnf_render_opts *opts, double *terms, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    MemberStacks st;
-    int rc = render_members("score_trajectory", fields_host, binaries_host, bitgrids_host, n_members, res_x, res_y, res_z, aabb_host, c2w, n_views, width, height,
-                            focal, pix_idx, n_pix, opts, false, terms, workspace, workspace_bytes, stream, &st);
-    if (rc) return rc;
-    return mnf_score_ensemble_views(st.rgb, st.depth, st.acc, st.sem, n_members, 1, n_views, n_pix, st.C, terms, st.tail, st.tail_bytes, stream);
+    return train_render_ray_grad(f, w.field_ws, io, c.stream);
 }

@@ -1310,7 +1310,7 @@ def _render_members(radiance_fields, estimators, o, d, P, planes, **opts):
 
 
 def _score_one_call(entry, workspace_bytes, radiance_fields, estimators, poses, width, height, focal, scale, device, **opts):
-    """ONE C call `entry` (csrc/trainstep.hip: mnf_score_poses, mnf_score_trajectory; `workspace_bytes` its size entry): poses -> the sub-sampled
+    """ONE C call `entry` (csrc/score.hip: mnf_score_poses, mnf_score_trajectory; `workspace_bytes` its size entry): poses -> the sub-sampled
     rays of every view -> renders by every ensemble member with `opts` (near_plane, render_step_size, cone_angle, alpha_thre, probabilistic)
     -> per-view terms [V,4] float64."""
     V, M = poses.shape[0], len(radiance_fields)
@@ -1375,7 +1375,7 @@ def score_views(radiance_fields, estimators, poses, width, height, focal, near_p
 @torch.no_grad()
 def score_poses(radiance_fields, estimators, poses, width, height, focal, near_plane, render_step_size, scale, cone_angle,
                 alpha_thre, device="cuda:0"):
-    """`score_views` on one rank as ONE C call (`mnf_score_poses`, csrc/trainstep.hip): poses -> the sub-sampled rays of every
+    """`score_views` on one rank as ONE C call (`mnf_score_poses`, csrc/score.hip): poses -> the sub-sampled rays of every
     view -> probabilistic renders by every ensemble member -> per-view terms.  Returns (terms [V,4] float64, score)."""
     lib = L.load_library()
     terms = _score_one_call(lib.mnf_score_poses, lib.mnf_score_poses_workspace_bytes, radiance_fields, estimators, np.asarray(poses), width, height, focal, scale, device,
@@ -1522,7 +1522,7 @@ def trajectory_uncertainty(radiance_fields, estimators, trajectory, step, width,
     """`ActiveNeRFMapper.trajector_uncertainty` (pipeline.py:800-916): the 40 `trajectory_view_indices` poses of `trajectory` rendered by
     every ensemble member (plain render, black background, 1024 samples per round: `render_image_from_pose`), reduced to the four clipped
     rows on the device, ONE host copy of [V,4] doubles at the end.  `one_call=True` and no sharding: one C call (`mnf_score_trajectory`,
-    csrc/trainstep.hip); otherwise `_render_jobs` followed by `ensemble_view_terms`, the views sharded over the ranks of `group` exactly as
+    csrc/score.hip); otherwise `_render_jobs` followed by `ensemble_view_terms`, the views sharded over the ranks of `group` exactly as
     `score_views` shards them (`group=False`: all views on this rank, no exchange).  All routes give the same bits.
     Returns (uncertainty, max_idx, rows): the first two as `trajectory_uncertainty_from_terms`, `rows` the [4,V] float64 host array
     that the reference appends to `trajector_uncertainty_list[step - 1]`."""

@@ -1,5 +1,5 @@
 """The ensemble-disagreement trajectory scorer on the device: `mnf_score_ensemble_views` (csrc/ensemble.hip), `mnf_score_trajectory`
-(csrc/trainstep.hip) and their Python routes `render.ensemble_view_terms` / `render.trajectory_uncertainty`, against
+(csrc/score.hip) and their Python routes `render.ensemble_view_terms` / `render.trajectory_uncertainty`, against
 
   * the RUNNING reference (`ActiveNeRFMapper.trajector_uncertainty`, scripts/pipeline.py:800-916; tests/golden/trajectory.npz), and
   * the float64 numpy restatement of test_trajectory_uncertainty_cpu.py, which that golden pins to 1e-12,
@@ -276,3 +276,58 @@ def test_bad_sizes_return_the_error_code_and_launch_nothing():
         RD.ensemble_view_terms(r(2, V, P, 3), r(2, V, P + 1), r(2, V, P), r(1, V, P, 4))
     with pytest.raises(L.MnfError):
         RD.ensemble_view_terms(r(2, V, P, 3).cpu(), r(2, V, P), r(2, V, P), r(1, V, P, 4))
+
+
+# ------------------------------------------------------------------ 8. the scoring workspace at exactly its size (csrc/score.hip: carve_score)
+SENTINEL, TAIL = 0xA5, 4096
+
+
+@pytest.fixture(scope="module")
+def ensemble(golden):
+    g = golden("trajectory")
+    sc = scene_of(g)
+    return g, sc["kw"], [_hip_ngp_field(g, s) for s in g["param_seeds"]], [_hip_estimator(sc), _hip_estimator(sc)]
+
+
+# members x views: two groups of 1 and 2 views per member, three groups of one view, four uneven groups (1, 1, 1, 2 views)
+@pytest.mark.parametrize("M,V", [(2, 3), (1, 3), (1, 5)])
+@pytest.mark.parametrize("name", ["mnf_score_poses", "mnf_score_trajectory"])
+def test_scoring_fits_exactly_the_workspace_it_asks_for(ensemble, name, M, V):
+    """Both one-call scorers, through `_lib` directly, in a workspace of exactly the size their size function returns, with a sentinel
+    tail behind it: the terms are those of the same call in a workspace 1 MB larger, no byte behind the size is written, and one
+    byte less is refused.  The size is the layout run on a null base, so nothing pads it: the tail is what shows that it suffices."""
+    import ctypes
+    from apnrf_amd import _lib as L
+    from apnrf_amd import render as RD
+    g, kw, fields, ests = ensemble
+    lib = L.load_library()
+    W, Hh, focal = (float(x) for x in g["whf"])
+    W, Hh, P = int(W), int(Hh), 8 * 8
+    poses = np.asarray(g["trajectory"])[RD.trajectory_view_indices(len(g["trajectory"]))][:V]
+    c2w = torch.from_numpy(np.stack([RD.pose_to_c2w(np.asarray(p, np.float64)) for p in poses]).astype(np.float32)[:, :3, :4].copy()).to(DEV)
+    idx = torch.from_numpy(RD.subsample_indices(W * Hh, P)).to(DEV)
+    handles = (ctypes.c_void_p * M)(*[f._ensure_handle() for f in fields[:M]])
+    grids = [RD._grid_args(e) for e in ests[:M]]
+    bins = (ctypes.c_void_p * M)(*[x.binaries.data_ptr() for x in grids])
+    bits = (ctypes.c_void_p * M)(*[x.bits.data_ptr() for x in grids])
+    ropts = RD._render_opts(max_samples=1024, far_plane=1e10, early_stop_eps=1e-4, rays_per_view=P, n_levels=grids[0].n_levels, near_plane=kw["near_plane"],
+                            render_step_size=kw["render_step_size"], cone_angle=kw["cone_angle"], alpha_thre=kw["alpha_thre"],
+                            probabilistic=name == "mnf_score_poses")
+    nbytes = int(getattr(lib, name + "_workspace_bytes")(M, V, P, fields[0].num_semantic_classes))
+    assert nbytes > 0
+
+    def run(ws, given):
+        terms = torch.full((V, 4), float("nan"), dtype=torch.float64, device=DEV)
+        L.launch(getattr(lib, name), handles, bins, bits, M, *grids[0].res, grids[0].aabb, L.ptr(c2w), V, W, Hh, float(np.float32(focal)), L.ptr(idx), P,
+                 ctypes.byref(ropts), L.ptr(terms), L.ptr(ws), given)
+        torch.cuda.synchronize()
+        return terms
+
+    roomy = run(torch.zeros(nbytes + (1 << 20), dtype=torch.uint8, device=DEV), nbytes + (1 << 20))
+    exact_ws = torch.full((nbytes + TAIL,), SENTINEL, dtype=torch.uint8, device=DEV)
+    exact = run(exact_ws, nbytes)
+    assert torch.isfinite(roomy).all()
+    assert torch.equal(exact, roomy)
+    assert bool((exact_ws[nbytes:] == SENTINEL).all()), "a byte behind the size the library asked for was written"
+    with pytest.raises(L.MnfError, match="workspace too small"):
+        run(exact_ws, nbytes - 1)

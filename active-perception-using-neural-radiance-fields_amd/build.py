@@ -5,7 +5,7 @@ Two libraries come out of one set of sources:
 
   libmi355nerf.so        the product.  No environment variable changes what it computes or how it schedules work.
   libmi355nerf_diag.so   the same code compiled with -DMNF_DIAG: the diagnostic knobs of tools/README.md (MNF_ROUND_LOG,
-                         MNF_MIN_SAMPLES, MNF_COMPOSITE_GENERAL, MNF_FIELD_SPLIT / _PIPE, MNF_HASH_BWD_*) are read from the
+                         MNF_MIN_SAMPLES, MNF_COMPOSITE_GENERAL, MNF_FIELD_ACTIVE_WAVES, MNF_HASH_BWD_*) are read from the
                          environment.  Loaded only when MNF_LIB_PATH points at it (tools/, one compositing test).
 """
 import os
@@ -29,6 +29,7 @@ SOURCES = {
     "march.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "score.hip": ["-ffp-contract=off"],
+    "field_api.hip": [],                   # the field handle and the forward's C entry points: operand-type independent, no diagnostic knob
     "field.hip": ["-fno-slp-vectorize"],   # packed-fp32 pairing of the compositing butterflies keeps their DPP operands from folding into the adds
     "train.hip": [],
     "scatter.hip": [],

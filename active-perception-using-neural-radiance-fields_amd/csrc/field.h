@@ -1,4 +1,6 @@
-// Radiance-field handle shared between field.hip (kernels) and render.hip (fused renderer).
+// Radiance-field handle and the structs of the field's calls, shared by every unit that evaluates or trains the field.  field_api.hip owns the handle: it creates,
+// fills (level table, fragment gather table) and destroys it and holds the forward's C entry points; field.hip holds the forward kernels and their launch per
+// operand type; train.hip lazily attaches train_state; render.hip, trainstep.hip and occupancy.hip call launch_field.
 #pragma once
 #include <vector>
 
@@ -83,12 +85,6 @@ struct FieldIO {
     int32_t n_rays;
     int32_t *ray_counter;
     float sdt_stop;                          // stop a ray once its accumulated sigma * dt exceeds this
-    // two-launch forms of the field evaluation (enc != NULL): phase 0 = gather launch then MLP launch on one stream (diagnostic
-    // MNF_FIELD_SPLIT), 1 = gather launch only, 2 = MLP launch only; both restricted to tile chunk `chunk` of `n_chunks`
-    // (0 / 0 = all tiles).  The renderer's pipelined mode (MNF_FIELD_PIPE) runs phase 1 of chunk i+1 beside phase 2 of chunk i.
-    int32_t phase, chunk, n_chunks, mlp_waves, gather_grid;
-    const void *enc;                         // optional [ceil(n/64)][8][64] x 16 B feature scratch: non-null selects the
-                                             // two-launch path (encode_kernel, then the MLP kernel on its output)
     // outputs: user layout (modes 0,1) ...
     float *rgb, *density, *sem;
     float *positions_out;                    // mode 1, optional: the sample positions [n,3] the kernel formed (the backward's scatter reads them)
@@ -161,7 +157,7 @@ struct BackwardCall {
     hipStream_t stream;
 };
 
-// dispatchers on the handle's operand type (defined once, in the fp16 translation units)
+// dispatchers on the handle's operand type, defined once: launch_field in field_api.hip, the others in the fp16 translation unit of train.hip / inputgrad.hip
 void free_train_state(mnf_field_t f);
 int launch_field(mnf_field_t f, const FieldIO &io, bool density_only, hipStream_t stream, const TrainBuf *train = nullptr);
 // training forward / backward

@@ -129,7 +129,6 @@ struct KernelArgs {
     int C;
     int out_fp16;           // mnf_field_config.output_fp16: round every network output to fp16 (tcnn's hand-over precision)
     int active_waves;       // experiment knob (MNF_FIELD_ACTIVE_WAVES): waves per workgroup that take tiles, default 8
-    int blend16;            // mnf_field_config.blend_fp16: the hash levels' 8-corner blend as fp16 fused multiply-adds (tcnn's T = __half arithmetic)
     const LevelMeta *levels;   // [16] in device memory, wave-uniform: read with scalar loads where a batch needs them
                                // (as a by-value kernarg array the 112 dwords were all loaded up front and lived in
                                // spilled SGPRs: ~1000 v_readlane per tile)

@@ -43,14 +43,10 @@ struct RenderWs {
     int32_t *col_ray;
     float *col_ts, *col_te;
     int32_t *tile_hdr;   // per 64-column tile: stride (= the view's budget this round) | view << 8
-    void *enc;           // hash features of the round's columns in MLP fragment order (two-launch field path)
+    void *kernarg_pad;   // unused.  Holds col_cap at its offset in the marcher's kernel arguments: 8 bytes earlier the compiler groups the kernels' scalar
+                         // argument loads differently and round_march_kernel<true, false> grows from 1688 to 1796 instructions
     int64_t col_cap;
 };
-
-static bool split_field() {
-    static const bool on = diag_env("MNF_FIELD_SPLIT") != nullptr;
-    return on;
-}
 
 static hipEvent_t *log_events() {
     static hipEvent_t ev[4];
@@ -91,7 +87,7 @@ static int64_t carve(RenderWs &ws, char *base, int64_t n_rays, int32_t rays_per_
     ws.col_ts = c.take<float>(col_cap);
     ws.col_te = c.take<float>(col_cap);
     ws.tile_hdr = c.take<int32_t>(col_cap / 64);
-    ws.enc = split_field() ? c.take((col_cap / 64 + 1) * 8192) : nullptr;   // two-launch path: 128 B per column
+    ws.kernarg_pad = nullptr;
     ws.col_cap = col_cap;
     return c.bytes();
 }
@@ -457,7 +453,6 @@ int job_begin(RenderJob &j, mnf_field_t f, const uint8_t *binaries, int32_t res_
     // (A/B builds; tests/diag_tile_order.py: the two orders render the same bits)
     if (!diag_env("MNF_FIELD_STATIC_TILES")) io.tickets = j.ws.tickets;
 #endif
-    io.enc = split_field() ? j.ws.enc : nullptr;   // MNF_FIELD_SPLIT (diagnostic: gather and MLP as two launches on one stream)
     io.fr.tile_hdr = j.ws.tile_hdr; io.fr.alive = j.ws.alive; io.fr.alive_count = j.ws.alive_count;
     io.fr.n_samples = j.ws.n_samples; io.fr.rgb = rgb; io.fr.acc = acc; io.fr.depth = depth; io.fr.sem = sem;
     io.fr.rgb_var = j.out.rgb_var; io.fr.depth_var = j.out.depth_var;

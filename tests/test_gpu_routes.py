@@ -288,3 +288,32 @@ def test_exclusive_scan_bucket_edges(n):
     L.launch(lib.mnf_exclusive_scan_i64, L.ptr(buf), n, L.ptr(buf), L.ptr(total), L.ptr(ws), nbytes)
     np.testing.assert_array_equal(buf.cpu().numpy(), want)
     assert int(total) == int(x.sum())
+
+
+# ------------------------------------------------------------------ field forward: the one dispatch row no other test reaches (csrc/field.hip kernel_for)
+@pytest.mark.parametrize("bf16", [False, True])
+def test_forward_samples_fp16_blend_route(bf16):
+    """`mnf_field_forward_samples` with rgb and logits (mode 1, not density-only) and tcnn's fp16 blend: field_kernel<128, NH, 1, false, 0, FEAT_GATHER, true> of
+    both units.  The other fp16-blend rows have their tests in test_gpu_precision_modes.py (forward and density on positions, density on samples and ray-major,
+    both train forwards, the renderer).  n = 513: nine tiles, two workgroups.  Against the oracle's fp16 blend on the positions the kernel forms, at this file's
+    forward bar (rgb and logits 1e-3 absolute, density 2e-3 relative; 8x in the bf16 unit, as test_gpu_precision_modes.BF16)."""
+    n, tol = 513, (8.0 if bf16 else 1.0)
+    sc = H.make_scene(neurons=128, layers=2, C=17, log2_hashmap_size=12, head_gain=2.0)
+    hip = H.hip_field(sc, mfma_bf16=bf16, tcnn_blend_fp16=True)
+    orc = H.oracle_field(sc, precision="bf16" if bf16 else "f16", blend="f16")
+    o, d = H.view_rays(sc, 3, h=16, w=16)
+    rng = np.random.default_rng(2)
+    ri = np.sort(rng.integers(0, 256, n))
+    ts = rng.uniform(0.2, 4.0, n).astype(np.float32)
+    te = ts + 0.003
+    with torch.no_grad():
+        rgb, sigma, sem = hip.forward_samples(o.to(DEV), d.to(DEV), _cu(ri), _cu(ts), _cu(te))
+        plain = H.hip_field(sc, mfma_bf16=bf16).forward_samples(o.to(DEV), d.to(DEV), _cu(ri), _cu(ts), _cu(te))
+    pos = o[ri] + d[ri] * (torch.from_numpy(ts) + torch.from_numpy(te))[:, None] / 2.0
+    r_rgb, r_sigma, r_sem = orc(pos, d[ri])
+    inside = (r_sigma[:, 0] > 0).numpy()
+    assert 50 < inside.sum() and (sigma.cpu().numpy() > 0).tolist() == inside.tolist()
+    np.testing.assert_allclose(sigma.cpu().numpy(), r_sigma.numpy()[:, 0], rtol=2e-3 * tol, atol=1e-6)
+    np.testing.assert_allclose(rgb.cpu().numpy()[inside], r_rgb.numpy()[inside], atol=1e-3 * tol, rtol=0)
+    np.testing.assert_allclose(sem.cpu().numpy()[inside], r_sem.numpy()[inside], atol=1e-3 * tol, rtol=2e-3 * tol)
+    assert not torch.equal(plain[2], sem) and not torch.equal(plain[1], sigma), "the blend switch has no effect on this route"

@@ -188,6 +188,15 @@ SIGNATURES = {
     "mnf_score_trajectory_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mnf_score_trajectory": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                        c_float, c_void_p, c_int64, POINTER(RenderOpts), c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_object_map_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "mnf_object_map_insert": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_float, c_float, c_float, c_void_p]),
+    "mnf_object_map_count": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mnf_object_map_clusters_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int64]),
+    "mnf_object_map_clusters": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_int32, c_int32, c_int64, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_object_map_match": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
 }
 
 

@@ -789,6 +789,74 @@ int mnf_frames_views(const float *rgb, const float *depth, const float *acc, con
                      uint8_t *rgb8, uint8_t *dep8, uint8_t *occ8, uint8_t *sem8, uint8_t *labels,
                      mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- semantic object map */
+
+/* The object count of scripts/eval/eval_pipeline_offline.py ("objects detected over planning steps"): one voxel grid per class filled
+ * from depth and label images, its clusters, and their greedy match to the ground-truth object positions.
+ *
+ * The map is a caller-owned, persistent bit grid uint32 bits[C][wpp] over res_x x res_y x res_z voxels of edge voxel_size whose corner
+ * is grid_min (three host floats): voxel (x, y, z) of class c is bit (lin & 31) of word c * wpp + (lin >> 5) with
+ * lin = (x * res_y + y) * res_z + z (the estimator's layout) and wpp = ceil(X Y Z / 32) ROUNDED UP TO AN EVEN NUMBER, so that every
+ * plane starts 8-byte aligned (at most 32 + 31 padding bits per plane; they are never set and every reader masks them).
+ * mnf_object_map_bytes returns C * wpp * 4, or 0 for a geometry the map does not index (a non-positive size, an axis above 2^24,
+ * more than 2^31 - 64 voxels per class or 2^31 - 1 words in all).  Clearing the map is a memset to 0.
+ *
+ * mnf_object_map_insert replaces eval_pipeline_offline.py:119-138 (per view and class: the depth image with every other class set to
+ * NaN, through VoxelGrid.insert_depth_image; VoxelGrid itself is not part of the reference tree, so the voxelisation is defined here).
+ * It ORs n_rays pixels into the map: origins, viewdirs [N,3] f32 (what mnf_generate_rays writes), depth [N] f32 (the distance along
+ * the ray), acc [N] f32 or NULL, and exactly one label source: sem [N,C] f32 logits, whose class is the first maximal logit (the label
+ * mnf_eval_views predicts), or labels [N], int64 or, with label_is_u8, uint8.  A pixel is skipped when its class is < first_class or
+ * >= C (the reference skips label 0: first_class = 1), when its depth is NaN or infinite, <= min_depth or > max_depth, or when acc is
+ * given and acc < min_acc.  Otherwise, per axis in float32, each operation rounded separately: p = o + depth * d,
+ * i = floor((p - grid_min) * inv) with inv = 1.0f / voxel_size; the pixel is kept when 0 <= i < res on all three axes and sets its
+ * voxel's bit (a plain load first, a 32-bit atomic OR only where the bit is clear).  Inserts accumulate.  n_rays == 0 returns MNF_OK.
+ *
+ * mnf_object_map_count writes the set voxels per class (popcount) to counts [C] int64 on the device.
+ *
+ * mnf_object_map_clusters replaces eval_pipeline_offline.py:26-42 (get_pointcloud, DBSCAN(eps=0.2, min_samples=1), np.mean per
+ * label).  Two voxels of one class are linked when their INTEGER offset has dx^2 + dy^2 + dz^2 <= link_r2 (1 .. 8; 4 is the
+ * reference's radius of two voxels, 3 the 26-neighbourhood); the clusters are the connected components, which is DBSCAN(eps =
+ * sqrt(link_r2), min_samples = 1) on the integer coordinates.  (On the float centres (i + 0.5) * 0.1 the distance of two voxels two
+ * apart comes out as 0.2 or as 0.20000000000000004 depending on i, and eps = 0.2 links only some of them.)  Clusters of fewer than
+ * min_cluster_voxels (>= 1) voxels are dropped.  Clusters are ordered by class, then by the smallest linear index they hold.
+ * Outputs on the device: clusters [max_clusters,5] f64 rows (class, voxel count, cx, cy, cz) with
+ * c = (double)grid_min + (sum / count + 0.5) * (double)voxel_size from exact int64 coordinate sums; cluster_counts [C] int64, the
+ * kept clusters per class; info [4] int64 = {set voxels, kept clusters, set voxels > max_voxels, kept clusters > max_clusters}; and,
+ * when non-NULL, the labelled point cloud: voxel_ids [max_voxels] int64 = class * (X Y Z) + lin in ascending order and voxel_cluster
+ * [max_voxels] int32, the row number of each voxel's cluster (its true number, also where that is >= max_clusters) or -1 where the
+ * cluster was dropped.  When the set voxels exceed max_voxels only info is written; when the kept clusters exceed max_clusters the
+ * first max_clusters rows are written and info[1] and cluster_counts hold the true numbers.  Nothing is written past a capacity.
+ * All sums are integer: the same map gives the same bytes.  workspace: mnf_object_map_clusters_workspace_bytes(C, X, Y, Z,
+ * max_voxels) bytes (0 for bad arguments), 8-byte aligned.
+ *
+ * mnf_object_map_match replaces eval_pipeline_offline.py:45-70.  gt_locs [G,3] f64 and gt_class [G] int32 on the device are the
+ * ground-truth objects, in index order within a class.  Per class the clusters are walked in row order: each takes the nearest
+ * still-unmatched object of its class, distance sqrt((dx dx + dy dy) + dz dz) in float64, provided that distance is strictly below
+ * det_dist_thresh and strictly below 10.0; of equal distances the lowest index wins; a matched object is out of the running.
+ * Outputs: detected [C] int32 (what update_sem_step returns), match [max_clusters] int32 = the object of each written row or -1 (rows
+ * that clusters did not write are not touched), gt_match [G] int32 = the row that took each object or -1.  `clusters` and `info` are
+ * mnf_object_map_clusters' outputs, max_clusters the capacity they were written with.
+ *
+ * Argument errors (a null required pointer, a non-positive resolution or voxel_size, link_r2 outside 1 .. 8, both label sources or
+ * neither, first_class outside [0, C), a negative capacity, a misaligned workspace or one that is too small) return MNF_ERR_INVALID
+ * before any HIP call.  Profile labels: "object_map_insert", "object_map_count", "object_map_clusters", "object_map_match".  Every
+ * call enqueues on `stream` and none synchronises. */
+int64_t mnf_object_map_bytes(int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z);
+int mnf_object_map_insert(uint32_t *bits, int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z, const float *grid_min_host,
+                          float voxel_size, int32_t first_class, const float *origins, const float *viewdirs, const float *depth,
+                          const float *acc, const float *sem, const void *labels, int32_t label_is_u8, int64_t n_rays,
+                          float min_depth, float max_depth, float min_acc, mnf_stream_t stream);
+int mnf_object_map_count(const uint32_t *bits, int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z, int64_t *counts,
+                         mnf_stream_t stream);
+int64_t mnf_object_map_clusters_workspace_bytes(int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z, int64_t max_voxels);
+int mnf_object_map_clusters(const uint32_t *bits, int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z,
+                            const float *grid_min_host, float voxel_size, int32_t link_r2, int32_t min_cluster_voxels,
+                            int64_t max_voxels, int64_t max_clusters, double *clusters, int64_t *cluster_counts, int64_t *info,
+                            int64_t *voxel_ids, int32_t *voxel_cluster, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+int mnf_object_map_match(const double *clusters, const int64_t *info, int64_t max_clusters, int32_t n_classes, const double *gt_locs,
+                         const int32_t *gt_class, int32_t n_gt, double det_dist_thresh, int32_t *detected, int32_t *match,
+                         int32_t *gt_match, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,15 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mnf_object_map_match": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "mnf_explore_map_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "mnf_explore_map_insert": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_float, c_float, c_void_p, c_void_p]),
+    "mnf_explore_map_count": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mnf_explore_map_topdown": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mnf_explore_map_frontiers": (c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_explore_map_frontier_clusters_workspace_bytes": (c_int64, [c_int32, c_int32, c_int64, c_int64]),
+    "mnf_explore_map_frontier_clusters": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_double,
+                                                    c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -857,6 +857,82 @@ int mnf_object_map_match(const double *clusters, const int64_t *info, int64_t ma
                          const int32_t *gt_class, int32_t n_gt, double det_dist_thresh, int32_t *detected, int32_t *match,
                          int32_t *gt_match, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- exploration map */
+
+/* The occupancy side of scripts/eval/frontier_baseline.py, the paper's comparison policy: every pixel of a depth image is ray-cast
+ * through a voxel grid (:170), the top-down view of the grid (:188) gives frontier cells (:52-67), those are clustered and the member
+ * nearest to the current pose of each cluster is a goal (:191-214).  The same map gives explored volume per planning step.
+ *
+ * The map is a caller-owned, persistent bit grid uint32 bits[2][wpp]: plane 0 is "a ray passed through", plane 1 is "a ray ended
+ * here".  Voxel indexing (lin = (x * res_y + y) * res_z + z, bit (lin & 31) of word plane * wpp + (lin >> 5)), wpp rounded up to an
+ * even number, the tail bits (never set, masked by every reader) and the limits on the geometry are the semantic object map's, above.
+ * mnf_explore_map_bytes returns 2 * wpp * 4, or 0 for a geometry that is refused.  Clearing the map is a memset to 0.  A voxel reads
+ * as OCCUPIED if its plane-1 bit is set, else FREE if its plane-0 bit is set, else UNKNOWN.
+ *
+ * mnf_explore_map_insert (VoxelGrid is not part of the reference tree, so the ray-cast is defined here).  origins, viewdirs [N,3] f32,
+ * depth [N] f32 (the distance along the ray), acc [N] f32 or NULL.  One launch, no host synchronisation; n_rays == 0 returns MNF_OK.
+ * Per pixel, in float32, each operation rounded separately (g = grid_min, three host floats; inv = 1.0f / voxel_size):
+ *   1. The pixel is skipped when depth is NaN, when depth <= min_depth (Habitat writes 0 for no data), when acc is given and
+ *      acc < min_acc, or when a component of o or d is not finite.
+ *   2. hit = depth is finite && depth <= max_range; t = hit ? depth : max_range.  (+inf, or a depth beyond the range, carves free space
+ *      out to max_range and marks nothing occupied.)
+ *   3. Per axis k: a_k = floor((o_k - g_k) * inv), p_k = o_k + t * d_k, b_k = floor((p_k - g_k) * inv).  The pixel is skipped when
+ *      some |a_k| or |b_k| is >= 2^24.  n_k = |b_k - a_k|, s_k = sign(b_k - a_k).
+ *   4. For the axes with n_k > 0 (so d_k != 0): edge_k = (float)(a_k + (s_k > 0 ? 1 : 0)) * voxel_size,
+ *      tm_k = ((g_k + edge_k) - o_k) / d_k, td_k = voxel_size / |d_k|.
+ *   5. The walk takes exactly n_x + n_y + n_z steps from voxel a.  Each step: the candidate is the first axis in x, y, z order with
+ *      n_k > 0; a later axis with n_k > 0 replaces it only if its tm is STRICTLY smaller.  The chosen axis moves by s_k, n_k -= 1,
+ *      tm_k = tm_k + td_k.  The walk therefore ends in voxel b whatever the rounding.
+ *   6. Every visited voxel but the last gets the free bit; the last, b, gets the occupied bit if hit, else the free bit.  Only voxels
+ *      inside the grid are written (a plain load first, a 32-bit atomic OR only where a bit is clear); voxels outside are walked or,
+ *      once the ray has left the box for good, skipped.  Only the resulting bits are specified.
+ * Inserts accumulate, and the bits do not depend on the order or the grouping of the pixels.  stats, when non-NULL, is int64 [2] on the
+ * device to which the call ADDS {voxel steps walked, atomic ORs issued} (a measurement aid; the second depends on the schedule).
+ * With the same grid, max_depth = max_range and labels all >= first_class, plane 1 equals the OR over the classes of a semantic object
+ * map given the same pixels.
+ *
+ * Read-outs (device outputs, integer sums):
+ * mnf_explore_map_count writes counts [3] int64 = {free, occupied, unknown} voxels.
+ * mnf_explore_map_topdown writes map [X][Z] int8 over the layers y_lo <= y < y_hi (0 <= y_lo <= y_hi <= res_y): 1 if a voxel of the
+ * column slab is occupied, else 0 if one is free, else -1: the grid frontier_baseline.py:188 reads.
+ * mnf_explore_map_frontiers replaces find_frontiers on such a map [X][Z] (any int8 map of -1 / 0 / 1).  A cell of value 0 is a
+ * frontier cell when an in-bounds cell of its 3 x 3 neighbourhood is -1.  The reference's `break` leaves only the inner loop, so it
+ * appends a cell once per dx in {-1, 0, 1} whose column x + dx holds an unknown neighbour: each frontier cell carries that
+ * MULTIPLICITY, 1 .. 3.  cells [max_frontiers,2] int32 (x, z) in ascending x * Z + z, mult [max_frontiers] int32, info [2] int64 =
+ * {frontier cells, frontier cells > max_frontiers}; the first max_frontiers are written, nothing past the capacity.
+ * mnf_explore_map_frontier_clusters replaces DBSCAN(eps=1, min_samples=3) and the nearest member per cluster on the first
+ * min(frontier_info[0], max_frontiers) cells of such a list (frontier_info is read on the device: no host copy in between).  Two
+ * cells are linked when their INTEGER offset has dx^2 + dz^2 <= eps2 (1 .. 8); a cell's neighbourhood is itself plus the cells linked
+ * to it; a cell is CORE when the multiplicities of its neighbourhood sum to >= min_samples (weighted == 0: every multiplicity counts
+ * 1); the clusters are the connected components of the core cells, numbered by their smallest row-major core cell; a non-core cell
+ * with a core neighbour takes the SMALLEST label among those neighbours; every other cell is -1.  This is what scikit-learn's DBSCAN
+ * gives on the duplicated list, and with sample_weight = mult, numbering included.  The goal of a cluster is its member cell (core or
+ * not) with the smallest dx * dx + dz * dz, dx = (double)x - current_x, dz = (double)z - current_z in float64 in that order; of
+ * equal distances the lowest row-major cell wins.  labels [max_frontiers] int32 (the true number, also where it is >=
+ * max_clusters), goals [max_clusters,2] int32 and sizes [max_clusters] int32 (member cells; 0 beyond the clusters found), info [2]
+ * int64 = {clusters, clusters > max_clusters}.  workspace: mnf_explore_map_frontier_clusters_workspace_bytes(X, Z, max_frontiers,
+ * max_clusters) bytes (0 for bad arguments), 8-byte aligned.
+ *
+ * Argument errors (a null required pointer, a non-positive resolution or voxel_size, max_range not finite or <= 0,
+ * max_range / voxel_size > 2^20, layers outside the grid, eps2 outside 1 .. 8, min_samples < 1, a negative capacity, a current that is
+ * not finite, a misaligned workspace or one that is too small) return MNF_ERR_INVALID before any HIP call.  Profile labels:
+ * "explore_map_insert", "explore_map_count", "explore_map_topdown", "explore_map_frontiers", "explore_map_frontier_clusters".  Every
+ * call enqueues on `stream` and none synchronises. */
+int64_t mnf_explore_map_bytes(int32_t res_x, int32_t res_y, int32_t res_z);
+int mnf_explore_map_insert(uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, const float *grid_min_host, float voxel_size,
+                           float max_range, const float *origins, const float *viewdirs, const float *depth, const float *acc,
+                           int64_t n_rays, float min_depth, float min_acc, int64_t *stats, mnf_stream_t stream);
+int mnf_explore_map_count(const uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, int64_t *counts, mnf_stream_t stream);
+int mnf_explore_map_topdown(const uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, int32_t y_lo, int32_t y_hi, int8_t *map,
+                            mnf_stream_t stream);
+int mnf_explore_map_frontiers(const int8_t *map, int32_t res_x, int32_t res_z, int64_t max_frontiers, int32_t *cells, int32_t *mult,
+                              int64_t *info, mnf_stream_t stream);
+int64_t mnf_explore_map_frontier_clusters_workspace_bytes(int32_t res_x, int32_t res_z, int64_t max_frontiers, int64_t max_clusters);
+int mnf_explore_map_frontier_clusters(const int32_t *cells, const int32_t *mult, const int64_t *frontier_info, int64_t max_frontiers,
+                                      int32_t res_x, int32_t res_z, int32_t eps2, int32_t min_samples, int32_t weighted,
+                                      double current_x, double current_z, int64_t max_clusters, int32_t *labels, int32_t *goals,
+                                      int32_t *sizes, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,406 @@
+"""GPU tests of the exploration map (csrc/explore.hip, apnrf_amd/explore.py) against the numpy restatement tests/explore_ref.py, which
+tests/test_explore_cpu.py holds to the definition, to hand-worked maps and to scikit-learn's DBSCAN.  Every comparison is `array_equal`:
+bit-grid bytes and integers."""
+import numpy as np
+import pytest
+import torch
+
+import helpers as H
+import explore_ref as ER
+from explore_ref import G_MIN, G_VS, MAX_RANGE, MIN_ACC, MIN_DEPTH, RES_A, RES_B, STATES
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+CANARY = 64
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def _new_map(res, max_range=MAX_RANGE):
+    from apnrf_amd.explore import ExplorationMap
+    aabb = list(G_MIN) + [G_MIN[k] + res[k] * G_VS for k in range(3)]
+    m = ExplorationMap(aabb, voxel_size=G_VS, max_range=max_range, device=DEV)
+    assert m.resolution == tuple(res) and m.words_per_plane == ER.words_per_plane(res) and tuple(m.bits.shape) == (2, m.words_per_plane)
+    return m
+
+
+def _gpu_insert(m, case, sl=slice(None), with_acc=True, stats=None):
+    m.insert(_dev(case["o"][sl]), _dev(case["d"][sl]), _dev(case["depth"][sl]), acc=_dev(case["acc"][sl]) if with_acc else None, min_depth=MIN_DEPTH,
+             min_acc=MIN_ACC if with_acc else 0.0, stats=stats)
+
+
+_CASES = {}
+
+
+def seeded(res, N):
+    """The seeded rays of (res, N) and the restatement's map of them: computed once, shared, never changed."""
+    if (res, N) not in _CASES:
+        case = ER.seeded_rays(res, N, seed=N + res[0])
+        steps = []
+        want = ER.insert(ER.new_bits(res), case["o"], case["d"], case["depth"], G_MIN, G_VS, res, MAX_RANGE, acc=case["acc"], min_depth=MIN_DEPTH,
+                         min_acc=MIN_ACC, stats=steps)
+        want.setflags(write=False)
+        _CASES[(res, N)] = (case, want, steps[0])
+    return _CASES[(res, N)]
+
+
+# ------------------------------------------------------------------ insert
+@pytest.mark.parametrize("N", [1000, 4097])
+@pytest.mark.parametrize("res", [RES_A, RES_B])
+def test_insert_bit_for_bit(res, N):
+    case, want, steps = seeded(res, N)
+    m = _new_map(res)
+    stats = torch.zeros(2, dtype=torch.int64, device=DEV)
+    _gpu_insert(m, case, stats=stats)
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    c = ER.counts(want, res)
+    assert c[0] > 50 and c[1] > 50 and c.sum() == np.prod(res)                                   # free and occupied voxels both occur
+    got = m.counts()
+    assert [got["free"], got["occupied"], got["unknown"]] == c.tolist()
+    assert got["explored_volume"] == float(c[0] + c[1]) * float(np.float32(G_VS)) ** 3
+    n_vox = int(np.prod(res))
+    tail = np.arange(want.shape[1] * 32) >= n_vox
+    assert not ((want[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(2, -1)[:, tail].any()     # the tail bits stay clear
+    walked, ors = stats.tolist()
+    assert walked == steps                                                                       # the kernel walks what the restatement walks
+    assert 0 < ors <= walked + N                                                                 # at most one OR per visited voxel
+
+
+def test_insert_without_acc_and_of_nothing():
+    case, _, _ = seeded(RES_B, 1000)
+    m = _new_map(RES_B)
+    _gpu_insert(m, case, with_acc=False)
+    want = ER.ref_insert(case, RES_B, with_acc=False)
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    assert (want != seeded(RES_B, 1000)[1]).any()                                                # acc mattered in the other test
+    empty = torch.empty(0, 3, device=DEV)
+    m.insert(empty, empty, torch.empty(0, device=DEV))                                           # N = 0: nothing changes
+    m.insert(empty, empty, torch.empty(0, device=DEV), acc=torch.empty(0, device=DEV))
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    m.clear()
+    assert not _u32(m.bits).any()
+
+
+def test_special_depths():
+    """One ray along +x through the middle of the grid per depth: NaN, 0, negative and -inf insert nothing; +inf and a depth beyond max_range carve
+    free space to max_range and mark nothing occupied; a depth in range ends occupied."""
+    res = RES_A
+    lo = np.array(G_MIN, np.float32)
+    o = (lo + (np.array([1, 4, 8], np.float32) + np.float32(0.5)) * np.float32(G_VS))[None]
+    d = np.array([[1.0, 0.0, 0.0]], np.float32)
+    for depth, free_x, occ_x in [(np.nan, [], []), (0.0, [], []), (-1.0, [], []), (-np.inf, [], []), (np.inf, list(range(1, 12)), []),
+                                 (3.0, list(range(1, 12)), []), (MAX_RANGE, list(range(1, 11)), [11]), (1.0, list(range(1, 5)), [5])]:
+        m = _new_map(res)
+        m.insert(_dev(o), _dev(d), _dev(np.array([depth], np.float32)))
+        want = ER.insert(ER.new_bits(res), o, d, [depth], G_MIN, G_VS, res, MAX_RANGE)
+        np.testing.assert_array_equal(_u32(m.bits), want, err_msg=str(depth))
+        st = ER.voxel_states(want, res)
+        assert np.nonzero(st[:, 4, 8] == 0)[0].tolist() == free_x and np.nonzero(st[:, 4, 8] == 1)[0].tolist() == occ_x, depth
+        assert (st != -1).sum() == len(free_x) + len(occ_x)
+
+
+def test_accumulation_and_order():
+    case, want, _ = seeded(RES_A, 4097)
+    m = _new_map(RES_A)
+    _gpu_insert(m, case)
+    _gpu_insert(m, case)                                                                         # twice: the same bits as once
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    halves = _new_map(RES_A)
+    _gpu_insert(halves, case, slice(0, 2048))
+    first = _u32(halves.bits).copy()
+    _gpu_insert(halves, case, slice(2048, 4097))
+    np.testing.assert_array_equal(_u32(halves.bits), want)
+    assert (first != want).any()                                                                 # the second half added something
+    perm = np.random.default_rng(3).permutation(4097)
+    shuffled = _new_map(RES_A)
+    _gpu_insert(shuffled, {k: v[perm] for k, v in case.items()})
+    np.testing.assert_array_equal(_u32(shuffled.bits), want)
+
+
+@pytest.mark.parametrize("res,N", [(RES_A, 4097), (RES_B, 1000)])
+def test_plane_1_is_the_class_or_of_the_object_map(res, N):
+    from apnrf_amd.objects import SemanticObjectMap
+    case, want, _ = seeded(res, N)
+    aabb = list(G_MIN) + [G_MIN[k] + res[k] * G_VS for k in range(3)]
+    om = SemanticObjectMap(aabb, voxel_size=G_VS, num_classes=4, first_class=1, device=DEV)
+    labels = (1 + np.arange(N) % 3).astype(np.uint8)                                             # all >= first_class
+    om.insert(_dev(case["o"]), _dev(case["d"]), _dev(case["depth"]), labels=_dev(labels), acc=_dev(case["acc"]), min_depth=MIN_DEPTH, max_depth=MAX_RANGE,
+              min_acc=MIN_ACC)
+    m = _new_map(res)
+    _gpu_insert(m, case)
+    class_or = np.bitwise_or.reduce(_u32(om.bits), axis=0)
+    np.testing.assert_array_equal(_u32(m.bits)[1], class_or)
+    np.testing.assert_array_equal(want[1], class_or)
+    assert class_or.any()
+
+
+# ------------------------------------------------------------------ read-outs
+def _upload(m, bits):
+    m.bits.copy_(_dev(bits.view(np.int32)))
+
+
+def _ref_goals(bits, m, current_world, y_lo=None, y_hi=None, **kw):
+    res = m.resolution
+    td = ER.top_down(bits, res, 0 if y_lo is None else y_lo, y_hi)
+    cells, mult, _ = ER.frontiers(td)
+    fc = ER.frontier_clusters(cells, mult, m.cell_of(current_world), **kw)
+    world = m.grid_min.astype(np.float64)[[0, 2]][None] + (fc["goals"].astype(np.float64) + 0.5) * float(m.voxel_size)
+    return td, cells, mult, fc, world
+
+
+def _assert_read_outs(m, bits, what):
+    res = m.resolution
+    c = ER.counts(bits, res)
+    np.testing.assert_array_equal(m.counts_device().cpu().numpy(), c, err_msg=what)
+    for y_lo, y_hi in [(None, None), (2, res[1] - 1), (1, 2), (3, 3)]:
+        td = ER.top_down(bits, res, 0 if y_lo is None else y_lo, y_hi)
+        np.testing.assert_array_equal(m.top_down(y_lo, y_hi).cpu().numpy(), td, err_msg=f"{what} layers {y_lo}:{y_hi}")
+        cells, mult, _ = ER.frontiers(td)
+        got = m.frontiers(y_lo, y_hi)
+        np.testing.assert_array_equal(got["cells"], cells, err_msg=what)
+        np.testing.assert_array_equal(got["mult"], mult, err_msg=what)
+        assert got["cells"].dtype == np.int32 and got["mult"].dtype == np.int32
+    found = 0
+    current = (G_MIN[0] + 1.3, G_MIN[2] + 2.1)
+    for kw in [dict(), dict(weighted=False), dict(eps2=2, min_samples=4), dict(eps2=4, min_samples=6, weighted=False), dict(eps2=8, min_samples=2),
+               dict(y_lo=2, y_hi=res[1] - 1)]:
+        _, cells, mult, fc, world = _ref_goals(bits, m, current, **kw)
+        got = m.frontier_goals(current, **kw)
+        np.testing.assert_array_equal(got["cells"], cells, err_msg=f"{what} {kw}")
+        np.testing.assert_array_equal(got["mult"], mult, err_msg=f"{what} {kw}")
+        np.testing.assert_array_equal(got["labels"], fc["labels"], err_msg=f"{what} {kw}")
+        np.testing.assert_array_equal(got["goal_cells"], fc["goals"], err_msg=f"{what} {kw}")
+        np.testing.assert_array_equal(got["sizes"], fc["sizes"], err_msg=f"{what} {kw}")
+        np.testing.assert_array_equal(got["goals"].view(np.int64), world.view(np.int64), err_msg=f"{what} {kw}")
+        found += int(fc["info"][0])
+    return c, found
+
+
+@pytest.mark.parametrize("res,N", [(RES_A, 1000), (RES_B, 1000)])
+def test_read_outs_of_an_inserted_map(res, N):
+    case, want, _ = seeded(res, N)
+    m = _new_map(res)
+    _gpu_insert(m, case)
+    c, found = _assert_read_outs(m, want, f"inserted {res}")
+    assert (found > 0) == (res == RES_A)                                                         # the small grid has no wholly unseen column left
+
+
+@pytest.mark.parametrize("name", list(STATES))
+def test_read_outs_of_an_uploaded_map(name):
+    st = STATES[name]()
+    res = st.shape
+    bits = ER.states_to_bits(st)
+    np.testing.assert_array_equal(ER.voxel_states(bits, res), np.minimum(st, 1))
+    dirty = bits.copy()
+    n_vox = int(np.prod(res))
+    if n_vox % 32:
+        dirty[:, n_vox // 32] |= np.uint32((0xFFFFFFFF << (n_vox % 32)) & 0xFFFFFFFF)             # a caller that filled the tail: readers mask it
+    dirty[:, (n_vox + 31) // 32:] = 0xFFFFFFFF
+    m = _new_map(res)
+    _upload(m, dirty)
+    c, found = _assert_read_outs(m, bits, name)
+    if name == "unknown":
+        assert c.tolist() == [0, 0, n_vox] and found == 0 and m.frontiers()["cells"].shape == (0, 2)
+    if name == "free":
+        assert c.tolist() == [n_vox, 0, 0] and found == 0 and m.frontiers()["cells"].shape == (0, 2)          # no frontier at all
+    if name in ("room", "sparse", "small"):
+        assert found > 0
+    if name == "dense":
+        assert found == 0 and c[2] > 0                                                           # unknown voxels, but no wholly unknown column
+    if name == "room":
+        got = m.frontier_goals((G_MIN[0] + 1.3, G_MIN[2] + 2.1), weighted=False)
+        assert (got["labels"] == -1).any() and (got["labels"] >= 0).any() and (got["mult"] == 3).any() and (got["mult"] == 1).any()
+
+
+# ------------------------------------------------------------------ capacities, through the C ABI with guards around every output
+def gpu_frontiers(grid, max_frontiers):
+    from apnrf_amd import _lib as L
+    X, Z = grid.shape
+    mf = max_frontiers
+    d_grid = _dev(grid.astype(np.int8))
+    out = dict(cells=torch.full((2 * mf + CANARY,), -777, dtype=torch.int32, device=DEV), mult=torch.full((mf + CANARY,), -777, dtype=torch.int32, device=DEV),
+               info=torch.full((2 + CANARY,), -777, dtype=torch.int64, device=DEV))
+    L.launch(L.load_library().mnf_explore_map_frontiers, L.ptr(d_grid), X, Z, mf, L.ptr(out["cells"]), L.ptr(out["mult"]), L.ptr(out["info"]))
+    torch.cuda.synchronize()
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    for k, n in dict(cells=2 * mf, mult=mf, info=2).items():
+        assert (host[k][n:] == -777).all(), f"{k}: written past its capacity"
+        host[k] = host[k][:n]
+    host["cells"] = host["cells"].reshape(mf, 2)
+    host["raw"] = out
+    return host
+
+
+def gpu_clusters(fr, shape, current, max_clusters, eps2=1, min_samples=3, weighted=True, exact_ws=False):
+    """mnf_explore_map_frontier_clusters on the device outputs of `gpu_frontiers`."""
+    from apnrf_amd import _lib as L
+    lib = L.load_library()
+    X, Z = shape
+    mf, mc = fr["mult"].shape[0], max_clusters
+    out = dict(labels=torch.full((mf + CANARY,), -777, dtype=torch.int32, device=DEV), goals=torch.full((2 * mc + CANARY,), -777, dtype=torch.int32, device=DEV),
+               sizes=torch.full((mc + CANARY,), -777, dtype=torch.int32, device=DEV), info=torch.full((2 + CANARY,), -777, dtype=torch.int64, device=DEV))
+    nbytes = int(lib.mnf_explore_map_frontier_clusters_workspace_bytes(X, Z, mf, mc))
+    assert nbytes > 0 and nbytes % 8 == 0
+    ws = torch.full((nbytes + (0 if exact_ws else 8 * CANARY),), 0xA5, dtype=torch.uint8, device=DEV)
+    raw = fr["raw"]
+    L.launch(lib.mnf_explore_map_frontier_clusters, L.ptr(raw["cells"]), L.ptr(raw["mult"]), L.ptr(raw["info"]), mf, X, Z, eps2, min_samples, int(weighted),
+             float(current[0]), float(current[1]), mc, L.ptr(out["labels"]), L.ptr(out["goals"]), L.ptr(out["sizes"]), L.ptr(out["info"]), L.ptr(ws), nbytes)
+    torch.cuda.synchronize()
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    for k, n in dict(labels=mf, goals=2 * mc, sizes=mc, info=2).items():
+        assert (host[k][n:] == -777).all(), f"{k}: written past its capacity"
+        host[k] = host[k][:n]
+    if not exact_ws:
+        assert (ws[nbytes:].cpu().numpy() == 0xA5).all(), "written past the workspace"
+    host["goals"] = host["goals"].reshape(mc, 2)
+    return host
+
+
+def _assert_capacity_case(grid, mf, mc, current=(3.0, 4.5), **kw):
+    cells, mult, finfo = ER.frontiers(grid, max_frontiers=mf)
+    fr = gpu_frontiers(grid, mf)
+    n = cells.shape[0]
+    np.testing.assert_array_equal(fr["info"], finfo)
+    np.testing.assert_array_equal(fr["cells"][:n], cells)
+    np.testing.assert_array_equal(fr["mult"][:n], mult)
+    assert (fr["cells"][n:] == -777).all() and (fr["mult"][n:] == -777).all()                    # spare capacity stays untouched
+    ref = ER.frontier_clusters(cells, mult, current, max_clusters=mc, **kw)                      # of the cells that were listed
+    for exact_ws in (False, True):
+        got = gpu_clusters(fr, grid.shape, current, mc, exact_ws=exact_ws, **kw)
+        np.testing.assert_array_equal(got["info"], ref["info"])
+        np.testing.assert_array_equal(got["labels"][:n], ref["labels"])                          # true numbers, also beyond the capacity
+        assert (got["labels"][n:] == -777).all()
+        k = ref["goals"].shape[0]
+        np.testing.assert_array_equal(got["goals"][:k], ref["goals"])
+        np.testing.assert_array_equal(got["sizes"][:k], ref["sizes"])
+        assert (got["goals"][k:] == -777).all() and (got["sizes"][k:] == 0).all()
+    return finfo, ref["info"]
+
+
+def test_capacities_hit_exactly_and_exceeded():
+    grid = ER.seeded_map2d(7, (12, 14))
+    F = int(ER.frontiers(grid)[2][0])
+    K = int(ER.frontier_clusters(*ER.frontiers(grid)[:2], (3.0, 4.5))["info"][0])
+    assert F > 20 and K > 2
+    finfo, cinfo = _assert_capacity_case(grid, F, K)                                             # hit exactly
+    assert finfo.tolist() == [F, 0] and cinfo.tolist() == [K, 0]
+    finfo, cinfo = _assert_capacity_case(grid, F + 9, K + 5)                                     # spare
+    assert finfo.tolist() == [F, 0] and cinfo.tolist() == [K, 0]
+    finfo, cinfo = _assert_capacity_case(grid, F, K - 1)                                         # one cluster too many
+    assert finfo.tolist() == [F, 0] and cinfo.tolist() == [K, 1]
+    finfo, cinfo = _assert_capacity_case(grid, F, 0)
+    assert cinfo.tolist() == [K, 1]
+    finfo, cinfo = _assert_capacity_case(grid, F - 1, K)                                         # one frontier cell too many
+    assert finfo.tolist() == [F, 1]
+    finfo, cinfo = _assert_capacity_case(grid, F // 2, K)
+    assert finfo.tolist() == [F, 1]
+    finfo, cinfo = _assert_capacity_case(grid, 0, 0)
+    assert finfo.tolist() == [F, 1] and cinfo.tolist() == [0, 0]
+
+
+@pytest.mark.parametrize("shape", [(40, 33), (1, 1), (1, 70), (70, 1), (33, 32)])
+def test_frontiers_across_batches_and_shapes(shape):
+    """40 x 33 = 1320 cells: more than one batch of the ordered compaction; degenerate maps; and every eps2."""
+    grid = ER.seeded_map2d(99, shape, (0.2, 0.6, 0.2))
+    F = int(ER.frontiers(grid)[2][0])
+    for eps2 in range(1, 9):
+        _assert_capacity_case(grid, F + 3, F + 3, current=(shape[0] / 3.0, shape[1] / 2.0), eps2=eps2, min_samples=3 + eps2 // 2, weighted=bool(eps2 % 2))
+    if shape == (40, 33):
+        assert F > 200
+
+
+def test_border_cell_and_goal_ties_on_the_device():
+    grid = np.ones((5, 7), np.int8)                                                              # the cells are given directly: the map only sizes the index
+    fr = gpu_frontiers(grid, len(ER.BORDER_CELLS))
+    assert fr["info"].tolist() == [0, 0]
+    raw = fr["raw"]
+    raw["cells"][:2 * len(ER.BORDER_CELLS)] = _dev(ER.BORDER_CELLS.reshape(-1))
+    raw["mult"][:len(ER.BORDER_CELLS)] = 1
+    raw["info"][0] = len(ER.BORDER_CELLS)
+    got = gpu_clusters(fr, grid.shape, (2.0, 3.0), 4, eps2=1, min_samples=4, weighted=False)
+    ref = ER.frontier_clusters(ER.BORDER_CELLS, np.ones(9, np.int32), (2.0, 3.0), eps2=1, min_samples=4, weighted=False)
+    assert got["labels"].tolist() == ER.BORDER_LABELS == ref["labels"].tolist()
+    assert got["info"].tolist() == [2, 0] and got["sizes"][:2].tolist() == [5, 4]
+    assert got["goals"][:2].tolist() == [[2, 3], [2, 4]] == ref["goals"].tolist()                # the shared arm is cluster 0's, at distance 0
+    got = gpu_clusters(fr, grid.shape, (1.5, 4.5), 4, eps2=1, min_samples=4, weighted=False)     # (1, 4), (2, 4) and (2, 5) tie at 0.5: the lowest
+    ref = ER.frontier_clusters(ER.BORDER_CELLS, np.ones(9, np.int32), (1.5, 4.5), eps2=1, min_samples=4, weighted=False)
+    assert got["goals"][:2].tolist() == [[2, 3], [1, 4]] == ref["goals"].tolist()
+
+
+# ------------------------------------------------------------------ end to end
+@pytest.fixture(scope="module")
+def scene():
+    return H.make_scene(log2_hashmap_size=15)
+
+
+@pytest.fixture(scope="module")
+def model(scene):
+    return H.hip_field(scene), H.hip_estimator(scene)
+
+
+def test_insert_views_end_to_end(scene, model):
+    """The map of 4 rendered poses (320 x 320 at scale 0.1: 32 x 32 rays each) equals the restatement's insert of the same planes, rendered
+    separately through `render_views` and copied to the host."""
+    from apnrf_amd import render as RD
+    from apnrf_amd.explore import ExplorationMap
+    field, est = model
+    kw = H.RENDER_KW
+    poses = scene["poses"][:4]
+    width = height = 320
+    focal = 0.5 * width / np.tan(np.pi / 4)
+    m = ExplorationMap(scene["aabb"], voxel_size=0.2, max_range=6.0, device=DEV)
+    ins = dict(min_depth=0.05, min_acc=0.5)
+    m.insert_views(field, est, poses, width, height, focal, kw["near_plane"], kw["render_step_size"], 0.1, kw["cone_angle"], kw["alpha_thre"], **ins)
+    o, d, h, w = RD._pose_rays(np.asarray(poses), width, height, focal, 0.1, DEV)
+    assert (h, w) == (32, 32)
+    r = RD.render_views(field, est, o, d, h * w, 1024, near_plane=kw["near_plane"], render_step_size=kw["render_step_size"], render_bkgd=torch.zeros(3),
+                        cone_angle=kw["cone_angle"], alpha_thre=kw["alpha_thre"], image_hw=(h, w), n_split=None)
+    want = ER.insert(ER.new_bits(m.resolution), o.cpu().numpy(), d.cpu().numpy(), r["depth"].cpu().numpy().reshape(-1), m.grid_min, m.voxel_size,
+                     m.resolution, 6.0, acc=r["acc"].cpu().numpy().reshape(-1), **ins)
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    c = ER.counts(want, m.resolution)
+    assert c[0] > 100 and c[1] > 20                                                              # not an empty map
+    got = m.counts()
+    assert [got["free"], got["occupied"], got["unknown"]] == c.tolist()
+    current = (float(poses[0][0]), float(poses[0][2]))
+    _, cells, mult, fc, world = _ref_goals(want, m, current)
+    goals = m.frontier_goals(current)
+    np.testing.assert_array_equal(goals["labels"], fc["labels"])
+    np.testing.assert_array_equal(goals["goal_cells"], fc["goals"])
+    np.testing.assert_array_equal(goals["goals"], world)
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("depth_along", ["z", "ray"])
+def test_insert_dataset_end_to_end(scene, tmp_path, packed, depth_along):
+    from apnrf_amd import render as RD
+    from apnrf_amd.dataset import Dataset
+    from apnrf_amd.explore import ExplorationMap
+    from apnrf_amd.objects import planar_to_ray_scale
+    rng = np.random.default_rng(11)
+    n_img, h, w, C = 3, 24, 20, 29
+    c2w = np.stack([RD.pose_to_c2w(np.asarray(p, np.float64)) for p in scene["poses"][:n_img]]).astype(np.float32)
+    depths = rng.uniform(0.3, 6.0, (n_img, h, w)).astype(np.float32)
+    depths[:, ::5, ::3] = 0.0                                        # Habitat's "no return"
+    sems = rng.integers(0, C, (n_img, h, w)).astype(np.int64)
+    ds = Dataset(training=False, save_fp=str(tmp_path / "ds"), device=DEV, packed=packed)
+    ds.update_data(rng.integers(0, 256, (n_img, h, w, 3), dtype=np.uint8), depths, sems, c2w)
+    ids = [2, 0]
+    m = ExplorationMap(scene["aabb"], voxel_size=0.2, max_range=4.0, device=DEV)
+    m.insert_dataset(ds, ids, depth_along=depth_along)
+    rays = RD.generate_image_rays(c2w[ids], w, h, ds.K, DEV)
+    stored = ds.depths[ids].to(torch.float32).cpu().numpy().reshape(len(ids), -1)                # what the storage holds (fp16-rounded when packed)
+    if depth_along == "z":
+        stored = stored * planar_to_ray_scale(w, h, float(ds.K[0, 0]), DEV).cpu().numpy()[None]  # one float32 multiplication, as torch does it
+    want = ER.insert(ER.new_bits(m.resolution), rays.origins.cpu().numpy(), rays.viewdirs.cpu().numpy(), stored.reshape(-1), m.grid_min, m.voxel_size,
+                     m.resolution, 4.0)
+    np.testing.assert_array_equal(_u32(m.bits), want)
+    c = ER.counts(want, m.resolution)
+    assert c[0] > 500 and c[1] > 100 and (stored > 4.0).any()                                    # hits, and misses that only carve
+    np.testing.assert_array_equal(m.counts_device().cpu().numpy(), c)

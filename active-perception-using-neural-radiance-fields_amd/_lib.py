@@ -206,6 +206,9 @@ SIGNATURES = {
     "mnf_explore_map_frontier_clusters_workspace_bytes": (c_int64, [c_int32, c_int32, c_int64, c_int64]),
     "mnf_explore_map_frontier_clusters": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_double,
                                                     c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_path_field_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "mnf_path_field": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mnf_path_trace": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -46,6 +46,7 @@ SOURCES = {
     "ssim.hip": ["-ffp-contract=off"],      # 2 (m m) and m m + m m stay the same double: SSIM(x, x) is exactly 1
     "objmap.hip": ["-ffp-contract=off"],    # voxel indices and centroids are chains of separately rounded operations (numpy restates them)
     "explore.hip": ["-ffp-contract=off"],   # the voxel walk is a chain of separately rounded float32 operations (numpy restates it)
+    "planning.hip": [],                     # integer labels only: no floating-point work
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
     "inputgrad.hip@bf16": ["-DMNF_BF16"],

@@ -177,6 +177,31 @@ class ExplorationMap:
         return {"cells": f["cells"][:n].cpu().numpy(), "mult": f["mult"][:n].cpu().numpy(), "labels": labels[:n].cpu().numpy(),
                 "goal_cells": goal_cells, "goals": world, "sizes": sizes[:k].cpu().numpy()}
 
+    @torch.no_grad()
+    def goal_paths(self, current_world_xz, goal_cells, y_lo=None, y_hi=None, unknown_blocked=True):
+        """The way to each of `goal_cells` [K,2] (x, z), e.g. `frontier_goals`' "goal_cells", over `top_down(y_lo, y_hi)`: occupied cells
+        are blocked, unknown cells too when `unknown_blocked`; moves and costs are the planner's (apnrf_amd.planning).  The source is the
+        cell floor(cell_of(current) + 0.5).  One shortest-path field, one trace.  -> `lengths_m` float64 [K] = (a + b sqrt(2)) *
+        voxel_size, inf where a goal cannot be reached; `paths` int32 [total,2] cells, goal first, packed at `offsets` int64 [K+1]
+        (host arrays).  The frontier baseline can order its goals by the way to them instead of the straight line."""
+        from . import planning as PL
+        grid = self.top_down(y_lo, y_hi)
+        blocked = ((grid == 1) | (grid == -1)) if unknown_blocked else (grid == 1)
+        cur = np.floor(self.cell_of(current_world_xz) + 0.5)
+        big = float(1 << 30)
+        source = torch.tensor([[int(min(max(cur[0], -1.0), big)), int(min(max(cur[1], -1.0), big))]], dtype=torch.int32, device=self.device)
+        out = PL.path_field(blocked.to(torch.int32), source)
+        PL.check_info(out["info"])
+        cells = np.asarray(goal_cells, np.int64).reshape(-1, 2)
+        goals = torch.from_numpy(np.concatenate([np.zeros((cells.shape[0], 1), np.int64), cells], axis=1).astype(np.int32)).to(self.device)
+        t = PL.trace_paths(out["field"], goals)
+        X, _, Z = self.resolution
+        gx, gz = goals[:, 1].long(), goals[:, 2].long()
+        inside = (gx >= 0) & (gx < X) & (gz >= 0) & (gz < Z)
+        cost = PL.field_costs(out["field"][0])[gx.clamp(0, X - 1), gz.clamp(0, Z - 1)]
+        cost = torch.where(inside, cost, torch.full_like(cost, float("inf")))
+        return {"lengths_m": cost.cpu().numpy() * float(self.voxel_size), "paths": t["paths"].cpu().numpy(), "offsets": t["offsets"].cpu().numpy()}
+
 
 def next_goal(goals, goal_cells, current_world_xz, visited):
     """The host glue of frontier_baseline.py:210-223 on the tiny goal arrays: drop the goals whose cell is in `visited` (a list of

@@ -933,6 +933,58 @@ int mnf_explore_map_frontier_clusters(const int32_t *cells, const int32_t *mult,
                                       double current_x, double current_z, int64_t max_clusters, int32_t *labels, int32_t *goals,
                                       int32_t *sizes, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- planner grid search */
+
+/* The first step of the planner, Dijkstra(aabb, path_finding_map, voxel_grid_size, 0.05).planning(...) of planning/dijkstra.py:72-182, which
+ * sample_traj calls once per sampled goal (planning/planning_funcs.py:288-326), as a single-source shortest-path FIELD over the map and
+ * paths read back out of it: one field per start cell answers every goal from that start: reached or not, at what cost, along which cells.
+ *
+ * The grid and the moves.  A map is blocked [nx][ny] int32, non-zero = obstacle, indexed [x][y] as verify_node indexes
+ * obstacle_map[node.x][node.y] (dijkstra.py:194-215): mnf_planner_map's output as it stands.  A move goes to one of the 8 neighbours,
+ * straight cost 1, diagonal cost sqrt(2) (dijkstra.py:247-260).  A move is legal when the cell moved TO lies in [0, lim_x) x [0, lim_y)
+ * and is not blocked; nothing else is checked: a diagonal move between two obstacles that touch at a corner is legal, as in the
+ * reference.  The source has cost 0 whether or not it is blocked or within the limits: the reference never verifies its start node.
+ * lim_x <= nx and lim_y <= ny stand for the reference's `px >= self.max_x` / `py >= self.max_y` tests.
+ *
+ * Costs are exact integers, not accumulated floats.  A way of a straight and b diagonal moves costs a + b sqrt(2); two different pairs
+ * never cost the same (sqrt(2) is irrational), so the cheapest (a, b) of a cell is unique.  A cell's LABEL is the uint32 (a << 16) | b;
+ * 0xFFFFFFFF = not reached: blocked cells, cells beyond the limits, cells cut off, and the whole field of a source outside
+ * [0, nx) x [0, ny).  Labels are ordered by the exact sign of da + db sqrt(2): where the signs of da and db agree, that sign; otherwise
+ * da^2 against 2 db^2 in integers.  (A float64 a + b sqrt(2) formed freshly from the two integers orders them the same way: its rounding
+ * error is below 2^-36 for a, b < 2^16 and distinct costs are more than 2^-18 apart.)  No cost is built by adding move after move.
+ *
+ * Size cap: (nx + 2)(ny + 2) <= 40 000, so that a field with a one-cell border, 160 000 B, fits the LDS of one CU and
+ * a + b <= nx ny - 1 < 2^16: up to 198 x 198.  Larger maps are refused; there is no second route through global memory.
+ *
+ * mnf_path_field_bytes returns nx * ny * n_sources * 4, the bytes of `field`, or 0 for a geometry that is refused or n_sources < 0.
+ * mnf_path_field: blocked [n_maps][nx][ny] with n_maps == 1 (one map for every source) or n_maps == n_sources (a map per source); sources
+ * [n_sources][2] int32 (x, y) on the device; field [n_sources][nx][ny] uint32; info [n_sources][2] int64 = {reached cells (the source
+ * included), sweeps run}.  One workgroup per source relaxes the labels in LDS, sweep after sweep, until a sweep changes nothing; the
+ * fixpoint is unique, so the field does not depend on the schedule.  A fixpoint needs at most nx ny sweeps; the kernel stops after that
+ * many whatever happens and then writes info[b][0] = -1 (a logic error: the field of that source is not to be used).  n_sources == 0 is a
+ * legal no-op.
+ *
+ * The path of a goal is fixed by the field alone (no parent array, no race).  From a reached cell c with label (a, b) step to c - m for
+ * the FIRST move m in the reference's motion order (1,0), (0,1), (-1,0), (0,-1), (-1,-1), (-1,1), (1,-1), (1,1) for which c - m lies
+ * inside the map and carries exactly the label (a - 1, b) for a straight m, (a, b - 1) for a diagonal m; repeat until label 0.  The path
+ * lists the cells goal first, source last, a + b + 1 of them, as calc_final_path lists them (dijkstra.py:170-182).  It is A shortest
+ * path, of the reference's cost and make-up; of several equal ones the reference returns the one the insertion order of its Python dict
+ * leads to, which need not be this one.
+ * mnf_path_trace: field [n_fields][nx][ny]; goals [n_goals][3] int32 = {field index, x, y}; offsets [n_goals + 1] int64 into paths
+ * [total][2] int32 (x, y), which the caller sizes; info [2] int64 = {goals whose path was written, goals whose slot did not fit}.  One
+ * lane per goal.  The length of a goal is a + b + 1, or 0 when it is not reached, lies outside the map or names no field.  A goal whose
+ * slot offsets[g + 1] - offsets[g] differs from its length gets nothing written and counts in info[1]; a goal of length 0 that fits
+ * counts in neither.
+ *
+ * Argument errors (a null required pointer, a size that is not positive or beyond the cap, limits outside [0, nx] x [0, ny], n_maps
+ * other than 1 or n_sources, a negative count, a misaligned info or offsets) return MNF_ERR_INVALID before any HIP call.  Profile
+ * labels: "path_field", "path_trace".  Both calls enqueue on `stream` and neither synchronises. */
+int64_t mnf_path_field_bytes(int32_t nx, int32_t ny, int32_t n_sources);
+int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx, int32_t ny, int32_t lim_x, int32_t lim_y, const int32_t *sources,
+                   int32_t n_sources, uint32_t *field, int64_t *info, mnf_stream_t stream);
+int mnf_path_trace(const uint32_t *field, int32_t n_fields, int32_t nx, int32_t ny, const int32_t *goals, const int64_t *offsets,
+                   int64_t n_goals, int32_t *paths, int64_t *info, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

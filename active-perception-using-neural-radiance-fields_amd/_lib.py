@@ -209,6 +209,15 @@ SIGNATURES = {
     "mnf_path_field_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "mnf_path_field": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mnf_path_trace": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mnf_surface_extract_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "mnf_surface_extract": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), c_int64, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_surface_measure": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "mnf_surface_lattice_points_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "mnf_surface_lattice_points": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_int64, c_void_p]),
+    "mnf_surface_lattice_scatter": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "mnf_surface_vertex_attrs": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

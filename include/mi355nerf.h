@@ -985,6 +985,84 @@ int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx, int32_t n
 int mnf_path_trace(const uint32_t *field, int32_t n_fields, int32_t nx, int32_t ny, const int32_t *goals, const int64_t *offsets,
                    int64_t n_goals, int32_t *paths, int64_t *info, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- surface mesh */
+
+/* The geometry a trained field has learnt as a triangle mesh with colours and classes: what the `extract_mesh` of the reference's nerfacc
+ * benchmarks does with a host package, and what simulator/build_point_cloud_from_mesh.py's semantic ground-truth cloud is compared with.
+ * Three parts: the iso-surface of ANY scalar lattice (1), the lattice of a trained field (2), the attributes of the vertices (3).
+ *
+ * 1. mnf_surface_extract: marching tetrahedra on the Kuhn split.
+ * Input: values [X+1][Y+1][Z+1] f32 on the device, x slowest, X = cells_x etc. (1 .. 1024 each); lin(p) = (x (Y+1) + y)(Z+1) + z.  A lattice
+ * point is INSIDE when value > iso: NaN is outside, and so is a value equal to iso.
+ * Tetrahedra.  Every cell c is cut into the same six tetrahedra around its main diagonal; tetrahedron k belongs to the k-th axis
+ * permutation pi in the order (x,y,z), (x,z,y), (y,x,z), (y,z,x), (z,x,y), (z,y,x) and has the vertices v0 = c, v1 = v0 + e_pi1,
+ * v2 = v1 + e_pi2, v3 = c + (1,1,1).  Neighbouring cells cut their common face the same way, so the mesh is watertight and manifold.
+ * Edges.  Every tetrahedron edge has one of 7 directions d, its TYPE: 0 (1,0,0), 1 (0,1,0), 2 (0,0,1), 3 (1,1,0), 4 (1,0,1), 5 (0,1,1),
+ * 6 (1,1,1), and is owned by its lower end p (the other end is p + d).  An edge whose ends differ in inside-ness carries exactly one vertex.
+ * Vertices, in ascending (lin(p), type).  In float32, every operation rounded on its own (a = values[p], b = values[p + d]):
+ *   t = (iso - a) / (b - a), or 0.5f when a or b is not finite;
+ *   pos_k = ((float)p_k + t * (float)d_k) * step_k + origin_k.
+ * Normals.  The lattice difference of axis k at a point q with coordinate i of n points: (values[q + e_k] - values[q - e_k]) * 0.5f for
+ * 0 < i < n - 1, values[q + e_k] - values[q] for i = 0, values[q] - values[q - e_k] for i = n - 1; a difference that is not finite counts
+ * as 0.  With ga, gb those of p and p + d:  g_k = ga_k + t * (gb_k - ga_k);  m_k = (-g_k) / step_k;
+ * len = sqrtf((m_x m_x + m_y m_y) + m_z m_z);  normal_k = m_k / len, or (0,0,0) when len is 0 or not finite.  (The normal points out of
+ * the matter: down the gradient.)
+ * Triangles, in ascending (cell (x Y + y) Z + z, tetrahedron, triangle).  With the tetrahedron's vertices numbered 0..3 and "ab" the
+ * vertex on the edge between a and b:
+ *   one inside a, outside b < c < d:        (ab, ac, ad)
+ *   three inside a < b < c, outside d:      (ad, bd, cd)
+ *   two inside a < b, outside c < d:        (ac, ad, bd), then (ac, bd, bc)
+ * The last two indices of a triangle are swapped where needed so that (q1 - q0) x (q2 - q0) points from the mean of the tetrahedron's inside
+ * vertices to the mean of its outside vertices, evaluated with every crossing at the midpoint of its edge; the sign does not depend on t,
+ * so the swap is a constant of (k, inside bits).
+ * Outputs: positions, normals [max_vertices,3] f32, triangles [max_triangles,3] int32 (vertex indices), info [4] int64 = {vertices,
+ * triangles, vertices - max_vertices if positive else 0, triangles - max_triangles if positive else 0}.  Vertex r is written iff
+ * r < max_vertices; triangle r iff r < max_triangles and its three indices are < max_vertices (it is counted either way, and its slot is
+ * then left as it was).  Nothing is written past either capacity; capacities of 0 (outputs may be NULL) make a counting call.
+ * The mesh is OPEN where matter touches the lattice boundary: no triangle is made on the boundary faces themselves.
+ * workspace: mnf_surface_extract_workspace_bytes(X, Y, Z) bytes (0 for a refused size; about 4.1 bytes per lattice point), 8-byte aligned.
+ *
+ * mnf_surface_measure: out [2] float64 = {area, enclosed volume} of the first min(info[1], max_triangles) triangles, info read on the
+ * device.  Each triangle (a, b, c), its positions widened to float64, adds |(b - a) x (c - a)| / 2 and a . (b x c) / 6; the order of the
+ * sum is not specified.  A triangle with an index outside [0, min(info[0], max_vertices)) adds nothing.  Meaningful when info[2] == info[3] == 0.
+ *
+ * 2. mnf_surface_lattice_points.  binaries [RX][RY][RZ] uint8 (level 0 of the estimator, non-zero = occupied), refine in {1, 2, 4, 8}, aabb
+ * six host floats.  The lattice has (R_k refine + 1) points per axis (R_k refine <= 1024); point i of an axis touches the cells
+ * (i - 1) / refine and i / refine (integer division) that exist: two where i is a multiple of refine, else one.  A point is LISTED when a
+ * cell it touches is occupied or has an occupied cell in its 3 x 3 x 3 neighbourhood clipped at the grid.  The list is in ascending lin:
+ * lin [max_points] int32, positions [max_points,3] f32 with pos_k = aabb_k + (float)i_k * step_k, step_k = (aabb_{3+k} - aabb_k) /
+ * (float)(R_k refine), in float32; info [2] int64 = {points, points - max_points if positive else 0}; nothing is written past the
+ * capacity.  (origin = aabb_0..2 and this step are what mnf_surface_extract takes for such a lattice.)
+ * mnf_surface_lattice_scatter fills values [n_values] with 0 and then writes values[lin[i]] = density[i] for i < min(point_info[0],
+ * max_points), point_info read on the device (a lin outside [0, n_values) is skipped).  Densities are never negative, so with iso > 0 no
+ * surface appears where nothing was evaluated.  The densities come from mnf_field_density at the listed positions.
+ *
+ * 3. mnf_surface_vertex_attrs.  rgb [n,3], sem [n,C] f32 as mnf_field_forward writes them; palette [C,3] uint8 (further rows are not read) or NULL.
+ *   colour [n,3] uint8 = (uint8)(min(max(c, 0), 1) * 255.0f + 0.5f) in float32, 0 for NaN;
+ *   label [n] int32 = the first index of the largest logit, -1 when a logit of the row is NaN;
+ *   sem_colour [n,3] uint8 = palette[label], (0,0,0) for label -1.
+ * Any output may be NULL; sem_colour needs the palette.
+ *
+ * Argument errors (a null required pointer, a size outside the limits, a step that is not finite or not positive, an iso that is not finite,
+ * a refine other than 1, 2, 4, 8, an aabb that is empty or not finite, a negative capacity or one >= 2^31, a workspace or info that is
+ * misaligned, a workspace that is too small) return MNF_ERR_INVALID before any HIP call.  Profile labels: "surface_extract",
+ * "surface_measure", "surface_lattice_points", "surface_lattice_scatter", "surface_vertex_attrs".  Every call enqueues on `stream` and
+ * none synchronises. */
+int64_t mnf_surface_extract_workspace_bytes(int32_t cells_x, int32_t cells_y, int32_t cells_z);
+int mnf_surface_extract(const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
+                        const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals,
+                        int32_t *triangles, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+int mnf_surface_measure(const float *positions, const int32_t *triangles, const int64_t *info, int64_t max_vertices, int64_t max_triangles,
+                        double *out, mnf_stream_t stream);
+int64_t mnf_surface_lattice_points_workspace_bytes(int32_t res_x, int32_t res_y, int32_t res_z, int32_t refine);
+int mnf_surface_lattice_points(const uint8_t *binaries, int32_t res_x, int32_t res_y, int32_t res_z, int32_t refine, const float *aabb_host,
+                               int64_t max_points, int32_t *lin, float *positions, int64_t *info, void *workspace, int64_t workspace_bytes,
+                               mnf_stream_t stream);
+int mnf_surface_lattice_scatter(const float *density, const int32_t *lin, const int64_t *point_info, int64_t max_points, float *values,
+                                int64_t n_values, mnf_stream_t stream);
+int mnf_surface_vertex_attrs(const float *rgb, const float *sem, int64_t n, int32_t n_classes, const uint8_t *palette, uint8_t *colour,
+                             int32_t *label, uint8_t *sem_colour, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,11 @@ SIGNATURES = {
     "mnf_path_field_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "mnf_path_field": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mnf_path_trace": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mnf_scan_map_bytes": (c_int64, [c_int32, c_int32]),
+    "mnf_scan_map_update": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_double), c_double, c_void_p, c_void_p]),
+    "mnf_planner_goal_map": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_planner_goal_pick": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mnf_surface_extract_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "mnf_surface_extract": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), c_int64, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

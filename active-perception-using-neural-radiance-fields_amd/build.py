@@ -47,6 +47,7 @@ SOURCES = {
     "objmap.hip": ["-ffp-contract=off"],    # voxel indices and centroids are chains of separately rounded operations (numpy restates them)
     "explore.hip": ["-ffp-contract=off"],   # the voxel walk is a chain of separately rounded float32 operations (numpy restates it)
     "planning.hip": [],                     # integer labels only: no floating-point work
+    "scanmap.hip": ["-ffp-contract=off"],   # a beam's end cell is a chain of separately rounded float64 operations (numpy restates it)
     "surface.hip": ["-ffp-contract=off"],   # a vertex is a chain of separately rounded float32 operations (numpy restates it)
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],

@@ -2,7 +2,12 @@
 planning/dijkstra.py, which sample_traj (planning/planning_funcs.py:288-326) calls once per sampled goal, as one single-source
 shortest-path field per start cell and paths traced out of it.  A field answers every goal from its start: reached or not, at what
 cost, along which cells.  The definition (moves, exact integer labels, the trace rule) is in include/mi355nerf.h ("planner grid search")
-and DESIGN.md."""
+and DESIGN.md.
+
+Further down, the planner's cost map and goal draw (csrc/scanmap.hip): `ScanCostMap` for `update_cost_map`
+(planning/planning_funcs.py:192-219) and the maps it updates, `goal_cells` for the vm map and free cells of sample_traj (:262-298),
+`draw_goals` for its draw-and-reject loop (:296-326); include/mi355nerf.h ("planner cost map")."""
+import ctypes
 import math
 
 import numpy as np
@@ -199,3 +204,205 @@ class Dijkstra:
         if field is None:
             return torch.full((self.x_width, self.y_width), float("inf"), dtype=torch.float64, device=self.device)
         return field_costs(field)
+
+
+# ---------------------------------------------------------------------- the cost map and the goal draw (csrc/scanmap.hip)
+COST_VALUES = (0.5, 0.0, 1.0)          # the cost codes 0 unknown, 1 free, 2 occupied as the reference's cost_map holds them
+DECAY_ENTRIES = 3728                   # np.exp(-m / 5) is 0.0 from m = 3727 on
+
+
+def align_angles(width):
+    """The angle of every image column from the optical axis (scripts/pipeline.py:227-230 for 640 columns) for any even width."""
+    width = int(width)
+    if width <= 0 or width % 2:
+        raise ValueError(f"align_angles is defined for an even, positive width (got {width}); pass align_angles= for another scan")
+    half = width // 2
+    r = np.arctan(np.linspace(0.5, half - 0.5, half) / half).tolist()
+    r.reverse()
+    l = np.arctan(-np.linspace(0.5, half - 0.5, half) / half).tolist()
+    return np.array(r + l)
+
+
+def yaw_of(poses_c2w):
+    """float64 [V]: the first angle of scipy's `Rotation.from_matrix(R).as_euler("yzx")` (scripts/pipeline.py:275) in closed form.  The
+    extrinsic sequence y, z, x composes to R = Rx(c) Rz(b) Ry(a), whose first row is (cos b cos a, -sin b, cos b sin a); away from the
+    singularity cos b = 0 that makes a = atan2(R[0,2], R[0,0])."""
+    m = np.asarray(poses_c2w, np.float64)
+    m = m.reshape((-1,) + m.shape[-2:])
+    return np.arctan2(m[:, 0, 2], m[:, 0, 0])
+
+
+def _decay_table():
+    return np.exp(-np.arange(DECAY_ENTRIES, dtype=np.float64) / 5)
+
+
+class ScanCostMap:
+    """`cost_map` and `visiting_map` of scripts/pipeline.py:122-125 on the device, and the loops over `update_cost_map`
+    (planning/planning_funcs.py:192-219) at pipeline.py:272-292, :1115-1138 and :1171-1189 as one call per batch of views.  The grid is
+    the reference's (main_grid_resolution[0], main_grid_resolution[2]).  The definition, and the
+    one deliberate difference (a cell with a negative index is skipped and counted, not wrapped round), are in include/mi355nerf.h
+    ("planner cost map")."""
+
+    def __init__(self, aabb, resolution, device="cuda:0"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.MnfError("ScanCostMap lives on a GPU; there is no CPU fallback")
+        if not resolution > 0:
+            raise ValueError(f"resolution must be positive (got {resolution})")
+        self.aabb = np.asarray(aabb.detach().cpu().numpy() if torch.is_tensor(aabb) else aabb).reshape(6)
+        self.resolution = resolution
+        a32 = self.aabb.astype(np.float32)                                             # pipeline.py:113-125
+        n = ((a32[3:] - a32[:3]) / resolution).astype(int).tolist()
+        self.nx, self.nz = int(n[0]), int(n[2])
+        nbytes = int(L.load_library().mnf_scan_map_bytes(self.nx, self.nz)) if self.nx > 0 and self.nz > 0 else 0
+        if nbytes <= 0:
+            raise L.MnfError(f"a {self.nx} x {self.nz} grid is outside what the cost map holds: (nx + 2)(nz + 2) <= 40000")
+        self._aabb_c = (ctypes.c_double * 6)(*[float(v) for v in self.aabb])
+        self.state = torch.zeros(3, self.nx, self.nz, dtype=torch.int32, device=self.device)   # cost codes, visit counts, scratch
+        self._info = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._values = torch.tensor(COST_VALUES, dtype=torch.float64, device=self.device)
+        self._align = {}
+
+    def clear(self):
+        self.state.zero_()
+        self._info.zero_()
+
+    @property
+    def codes(self):
+        """int32 device tensor [nx,nz]: 0 unknown, 1 free, 2 occupied."""
+        return self.state[0]
+
+    @property
+    def visits(self):
+        """int32 device tensor [nx,nz]: how many views left each cell free (what `goal_cells` takes)."""
+        return self.state[1]
+
+    def cost_map(self):
+        """float64 device tensor [nx,nz]: the reference's cost_map (0.5 unknown, 0.0 free, 1.0 occupied)."""
+        return self._values[self.state[0].long()]
+
+    def visiting_map(self):
+        """float64 device tensor [nx,nz]: the reference's self.visiting_map."""
+        return self.state[1].to(torch.float64)
+
+    def info(self):
+        """dict of beam counts since the last clear(): negative_cell (drawn without those cells), bad_depth, far (both skipped), drawn."""
+        v = [int(x) for x in self._info.cpu().numpy()]
+        return {"negative_cell": v[0], "bad_depth": v[1], "far": v[2], "drawn": v[3]}
+
+    def view_inputs(self, poses_c2w):
+        """(yaw [V], loc [V,2], centre [V,2] int32) on the host, formed as scripts/pipeline.py:274-282 forms them."""
+        m = np.asarray(poses_c2w.detach().cpu().numpy() if torch.is_tensor(poses_c2w) else poses_c2w, np.float64)
+        m = m.reshape((-1,) + m.shape[-2:])
+        yaw = yaw_of(m)
+        w_loc = m[:, :3, 3]
+        with np.errstate(invalid="ignore", over="ignore"):
+            g = (w_loc - self.aabb[:3]) // self.resolution
+        far = float((1 << 30) + 1)                                                     # beyond +-2^30 the kernel skips the view's beams
+        g = np.where(np.isfinite(g), np.clip(g, -far, far), far)
+        return yaw, np.ascontiguousarray(w_loc[:, [0, 2]]), np.ascontiguousarray(g[:, [0, 2]].astype(np.int32))
+
+    def _align_device(self, width, align):
+        if align is not None:
+            a = align if torch.is_tensor(align) else torch.from_numpy(np.ascontiguousarray(np.asarray(align, np.float64)))
+            a = L.contig(a.to(self.device), torch.float64).reshape(-1)
+            if int(a.shape[0]) != width:
+                raise ValueError(f"{int(a.shape[0])} align angles for {width} columns")
+            return a
+        if width not in self._align:
+            self._align[width] = torch.from_numpy(align_angles(width)).to(self.device)
+        return self._align[width]
+
+    @torch.no_grad()
+    def update(self, depth_images, poses_c2w, align_angles=None):
+        """Fold the middle rows of `depth_images` [V,H,W] (device or host) taken at `poses_c2w` [V,4,4] into the map, in order.  The
+        depth goes up once if it is on the host; yaw, location and centre cell of every view go up in one small copy."""
+        d = depth_images if torch.is_tensor(depth_images) else torch.from_numpy(np.ascontiguousarray(np.asarray(depth_images)))
+        if d.dim() == 2:
+            d = d[None]
+        if d.dim() != 3:
+            raise ValueError(f"depth_images is [V,H,W] (got {tuple(d.shape)})")
+        d = L.contig(d.to(self.device), torch.float32)
+        V, H, W = (int(v) for v in d.shape)
+        yaw, loc, centre = self.view_inputs(poses_c2w)
+        if yaw.shape[0] != V:
+            raise ValueError(f"{yaw.shape[0]} poses for {V} depth images")
+        if V == 0:
+            return
+        if H <= 0 or W <= 0:
+            raise ValueError(f"empty depth images {tuple(d.shape)}")
+        align = self._align_device(W, align_angles)
+        packed = np.empty(4 * V, np.float64)                                           # yaw | loc | centre (two int32 per float64 slot)
+        packed[:V] = yaw
+        packed[V:3 * V] = loc.reshape(-1)
+        packed[3 * V:].view(np.int32)[:] = centre.reshape(-1)
+        p = torch.from_numpy(packed).to(self.device)
+        L.launch(L.load_library().mnf_scan_map_update, L.ptr(self.state), self.nx, self.nz, L.ptr(d), V, H, W, L.ptr(align), L.ptr(p[:V]),
+                 L.ptr(p[V:3 * V]), L.ptr(p[3 * V:]), self._aabb_c, float(self.resolution), L.ptr(self._info))
+
+    @torch.no_grad()
+    def update_dataset(self, dataset, image_ids, align_angles=None):
+        """`update` from the stored depth images and poses of views `image_ids` of a `Dataset`, either storage layout."""
+        from . import render as RD
+        ids = RD._eval_index_tensor(image_ids, self.device, len(dataset), "image_ids")
+        if int(ids.shape[0]) == 0:
+            return
+        L.require_gpu(dataset.depths, dataset.camtoworlds)
+        H, W = int(dataset.height), int(dataset.width)
+        self.update(dataset.depths[ids].reshape(-1, H, W), dataset.camtoworlds[ids], align_angles=align_angles)
+
+
+@torch.no_grad()
+def goal_cells(blocked, visits, dijkstra=None, start_xy=None):
+    """The vm map of sample_traj (planning/planning_funcs.py:262-276) and the goals worth drawing.  `blocked` [nx,nz] (the
+    path-finding map, > 0 = blocked) and `visits` [nx,nz] (`ScanCostMap.visits`, or any integer counts) on the device; with a `Dijkstra`
+    and its start (`start_xy` = the (sx, sy) given to `planning`) only cells that start reaches are listed.  -> {"vm": float64
+    [nx,nz], "cells": int32 [nx*nz,2] in np.argwhere's order, rows from `count` on are -1, "count": int64 [1]}: device tensors, one
+    launch, no synchronisation."""
+    blocked = blocked if torch.is_tensor(blocked) else torch.from_numpy(np.ascontiguousarray(np.asarray(blocked)))
+    visits = visits if torch.is_tensor(visits) else torch.from_numpy(np.ascontiguousarray(np.asarray(visits)))
+    L.require_gpu(blocked, visits)
+    dev = blocked.device
+    if blocked.dim() != 2 or tuple(visits.shape) != tuple(blocked.shape):
+        raise ValueError(f"blocked and visits are [nx,nz] (got {tuple(blocked.shape)} and {tuple(visits.shape)})")
+    if visits.dtype.is_floating_point:
+        visits = visits.round()
+    b, v = L.contig(blocked, torch.int32), L.contig(visits, torch.int32)
+    nx, nz = int(b.shape[0]), int(b.shape[1])
+    if nx <= 0 or nz <= 0 or int(L.load_library().mnf_scan_map_bytes(nx, nz)) <= 0:
+        raise L.MnfError(f"a {nx} x {nz} map is outside the planner's cap: (nx + 2)(nz + 2) <= 40000")
+    field = None
+    if dijkstra is not None:
+        if start_xy is None:
+            raise ValueError("a Dijkstra needs start_xy = (sx, sy)")
+        if (dijkstra.x_width, dijkstra.y_width) != (nx, nz):
+            raise ValueError(f"the Dijkstra's map is {dijkstra.x_width} x {dijkstra.y_width}, blocked is {nx} x {nz}")
+        field = dijkstra._field(float(start_xy[0]), float(start_xy[1]))
+        if field is None:                                                              # a start outside the map reaches nothing
+            field = torch.full((nx, nz), UNREACHED, dtype=torch.int32, device=dev)
+        field = field.contiguous()
+    decay = torch.from_numpy(_decay_table()).to(dev)
+    vm = torch.empty(nx, nz, dtype=torch.float64, device=dev)
+    cells = torch.empty(nx * nz, 2, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    L.launch(L.load_library().mnf_planner_goal_map, L.ptr(b), L.ptr(v), L.ptr(field), nx, nz, L.ptr(decay), DECAY_ENTRIES, L.ptr(vm), L.ptr(cells),
+             L.ptr(count))
+    return {"vm": vm, "cells": cells, "count": count}
+
+
+@torch.no_grad()
+def draw_goals(cells, count, u):
+    """int32 device tensor [N,2]: cells[min(floor(u * count), count - 1)] for uniforms `u` [N] in [0, 1) from the caller's generator,
+    (-1, -1) when there is no goal.  Uniform over the free cells the start reaches: the distribution of the reference's
+    draw-and-reject loop (planning_funcs.py:296-326), not its random stream."""
+    L.require_gpu(cells, count)
+    dev = cells.device
+    if cells.dtype != torch.int32 or count.dtype != torch.int64:
+        raise TypeError("cells and count are the tensors goal_cells returns")
+    u = u if torch.is_tensor(u) else torch.from_numpy(np.ascontiguousarray(np.asarray(u, np.float64)).reshape(-1))
+    u = L.contig(u.to(dev), torch.float64).reshape(-1)
+    cells = cells.contiguous()
+    n = int(u.shape[0])
+    goals = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    L.launch(L.load_library().mnf_planner_goal_pick, L.ptr(cells), L.ptr(count), int(cells.shape[0]), L.ptr(u), n, L.ptr(goals))
+    return goals

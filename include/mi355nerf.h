@@ -985,6 +985,69 @@ int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx, int32_t n
 int mnf_path_trace(const uint32_t *field, int32_t n_fields, int32_t nx, int32_t ny, const int32_t *goals, const int64_t *offsets,
                    int64_t n_goals, int32_t *paths, int64_t *info, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- planner cost map */
+
+/* The planner's 2-D cost map and visit counts, which the reference updates from the middle row of every sampled depth image
+ * (update_cost_map, planning/planning_funcs.py:192-219, over generate_ray_casting_grid_map and bresenham,
+ * perception/data_proc/depth_to_grid.py:31-73, :142-182; called at scripts/pipeline.py:272-292, :1115-1138 and :1171-1189), and the goal
+ * draw of sample_traj: its vm map (planning_funcs.py:262-276) and its draw-and-reject loop (planning_funcs.py:296-326).
+ *
+ * The scan.  depth [n_views][height][width] f32; the kernel reads row height / 2 of every view as a planar scan of `width` beams.  align
+ * [width] f64 (the angle of a column from the optical axis), yaw [n_views] f64, loc [n_views][2] f64 (world x and z of the camera), centre
+ * [n_views][2] int32 (the camera's cell, g_loc[0] and g_loc[2] of the reference), all on the device; aabb_host six host doubles, res the
+ * cell size; the grid is nx x nz cells.  Per view in order and per beam j in order, in float64 with every operation rounded on its own
+ * (d = the depth widened to float64):
+ *   a  = (align[j] + yaw) mod 2 pi, with Python's sign rule (fmod, plus 2 pi where that is negative);
+ *   ox = sin(-a) d + loc_x,   oy = (-cos(-a)) d + loc_z;
+ *   ix = rint((ox - aabb[2]) / res),   iy = rint((oy - aabb[0]) / res)   (round-half-even, Python's round).
+ * The reference subtracts aabb[2] from an x coordinate and aabb[0] from a z coordinate; that is reproduced, not repaired.
+ * Every cell of the reference's Bresenham walk from centre to (ix, iy) becomes FREE.  The walk (depth_to_grid.py:31-73): with (x1, y1) =
+ * centre and (x2, y2) = (ix, iy), swap x and y of both ends when |y2 - y1| > |x2 - x1| ("steep"), then swap the ends when x1 > x2; with
+ * dx = x2 - x1, e0 = dx / 2 (integer) and ystep = 1 if y1 < y2 else -1, column k = 0 .. dx holds the cell (x1 + k, y1 + ystep s_k) (swapped
+ * back when steep), where s_k = 0 for dx = 0 and otherwise (k |y2 - y1| - e0 + dx - 1) / dx in integer division: the number of times the
+ * loop's error term has gone negative before column k.  Then the cells (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) become
+ * OCCUPIED.  A later write wins, within a view and across views.  After a view, cost is 1.0 where the view left a cell occupied, 0.0 where
+ * it left it free, and a cell it left free adds one to that cell's visit count (visiting_map, which the callers sum over views).
+ * Order without a serial loop: every write carries the key 2 j + occ + 1; keys are combined with an integer max on the view's plane, a cell's
+ * state in a view is (largest key - 1) & 1, and views are ordered the same way by the key 2 (v + 1) + occ.  All atomics are integer max
+ * or add; the result does not depend on the schedule and no floating-point value is accumulated.
+ * Cells outside the grid.  A cell at or beyond the grid on the high side is skipped, as in the reference.  A cell with a NEGATIVE index is
+ * skipped too and its beam counted: the reference wraps such a cell round through Python's negative indexing, or raises.  This is the one
+ * deliberate difference.  A beam whose depth is not finite is skipped whole and counted; so is a beam whose end cell or centre lies
+ * beyond +-2^30 in either index (a NaN among yaw, loc or align ends here too).  The work of a beam is bounded by the grid, not by its depth.
+ *
+ * State: mnf_scan_map_bytes(nx, nz) = 3 * nx * nz * 4 bytes, or 0 for a grid outside the planner's cap (nx + 2)(nz + 2) <= 40 000: three
+ * int32 planes [nx][nz], the cost code (0 unknown = 0.5, 1 free = 0.0, 2 occupied = 1.0), the visit counts, and a scratch plane the update
+ * clears itself.  A new map is a memset to 0.  mnf_scan_map_update adds to info [4] int64 = {beams with a negative cell, beams with a
+ * non-finite depth, beams beyond +-2^30, beams drawn (the first kind included)}; the caller clears it.  One launch walks every view of the
+ * batch (one workgroup per view, its key plane in LDS), a second small one writes the cost codes.  n_views == 0 is a legal no-op.  A batch
+ * and the same views given one call at a time leave the same cost codes, visit counts and info.
+ *
+ * mnf_planner_goal_map.  blocked [nx][nz] int32 (mnf_planner_map's output as it stands; a cell is FREE when its value is not above 0, the
+ * reference's `> 1e-4` on integers), visits [nx][nz] int32, field [nx][nz] uint32 of mnf_path_field for the start cell, or NULL.
+ *   vm [nx][nz] f64 = -1 on blocked cells, decay[visits - least] on free ones, least = the smallest visit count of a free cell; decay
+ *   [n_decay] f64 is the caller's table decay[m] = exp(-m / 5) in float64 (a difference of n_decay or more reads as 0.0, which
+ *   exp(-m / 5) is from m = 3727 on), so vm holds the bytes the caller's own exp gives, as planning_funcs.py:268-276 forms them.
+ *   cells [nx nz][2] int32: the cells with vm >= 0 that, where a field is given, are reached in it, in row-major order (np.argwhere's), by an
+ *   ordered prefix sum; rows from count on are -1.  count [1] int64.  The same inputs give the same bytes.
+ * mnf_planner_goal_pick.  u [n_draws] f64 in [0, 1) from the caller's generator; goals [n_draws][2] int32 = cells[min(floor(u n), n - 1)]
+ * with n = min(count[0], max_cells) read on the device, (-1, -1) when n is 0; a u below 0 or NaN takes the first cell.  This has the
+ * distribution of the reference's loop (a uniform free cell, redrawn until planning() finds a way); it does not reproduce the
+ * reference's random stream.  The reference's visit weighting is multiplied by 0 (planning_funcs.py:301) and is left out.
+ *
+ * Argument errors (a null required pointer, a size that is not positive or beyond the cap, a height or width that is not positive, a
+ * negative count, an aabb or res that is not finite, res <= 0, n_decay < 1, a misaligned pointer) return MNF_ERR_INVALID before any
+ * HIP call.  Profile labels: "scan_map_update", "planner_goal_map", "planner_goal_pick".  Every call enqueues on `stream` and none
+ * synchronises.  There is no CPU fallback. */
+int64_t mnf_scan_map_bytes(int32_t nx, int32_t nz);
+int mnf_scan_map_update(void *state, int32_t nx, int32_t nz, const float *depth, int32_t n_views, int32_t height, int32_t width,
+                        const double *align, const double *yaw, const double *loc, const int32_t *centre, const double *aabb_host, double res,
+                        int64_t *info, mnf_stream_t stream);
+int mnf_planner_goal_map(const int32_t *blocked, const int32_t *visits, const uint32_t *field, int32_t nx, int32_t nz, const double *decay,
+                         int32_t n_decay, double *vm, int32_t *cells, int64_t *count, mnf_stream_t stream);
+int mnf_planner_goal_pick(const int32_t *cells, const int64_t *count, int64_t max_cells, const double *u, int64_t n_draws, int32_t *goals,
+                          mnf_stream_t stream);
+
 /* ---------------------------------------------------------------- surface mesh */
 
 /* The geometry a trained field has learnt as a triangle mesh with colours and classes: what the `extract_mesh` of the reference's nerfacc

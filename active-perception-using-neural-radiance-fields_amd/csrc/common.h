@@ -55,6 +55,11 @@ inline hipStream_t as_stream(mnf_stream_t s) { return reinterpret_cast<hipStream
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// workgroups of `threads` lanes, one lane per element; at least one
+inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, threads); }
+
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 // Diagnostic knobs (tools/README.md) exist only in the -DMNF_DIAG build (libmi355nerf_diag.so): the product library never
 // reads the environment, so no stray variable can change its results, its round schedule or its timings.
 #ifdef MNF_DIAG

@@ -5,9 +5,7 @@
 //   mnf_explore_map_frontiers          <- frontier_baseline.py:52-67 (find_frontiers, its inner-loop-only `break` included)
 //   mnf_explore_map_frontier_clusters  <- frontier_baseline.py:191-214 (DBSCAN(eps=1, min_samples=3), the member nearest to the current pose)
 //
-// The map: uint32 bits[2][wpp], plane 0 = "a ray passed through", plane 1 = "a ray ended here"; voxel (x, y, z) is bit (lin & 31) of word
-// plane * wpp + (lin >> 5), lin = (x * Y + y) * Z + z, wpp = ceil(X Y Z / 32) rounded up to an even number: the object map's layout (objmap.hip)
-// with two planes, and its limits on the geometry.  Tail bits are never set by the insert and masked by every reader.
+// The map: uint32 bits[2][wpp], the bit grid of map_dev.h with two planes: plane 0 = "a ray passed through", plane 1 = "a ray ended here".
 //
 // Insert: one lane per pixel walks its voxels from the origin's to the end point's, exactly n_x + n_y + n_z steps (include/mi355nerf.h has the
 // definition).  Built with -ffp-contract=off: every float expression is one separately rounded operation, as numpy evaluates it.  Only the
@@ -18,36 +16,14 @@
 // clear, one 32-bit atomic OR.  Neighbouring pixels walk nearly the same voxels, so most loads are L2 hits and most runs find their bits set.
 // Read-outs: count and top-down read the two planes once; frontiers reads the [X][Z] byte map nine times (L1 / L2 hits) in one workgroup, in
 // row-major order, which is what orders its output; the clusters are O(X Z + frontier cells).
-#include "common.h"
+#include "map_dev.h"
+#include "workspace.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kMaxAxis = 1 << 24;
 constexpr float kMaxIndex = 16777216.0f;      // 2^24: below it a floored float converts to int exactly
 constexpr int kMaxOffsets = 32;               // offsets with dx^2 + dz^2 <= 8, the centre excluded: 24
-
-struct Grid { int X, Y, Z; int64_t n_vox; int64_t wpp; };
-
-// false when the geometry is refused: the object map's rules (objmap.hip: make_grid) with two planes
-inline bool make_grid(int32_t X, int32_t Y, int32_t Z, Grid *g) {
-    if (X <= 0 || Y <= 0 || Z <= 0) return false;
-    if (X > kMaxAxis || Y > kMaxAxis || Z > kMaxAxis) return false;
-    if ((int64_t)X * Y > (int64_t)1 << 31) return false;
-    const int64_t n = (int64_t)X * Y * Z;
-    if (n > ((int64_t)1 << 31) - 64) return false;
-    const int64_t wpp = (ceil_div(n, 32) + 1) & ~(int64_t)1;
-    if (wpp * 2 > ((int64_t)1 << 31) - 1) return false;
-    *g = {X, Y, Z, n, wpp};
-    return true;
-}
-
-__device__ __forceinline__ unsigned int valid_bits(int64_t w, int64_t n_vox) {
-    const int64_t left = n_vox - w * 32;
-    return left >= 32 ? 0xffffffffu : left <= 0 ? 0u : (1u << (int)left) - 1u;
-}
-
-inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, threads); }
 
 // ---------------------------------------------------------------------------------------------------------------- insert
 // a plain load first, the atomic only where a bit of `m` is clear; a stale "clear" only repeats the OR.  (Joining the ORs of a wave's lanes into one per
@@ -59,7 +35,7 @@ __device__ __forceinline__ void or_bits(unsigned int *word, unsigned int m, int 
 
 __global__ void __launch_bounds__(256) explore_insert_kernel(
     const float *__restrict__ origins, const float *__restrict__ viewdirs, const float *__restrict__ depth, const float *__restrict__ acc, int64_t N,
-    float gx, float gy, float gz, float vs, float inv, Grid g, float min_depth, float min_acc, float max_range, unsigned int *bits,
+    float gx, float gy, float gz, float vs, float inv, BitGrid g, float min_depth, float min_acc, float max_range, unsigned int *bits,
     unsigned long long *stats) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int steps = 0, ors = 0;
@@ -150,7 +126,7 @@ __global__ void __launch_bounds__(256) explore_insert_kernel(
 
 // ---------------------------------------------------------------------------------------------------------------- count
 // counts[] is zeroed before the launch; integer atomics: exact, whatever the order
-__global__ void __launch_bounds__(256) explore_count_kernel(const unsigned int *__restrict__ bits, Grid g, int64_t *__restrict__ counts) {
+__global__ void __launch_bounds__(256) explore_count_kernel(const unsigned int *__restrict__ bits, BitGrid g, int64_t *__restrict__ counts) {
     __shared__ int64_t red[4][3];
     const int tid = threadIdx.x;
     const int64_t words = (g.n_vox + 31) >> 5;
@@ -172,7 +148,7 @@ __global__ void __launch_bounds__(256) explore_count_kernel(const unsigned int *
 
 // ---------------------------------------------------------------------------------------------------------------- top-down
 // one lane per cell (x, z); neighbouring lanes read neighbouring bits
-__global__ void __launch_bounds__(256) explore_topdown_kernel(const unsigned int *__restrict__ bits, Grid g, int y_lo, int y_hi, int8_t *__restrict__ map) {
+__global__ void __launch_bounds__(256) explore_topdown_kernel(const unsigned int *__restrict__ bits, BitGrid g, int y_lo, int y_hi, int8_t *__restrict__ map) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= (int64_t)g.X * g.Z) return;
     const int64_t x = c / g.Z, z = c - x * g.Z;
@@ -194,8 +170,7 @@ constexpr int kFrontierThreads = 1024;
 // before it: the output is ordered without a workspace.  At most X Z cells; a map of 500 x 500 is 245 batches.
 __global__ void __launch_bounds__(kFrontierThreads) explore_frontiers_kernel(const int8_t *__restrict__ map, int X, int Z, int64_t cap, int *__restrict__ cells,
                                                                             int *__restrict__ mult, int64_t *__restrict__ info) {
-    __shared__ int wave_total[kFrontierThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t total = (int64_t)X * Z;
     int64_t base = 0;
     for (int64_t c0 = 0; c0 < total; c0 += kFrontierThreads) {
@@ -215,21 +190,10 @@ __global__ void __launch_bounds__(kFrontierThreads) explore_frontiers_kernel(con
                 m += any ? 1 : 0;
             }
         }
-        const unsigned long long votes = __ballot(m > 0);
-        if (lane == 0) wave_total[wave] = __popcll(votes);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < kFrontierThreads / 64; ++w) {
-            const int n = wave_total[w];
-            before += w < wave ? n : 0;
-            all += n;
-        }
-        if (m > 0) {
-            const int64_t r = base + before + __popcll(votes & ((1ull << lane) - 1ull));
-            if (r < cap) { cells[2 * r] = x; cells[2 * r + 1] = z; mult[r] = m; }
-        }
+        int all;
+        const int64_t r = base + block_rank<kFrontierThreads>(m > 0, &all);
+        if (m > 0 && r < cap) { cells[2 * r] = x; cells[2 * r + 1] = z; mult[r] = m; }
         base += all;
-        __syncthreads();                                             // wave_total is read
     }
     if (tid == 0) { info[0] = base; info[1] = base > cap ? 1 : 0; }
 }
@@ -245,22 +209,19 @@ struct ClusterWs {
     int64_t bytes;
 };
 
-inline int64_t scan_bytes(int64_t n) { return mnf_scan_workspace_bytes(n > 0 ? n : 1); }
-
 inline ClusterWs carve(void *base, int64_t cells, int64_t mf, int64_t mc) {
-    char *p = (char *)base;
-    auto take = [&](int64_t bytes) { char *q = p; p += (bytes + 7) & ~(int64_t)7; return q; };
+    Carver c(base, 8);
     ClusterWs w;
-    w.flag = (int64_t *)take(mf * 8);
-    w.row = (int64_t *)take(mf * 8);
-    w.scan = (int64_t *)take(scan_bytes(mf));
-    w.totals = (int64_t *)take(8);
-    w.best = (unsigned long long *)take(mc * 8);
-    w.index = (int *)take(cells * 4);
-    w.parent = (int *)take(mf * 4);
-    w.core = (int *)take(mf * 4);
-    w.goal = (int *)take(mc * 4);
-    w.bytes = (int64_t)(p - (char *)base);
+    w.flag = c.take<int64_t>(mf);
+    w.row = c.take<int64_t>(mf);
+    w.scan = (int64_t *)c.take(scan_bytes(mf));
+    w.totals = c.take<int64_t>(1);
+    w.best = c.take<unsigned long long>(mc);
+    w.index = c.take<int>(cells);
+    w.parent = c.take<int>(mf);
+    w.core = c.take<int>(mf);
+    w.goal = c.take<int>(mc);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -303,33 +264,7 @@ __global__ void __launch_bounds__(256) fc_core_kernel(const int *__restrict__ ce
     core[i] = sum >= min_samples ? 1 : 0;
 }
 
-// the object map's union-find (objmap.hip): parent[] is shared between the workgroups of the link launch, every access is an agent-scope atomic,
-// the larger root is hooked under the smaller, so a component's root is its smallest member whatever the schedule
-__device__ __forceinline__ int load_parent(int *parent, int i) { return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int find_root(int *parent, int i) {
-    int p = load_parent(parent, i);
-    while (p != i) {                                                 // parent[i] < i for every non-root: the walk strictly descends
-        const int gp = load_parent(parent, p);
-        if (gp != p) __hip_atomic_store(parent + i, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void unite(int *parent, int a, int b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }                // a > b
-        const int old = atomicCAS(parent + a, a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
+// the union-find over the list positions of the core cells: map_dev.h
 __global__ void __launch_bounds__(256) fc_link_kernel(const int *__restrict__ cells, const int64_t *__restrict__ finfo, int64_t mf, int X, int Z, Offsets offs,
                                                      const int *__restrict__ index, const int *__restrict__ core, int *parent) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -349,13 +284,7 @@ __global__ void __launch_bounds__(256) fc_flag_kernel(const int *__restrict__ pa
     flag[i] = (i < listed(finfo, mf) && core[i] && parent[i] == (int)i) ? 1 : 0;
 }
 
-// the link launch is over: parent[] is read-only here
-__device__ __forceinline__ int settled_root(const int *__restrict__ parent, int i) {
-    for (int p = parent[i]; p != i; p = parent[i]) i = p;
-    return i;
-}
-
-// labels, member counts and the smallest squared distance per cluster
+// labels, member counts and the smallest squared distance per cluster (the link launch is over: parent[] is read-only here)
 __global__ void __launch_bounds__(256) fc_label_kernel(const int *__restrict__ cells, const int64_t *__restrict__ finfo, int64_t mf, int X, int Z, Offsets offs,
                                                       const int *__restrict__ index, const int *__restrict__ core, const int *__restrict__ parent,
                                                       const int64_t *__restrict__ row, double cur_x, double cur_z, int64_t mc, int *__restrict__ labels,
@@ -411,17 +340,17 @@ __global__ void __launch_bounds__(256) fc_finish_kernel(const int *__restrict__ 
 using namespace mnf;
 
 extern "C" int64_t mnf_explore_map_bytes(int32_t res_x, int32_t res_y, int32_t res_z) {
-    Grid g;
-    if (!make_grid(res_x, res_y, res_z, &g)) return 0;
+    BitGrid g;
+    if (!make_bit_grid(2, res_x, res_y, res_z, &g)) return 0;
     return g.wpp * 2 * (int64_t)sizeof(uint32_t);
 }
 
 extern "C" int mnf_explore_map_insert(uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, const float *grid_min_host, float voxel_size,
                                       float max_range, const float *origins, const float *viewdirs, const float *depth, const float *acc,
                                       int64_t n_rays, float min_depth, float min_acc, int64_t *stats, mnf_stream_t stream) {
-    Grid g;
+    BitGrid g;
     MNF_REQUIRE(res_x > 0 && res_y > 0 && res_z > 0, "explore_map_insert: resolution must be positive (got %d x %d x %d)", res_x, res_y, res_z);
-    MNF_REQUIRE(make_grid(res_x, res_y, res_z, &g), "explore_map_insert: resolution %d x %d x %d is more than the map indexes", res_x, res_y, res_z);
+    MNF_REQUIRE(make_bit_grid(2, res_x, res_y, res_z, &g), "explore_map_insert: resolution %d x %d x %d is more than the map indexes", res_x, res_y, res_z);
     MNF_REQUIRE(voxel_size > 0.0f && voxel_size - voxel_size == 0.0f, "explore_map_insert: voxel_size must be positive and finite (got %g)", (double)voxel_size);
     MNF_REQUIRE(max_range > 0.0f && max_range - max_range == 0.0f, "explore_map_insert: max_range must be positive and finite (got %g)", (double)max_range);
     MNF_REQUIRE(max_range / voxel_size <= 1048576.0f, "explore_map_insert: max_range / voxel_size is more than 2^20 voxels (got %g)",
@@ -434,8 +363,8 @@ extern "C" int mnf_explore_map_insert(uint32_t *bits, int32_t res_x, int32_t res
     MNF_REQUIRE(origins || n_rays == 0, "explore_map_insert: origins is null");
     MNF_REQUIRE(viewdirs || n_rays == 0, "explore_map_insert: viewdirs is null");
     MNF_REQUIRE(depth || n_rays == 0, "explore_map_insert: depth is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(bits) & 7) == 0, "explore_map_insert: bits must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 7) == 0, "explore_map_insert: stats must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(bits), "explore_map_insert: bits must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(stats), "explore_map_insert: stats must be 8-byte aligned");
     if (n_rays == 0) return MNF_OK;
     const float inv = 1.0f / voxel_size;
     hipStream_t s = as_stream(stream);
@@ -447,8 +376,8 @@ extern "C" int mnf_explore_map_insert(uint32_t *bits, int32_t res_x, int32_t res
 }
 
 extern "C" int mnf_explore_map_count(const uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, int64_t *counts, mnf_stream_t stream) {
-    Grid g;
-    MNF_REQUIRE(make_grid(res_x, res_y, res_z, &g), "explore_map_count: bad geometry (resolution %d x %d x %d)", res_x, res_y, res_z);
+    BitGrid g;
+    MNF_REQUIRE(make_bit_grid(2, res_x, res_y, res_z, &g), "explore_map_count: bad geometry (resolution %d x %d x %d)", res_x, res_y, res_z);
     MNF_REQUIRE(bits, "explore_map_count: bits is null");
     MNF_REQUIRE(counts, "explore_map_count: counts is null");
     hipStream_t s = as_stream(stream);
@@ -462,8 +391,8 @@ extern "C" int mnf_explore_map_count(const uint32_t *bits, int32_t res_x, int32_
 
 extern "C" int mnf_explore_map_topdown(const uint32_t *bits, int32_t res_x, int32_t res_y, int32_t res_z, int32_t y_lo, int32_t y_hi, int8_t *map,
                                        mnf_stream_t stream) {
-    Grid g;
-    MNF_REQUIRE(make_grid(res_x, res_y, res_z, &g), "explore_map_topdown: bad geometry (resolution %d x %d x %d)", res_x, res_y, res_z);
+    BitGrid g;
+    MNF_REQUIRE(make_bit_grid(2, res_x, res_y, res_z, &g), "explore_map_topdown: bad geometry (resolution %d x %d x %d)", res_x, res_y, res_z);
     MNF_REQUIRE(y_lo >= 0 && y_lo <= y_hi && y_hi <= res_y, "explore_map_topdown: layers [y_lo, y_hi) = [%d, %d) outside [0, %d]", y_lo, y_hi, res_y);
     MNF_REQUIRE(bits, "explore_map_topdown: bits is null");
     MNF_REQUIRE(map, "explore_map_topdown: map is null");
@@ -515,7 +444,7 @@ extern "C" int mnf_explore_map_frontier_clusters(const int32_t *cells, const int
     MNF_REQUIRE(sizes || max_clusters == 0, "explore_map_frontier_clusters: sizes is null");
     MNF_REQUIRE(info, "explore_map_frontier_clusters: info is null");
     MNF_REQUIRE(workspace, "explore_map_frontier_clusters: workspace is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "explore_map_frontier_clusters: workspace must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(workspace), "explore_map_frontier_clusters: workspace must be 8-byte aligned");
     const int64_t n_cells = (int64_t)res_x * res_z, mf = max_frontiers, mc = max_clusters;
     const ClusterWs w = carve(workspace, n_cells, mf, mc);
     MNF_REQUIRE(workspace_bytes >= w.bytes, "explore_map_frontier_clusters: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,

@@ -5,57 +5,33 @@
 //   mnf_object_map_clusters  <- eval_pipeline_offline.py:26-42 (get_pointcloud, DBSCAN(eps=0.2, min_samples=1), the mean per label)
 //   mnf_object_map_match     <- eval_pipeline_offline.py:45-70 (greedy nearest unmatched ground-truth object per cluster)
 //
-// The map: uint32 bits[C][wpp], voxel (x, y, z) of class c is bit (lin & 31) of word c * wpp + (lin >> 5), lin = (x * Y + y) * Z + z (the
-// estimator's layout); wpp = ceil(X Y Z / 32) rounded up to an even number, so every plane starts 8-byte aligned.  The tail bits of a plane are
-// never set by the insert and are masked by every reader.
+// The map: uint32 bits[C][wpp], the bit grid of map_dev.h with one plane per class.
 //
 // Linkage is defined on integer voxel offsets (dx^2 + dy^2 + dz^2 <= link_r2), so with min_samples = 1 the clusters are the connected
-// components of that graph: a lock-free union-find over the RANKS of the set voxels (rank = position in class-then-linear-index order, found
-// in constant time as prefix[word] + popc(word & below)) that always hooks the larger root under the smaller.  A component's root is then its
-// smallest rank whatever the schedule, the per-cluster sums are integers, and the centroid is formed from them in float64: the same grid gives
-// the same bytes.  Built with -ffp-contract=off: every float expression is one separately rounded operation, as numpy evaluates it.
+// components of that graph: the union-find of map_dev.h over the RANKS of the set voxels (rank = position in class-then-linear-index order,
+// found in constant time as prefix[word] + popc(word & below)).  A component's root is then its smallest rank whatever the schedule, the
+// per-cluster sums are integers, and the centroid is formed from them in float64: the same grid gives the same bytes.  Built with
+// -ffp-contract=off: every float expression is one separately rounded operation, as numpy evaluates it.
 //
 // Traffic.  Insert: 12 + 12 + 4 (+ 4) bytes of rays, depth and acc and 4 C bytes of logits per pixel, read once (the logits through LDS:
 // view_dev.h's stage_rows), one 4-byte bit test and, only where the bit is clear, one 32-bit atomic OR.  Clusters: the bit grid is read three
 // times (popcount, enumerate, and as the neighbour test of the link pass: 16 word reads per set voxel at link_r2 = 4, L2 hits), the rest is
 // O(set voxels).
+#include "map_dev.h"
 #include "view_dev.h"
+#include "workspace.h"
 
 namespace mnf {
 namespace {
 
 constexpr int kInsertMaxBlocks = 2048;
-constexpr int kMaxAxis = 1 << 24;
 constexpr int kMaxOffsets = 64;               // forward half of the offsets with squared length <= 8: 58
-
-struct Grid { int X, Y, Z; int64_t n_vox; int64_t wpp; };
-
-inline int64_t words_per_plane(int64_t n_vox) { return (ceil_div(n_vox, 32) + 1) & ~(int64_t)1; }
-
-// false when the geometry is refused
-inline bool make_grid(int32_t C, int32_t X, int32_t Y, int32_t Z, Grid *g) {
-    if (C <= 0 || X <= 0 || Y <= 0 || Z <= 0) return false;
-    if (X > kMaxAxis || Y > kMaxAxis || Z > kMaxAxis) return false;  // (float)res is exact: the insert compares a floored float against it
-    if ((int64_t)X * Y > (int64_t)1 << 31) return false;
-    const int64_t n = (int64_t)X * Y * Z;
-    if (n > ((int64_t)1 << 31) - 64) return false;
-    const int64_t wpp = words_per_plane(n);
-    if (wpp * C > ((int64_t)1 << 31) - 1) return false;
-    *g = {X, Y, Z, n, wpp};
-    return true;
-}
-
-// the bits of word w of a plane that stand for voxels
-__device__ __forceinline__ unsigned int valid_bits(int64_t w, int64_t n_vox) {
-    const int64_t left = n_vox - w * 32;
-    return left >= 32 ? 0xffffffffu : left <= 0 ? 0u : (1u << (int)left) - 1u;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- insert
 __global__ void __launch_bounds__(kViewThreads) object_map_insert_kernel(
     const float *__restrict__ origins, const float *__restrict__ viewdirs, const float *__restrict__ depth, const float *__restrict__ acc,
     const float *__restrict__ sem, const void *__restrict__ labels, int label_is_u8, int64_t N, int C, int tp, int64_t tiles,
-    float gx, float gy, float gz, float inv, Grid g, int first_class, float min_depth, float max_depth, float min_acc,
+    float gx, float gy, float gz, float inv, BitGrid g, int first_class, float min_depth, float max_depth, float min_acc,
     unsigned int *__restrict__ bits) {
     extern __shared__ float stage[];                                 // [tp][C | 1], logits only
     const int tid = threadIdx.x, nb = gridDim.x, b = blockIdx.x;
@@ -106,7 +82,7 @@ __global__ void __launch_bounds__(kViewThreads) object_map_insert_kernel(
 
 // ---------------------------------------------------------------------------------------------------------------- count
 // one workgroup per class
-__global__ void __launch_bounds__(256) object_map_count_kernel(const unsigned int *__restrict__ bits, Grid g, int64_t *__restrict__ counts) {
+__global__ void __launch_bounds__(256) object_map_count_kernel(const unsigned int *__restrict__ bits, BitGrid g, int64_t *__restrict__ counts) {
     __shared__ int64_t red[4];
     const int c = blockIdx.x, tid = threadIdx.x;
     const int64_t words = (g.n_vox + 31) >> 5;
@@ -130,29 +106,26 @@ struct ClusterWs {
     int64_t bytes;
 };
 
-inline int64_t scan_bytes(int64_t n) { return mnf_scan_workspace_bytes(n > 0 ? n : 1); }
-
-inline ClusterWs carve(void *base, const Grid &g, int C, int64_t mv) {
-    char *p = (char *)base;
-    auto take = [&](int64_t bytes) { char *q = p; p += (bytes + 7) & ~(int64_t)7; return q; };
+inline ClusterWs carve(void *base, const BitGrid &g, int C, int64_t mv) {
+    Carver c(base, 8);
     const int64_t nw = g.wpp * C;
     ClusterWs w;
-    w.wordcnt = (int64_t *)take(nw * 8);
-    w.prefix = (int64_t *)take(nw * 8);
-    w.scan = (int64_t *)take(scan_bytes(nw > mv ? nw : mv));
-    w.totals = (int64_t *)take(16);
-    w.vox = (int64_t *)take(mv * 8);
-    w.flag = (int64_t *)take(mv * 8);
-    w.row = (int64_t *)take(mv * 8);
-    w.sums = (int64_t *)take(mv * 32);                               // a row per kept cluster: there are no more clusters than voxels
-    w.parent = (int *)take(mv * 4);
-    w.root = (int *)take(mv * 4);
-    w.size = (int *)take(mv * 4);
-    w.bytes = (int64_t)(p - (char *)base);
+    w.wordcnt = c.take<int64_t>(nw);
+    w.prefix = c.take<int64_t>(nw);
+    w.scan = (int64_t *)c.take(scan_bytes(nw > mv ? nw : mv));
+    w.totals = c.take<int64_t>(2);
+    w.vox = c.take<int64_t>(mv);
+    w.flag = c.take<int64_t>(mv);
+    w.row = c.take<int64_t>(mv);
+    w.sums = c.take<int64_t>(mv * 4);                                // a row per kept cluster: there are no more clusters than voxels
+    w.parent = c.take<int>(mv);
+    w.root = c.take<int>(mv);
+    w.size = c.take<int>(mv);
+    w.bytes = c.bytes();
     return w;
 }
 
-__global__ void __launch_bounds__(256) popcount_words_kernel(const unsigned int *__restrict__ bits, Grid g, int64_t nw, int64_t *__restrict__ wordcnt) {
+__global__ void __launch_bounds__(256) popcount_words_kernel(const unsigned int *__restrict__ bits, BitGrid g, int64_t nw, int64_t *__restrict__ wordcnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nw) return;
     wordcnt[i] = __popc(bits[i] & valid_bits(i % g.wpp, g.n_vox));
@@ -170,7 +143,7 @@ __global__ void __launch_bounds__(256) clusters_init_kernel(const int64_t *__res
 }
 
 // one lane per word: the set voxels in class-then-linear-index order
-__global__ void __launch_bounds__(256) enumerate_kernel(const unsigned int *__restrict__ bits, Grid g, int64_t nw, const int64_t *__restrict__ prefix,
+__global__ void __launch_bounds__(256) enumerate_kernel(const unsigned int *__restrict__ bits, BitGrid g, int64_t nw, const int64_t *__restrict__ prefix,
                                                        const int64_t *__restrict__ totals, int64_t mv, int64_t *__restrict__ vox, int *__restrict__ parent,
                                                        int *__restrict__ size, int64_t *__restrict__ voxel_ids) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -190,36 +163,8 @@ __global__ void __launch_bounds__(256) enumerate_kernel(const unsigned int *__re
     }
 }
 
-// parent[] is shared between every workgroup of the link launch: every access is an agent-scope atomic (no L1, coherent across the XCDs)
-__device__ __forceinline__ int load_parent(int *parent, int i) { return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of i, halving the path on the way (a non-root's parent is only ever replaced by another of its ancestors, and a non-root never becomes a
-// root again, so these stores cannot undo a hook)
-__device__ __forceinline__ int find_root(int *parent, int i) {
-    int p = load_parent(parent, i);
-    while (p != i) {                                                 // parent[i] < i for every non-root: the walk strictly descends
-        const int gp = load_parent(parent, p);
-        if (gp != p) __hip_atomic_store(parent + i, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-// hook the larger root under the smaller; a failed CAS means another lane has hooked that root meanwhile: find again from there
-__device__ __forceinline__ void unite(int *parent, int a, int b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }                // a > b
-        const int old = atomicCAS(parent + a, a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__global__ void __launch_bounds__(256) link_kernel(const unsigned int *__restrict__ bits, Grid g, const int64_t *__restrict__ prefix,
+// the union-find over the ranks: map_dev.h
+__global__ void __launch_bounds__(256) link_kernel(const unsigned int *__restrict__ bits, BitGrid g, const int64_t *__restrict__ prefix,
                                                   const int64_t *__restrict__ totals, int64_t mv, const int64_t *__restrict__ vox, Offsets offs,
                                                   int *parent) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -271,8 +216,7 @@ __global__ void __launch_bounds__(256) roots_kernel(const int *__restrict__ pare
     const bool live = i < total;
     int r = -1;
     if (live) {
-        r = (int)i;
-        for (int p = parent[r]; p != r; p = parent[r]) r = p;
+        r = settled_root(parent, (int)i);
         root[i] = r;
     }
     const int lane = threadIdx.x & 63;
@@ -292,7 +236,7 @@ __global__ void __launch_bounds__(256) flag_kernel(const int *__restrict__ root,
 
 // per voxel: its cluster's row; per kept cluster: count and coordinate sums (integer atomics: exact, whatever the order)
 __global__ void __launch_bounds__(256) rows_kernel(const int64_t *__restrict__ vox, const int *__restrict__ root, const int64_t *__restrict__ flag,
-                                                  const int64_t *__restrict__ row, const int64_t *__restrict__ totals, int64_t mv, int64_t mc, Grid g,
+                                                  const int64_t *__restrict__ row, const int64_t *__restrict__ totals, int64_t mv, int64_t mc, BitGrid g,
                                                   int64_t *__restrict__ sums, double *__restrict__ clusters, int64_t *__restrict__ cluster_counts,
                                                   int *__restrict__ voxel_cluster) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -390,16 +334,14 @@ __global__ void __launch_bounds__(64) match_kernel(const double *__restrict__ cl
     if (lane == 0) detected[c] = found;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, 256); }
-
 }  // namespace
 }  // namespace mnf
 
 using namespace mnf;
 
 extern "C" int64_t mnf_object_map_bytes(int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z) {
-    Grid g;
-    if (!make_grid(n_classes, res_x, res_y, res_z, &g)) return 0;
+    BitGrid g;
+    if (!make_bit_grid(n_classes, res_x, res_y, res_z, &g)) return 0;
     return g.wpp * n_classes * (int64_t)sizeof(uint32_t);
 }
 
@@ -407,10 +349,10 @@ extern "C" int mnf_object_map_insert(uint32_t *bits, int32_t n_classes, int32_t 
                                      float voxel_size, int32_t first_class, const float *origins, const float *viewdirs, const float *depth,
                                      const float *acc, const float *sem, const void *labels, int32_t label_is_u8, int64_t n_rays,
                                      float min_depth, float max_depth, float min_acc, mnf_stream_t stream) {
-    Grid g;
+    BitGrid g;
     MNF_REQUIRE(n_classes > 0, "object_map_insert: n_classes must be positive (got %d)", n_classes);
     MNF_REQUIRE(res_x > 0 && res_y > 0 && res_z > 0, "object_map_insert: resolution must be positive (got %d x %d x %d)", res_x, res_y, res_z);
-    MNF_REQUIRE(make_grid(n_classes, res_x, res_y, res_z, &g), "object_map_insert: resolution %d x %d x %d with %d classes is more than the map indexes",
+    MNF_REQUIRE(make_bit_grid(n_classes, res_x, res_y, res_z, &g), "object_map_insert: resolution %d x %d x %d with %d classes is more than the map indexes",
                 res_x, res_y, res_z, n_classes);
     MNF_REQUIRE(voxel_size > 0.0f && voxel_size - voxel_size == 0.0f, "object_map_insert: voxel_size must be positive and finite (got %g)", (double)voxel_size);
     MNF_REQUIRE(first_class >= 0 && first_class < n_classes, "object_map_insert: first_class (%d) outside [0, %d)", first_class, n_classes);
@@ -421,7 +363,7 @@ extern "C" int mnf_object_map_insert(uint32_t *bits, int32_t n_classes, int32_t 
     MNF_REQUIRE(min_depth == min_depth && max_depth == max_depth && min_acc == min_acc, "object_map_insert: min_depth, max_depth or min_acc is NaN");
     if (n_rays == 0) return MNF_OK;
     MNF_REQUIRE(bits, "object_map_insert: bits is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(bits) & 7) == 0, "object_map_insert: bits must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(bits), "object_map_insert: bits must be 8-byte aligned");
     MNF_REQUIRE(origins, "object_map_insert: origins is null");
     MNF_REQUIRE(viewdirs, "object_map_insert: viewdirs is null");
     MNF_REQUIRE(depth, "object_map_insert: depth is null");
@@ -447,8 +389,8 @@ extern "C" int mnf_object_map_insert(uint32_t *bits, int32_t n_classes, int32_t 
 
 extern "C" int mnf_object_map_count(const uint32_t *bits, int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z, int64_t *counts,
                                     mnf_stream_t stream) {
-    Grid g;
-    MNF_REQUIRE(make_grid(n_classes, res_x, res_y, res_z, &g), "object_map_count: bad geometry (%d classes, resolution %d x %d x %d)", n_classes, res_x, res_y,
+    BitGrid g;
+    MNF_REQUIRE(make_bit_grid(n_classes, res_x, res_y, res_z, &g), "object_map_count: bad geometry (%d classes, resolution %d x %d x %d)", n_classes, res_x, res_y,
                 res_z);
     MNF_REQUIRE(bits, "object_map_count: bits is null");
     MNF_REQUIRE(counts, "object_map_count: counts is null");
@@ -460,8 +402,8 @@ extern "C" int mnf_object_map_count(const uint32_t *bits, int32_t n_classes, int
 }
 
 extern "C" int64_t mnf_object_map_clusters_workspace_bytes(int32_t n_classes, int32_t res_x, int32_t res_y, int32_t res_z, int64_t max_voxels) {
-    Grid g;
-    if (!make_grid(n_classes, res_x, res_y, res_z, &g) || max_voxels < 0 || max_voxels > 0x7fffffff) return 0;
+    BitGrid g;
+    if (!make_bit_grid(n_classes, res_x, res_y, res_z, &g) || max_voxels < 0 || max_voxels > 0x7fffffff) return 0;
     return carve(nullptr, g, n_classes, max_voxels).bytes;
 }
 
@@ -469,10 +411,10 @@ extern "C" int mnf_object_map_clusters(const uint32_t *bits, int32_t n_classes, 
                                        float voxel_size, int32_t link_r2, int32_t min_cluster_voxels, int64_t max_voxels, int64_t max_clusters,
                                        double *clusters, int64_t *cluster_counts, int64_t *info, int64_t *voxel_ids, int32_t *voxel_cluster,
                                        void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
-    Grid g;
+    BitGrid g;
     MNF_REQUIRE(n_classes > 0, "object_map_clusters: n_classes must be positive (got %d)", n_classes);
     MNF_REQUIRE(res_x > 0 && res_y > 0 && res_z > 0, "object_map_clusters: resolution must be positive (got %d x %d x %d)", res_x, res_y, res_z);
-    MNF_REQUIRE(make_grid(n_classes, res_x, res_y, res_z, &g), "object_map_clusters: resolution %d x %d x %d with %d classes is more than the map indexes",
+    MNF_REQUIRE(make_bit_grid(n_classes, res_x, res_y, res_z, &g), "object_map_clusters: resolution %d x %d x %d with %d classes is more than the map indexes",
                 res_x, res_y, res_z, n_classes);
     MNF_REQUIRE(voxel_size > 0.0f && voxel_size - voxel_size == 0.0f, "object_map_clusters: voxel_size must be positive and finite (got %g)", (double)voxel_size);
     MNF_REQUIRE(link_r2 >= 1 && link_r2 <= 8, "object_map_clusters: link_r2 must lie in 1 .. 8 (got %d)", link_r2);
@@ -485,7 +427,7 @@ extern "C" int mnf_object_map_clusters(const uint32_t *bits, int32_t n_classes, 
     MNF_REQUIRE(cluster_counts, "object_map_clusters: cluster_counts is null");
     MNF_REQUIRE(info, "object_map_clusters: info is null");
     MNF_REQUIRE(workspace, "object_map_clusters: workspace is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "object_map_clusters: workspace must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(workspace), "object_map_clusters: workspace must be 8-byte aligned");
     const ClusterWs w = carve(workspace, g, n_classes, max_voxels);
     MNF_REQUIRE(workspace_bytes >= w.bytes, "object_map_clusters: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes);
     Offsets offs;

@@ -268,7 +268,7 @@ OccWs carve_occ(char *base, int64_t cells, bool fused) {
     return w;
 }
 
-inline int blocks_for(int64_t n, int threads, int cap = 4096) {
+inline int blocks_capped(int64_t n, int threads, int cap = 4096) {
     const int64_t b = (n + threads - 1) / threads;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
@@ -286,9 +286,9 @@ int sample_cells(const float *occs, const uint32_t *bitgrid, int32_t rx, int32_t
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step = step;
     a.idx_in = idx_in; a.jitter_in = jitter_in; a.n_in = n_in;
     a.idx_out = idx_out; a.pts_out = pts_out; a.owner = w.owner; a.cap = cap;
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks_for(cells, 256)), dim3(256), 0, s, w.owner, cells, -1);
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks_capped(cells, 256)), dim3(256), 0, s, w.owner, cells, -1);
     if (!idx_in && !a.warm) hipLaunchKernelGGL(occ_prefix_kernel, dim3(1), dim3(1024), 0, s, bitgrid, a.n_words, w.prefix);
-    hipLaunchKernelGGL(occ_sample_kernel, dim3(blocks_for(cap, 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(occ_sample_kernel, dim3(blocks_capped(cap, 256)), dim3(256), 0, s, a);
     return launch_status("occ_sample_kernel");
 }
 
@@ -309,7 +309,7 @@ extern "C" int64_t mnf_occ_list_capacity(int64_t cells_per_level, int32_t step, 
 extern "C" int mnf_pack_bitgrid(const uint8_t *binaries, int64_t cells_per_level, int32_t levels, uint32_t *bitgrid, mnf_stream_t stream) {
     MNF_REQUIRE(binaries && bitgrid && cells_per_level > 0 && levels > 0, "pack_bitgrid: bad arguments");
     const int words = (int)((cells_per_level + 31) / 32);
-    hipLaunchKernelGGL(pack_bits_kernel, dim3(blocks_for(words, 256), levels), dim3(256), 0, as_stream(stream), binaries, cells_per_level, words, bitgrid);
+    hipLaunchKernelGGL(pack_bits_kernel, dim3(blocks_capped(words, 256), levels), dim3(256), 0, as_stream(stream), binaries, cells_per_level, words, bitgrid);
     return launch_status("pack_bits_kernel");
 }
 
@@ -342,7 +342,7 @@ extern "C" int mnf_occ_apply(float *occs, const int64_t *cell_idx, const float *
     MNF_REQUIRE(occs && cell_idx && values && workspace && n > 0 && cells_per_level > 0, "occ_apply: bad arguments");
     const OccWs w = carve_occ((char *)workspace, cells_per_level, false);
     if (workspace_bytes < w.bytes) { set_error("occ_apply: workspace too small"); return MNF_ERR_WORKSPACE; }
-    hipLaunchKernelGGL(occ_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), occs, cell_idx, values, value_scale, n, ema_decay,
+    hipLaunchKernelGGL(occ_apply_kernel, dim3(blocks_capped(n, 256)), dim3(256), 0, as_stream(stream), occs, cell_idx, values, value_scale, n, ema_decay,
                        w.owner);
     return launch_status("occ_apply_kernel");
 }
@@ -355,7 +355,7 @@ extern "C" int mnf_occ_binarize(const float *occs, int64_t cells_per_level, int3
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(occ_reduce_kernel, dim3(kReduceBlocks), dim3(256), 0, s, occs, cells_per_level * levels, w.part_sum, w.part_cnt);
     const int words = (int)((cells_per_level + 31) / 32);
-    hipLaunchKernelGGL(occ_binarize_kernel, dim3(blocks_for((cells_per_level + 2047) / 2048, 4, 1024), levels), dim3(256), 0, s, occs,
+    hipLaunchKernelGGL(occ_binarize_kernel, dim3(blocks_capped((cells_per_level + 2047) / 2048, 4, 1024), levels), dim3(256), 0, s, occs,
                        cells_per_level, levels, occ_thre, w.part_sum, w.part_cnt, binaries, bitgrid, words, threshold_out);
     return launch_status("occ_binarize_kernel");
 }
@@ -379,12 +379,12 @@ extern "C" int mnf_update_occupancy(mnf_field_t f, float *occs, uint8_t *binarie
     io.mode = 0; io.positions = w.pts; io.n = cap; io.density = w.vals;
     rc = launch_field(f, io, true, s);                              // occ_eval_fn: query_density(x) * render_step_size (pipeline.py:376-378)
     if (rc) return rc;
-    hipLaunchKernelGGL(occ_apply_kernel, dim3(blocks_for(cap, 256)), dim3(256), 0, s, occs, w.idx, w.vals, density_scale, cap, ema_decay, w.owner);
+    hipLaunchKernelGGL(occ_apply_kernel, dim3(blocks_capped(cap, 256)), dim3(256), 0, s, occs, w.idx, w.vals, density_scale, cap, ema_decay, w.owner);
     rc = launch_status("occ_apply_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(occ_reduce_kernel, dim3(kReduceBlocks), dim3(256), 0, s, occs, cells, w.part_sum, w.part_cnt);
     const int words = (int)((cells + 31) / 32);
-    hipLaunchKernelGGL(occ_binarize_kernel, dim3(blocks_for((cells + 2047) / 2048, 4, 1024), 1), dim3(256), 0, s, occs, cells, 1, occ_thre,
+    hipLaunchKernelGGL(occ_binarize_kernel, dim3(blocks_capped((cells + 2047) / 2048, 4, 1024), 1), dim3(256), 0, s, occs, cells, 1, occ_thre,
                        w.part_sum, w.part_cnt, binaries, bitgrid, words, (float *)nullptr);
     return launch_status("occ_binarize_kernel");
 }

@@ -21,19 +21,15 @@
 // for a shared GPU against a logic error that would never end, after nx ny sweeps whatever happens (info = -1 then).
 //
 // path_trace_kernel: one lane per goal walks the field in global memory (at most 160 KB per field: L2 hits) by the rule of the header.
-#include "common.h"
+#include "map_dev.h"
 
 namespace mnf {
 namespace {
 
 constexpr int kFieldThreads = 1024;
-constexpr int64_t kMaxBorderedCells = 40000;          // (nx + 2)(ny + 2): 160 000 B of LDS, and a + b <= nx ny - 1 < 2^16
-constexpr uint32_t kUnreached = 0xFFFFFFFFu;
-constexpr uint32_t kNoEntry = 0xFFFFFFFEu;            // LDS only: blocked or beyond the limits
+constexpr uint32_t kNoEntry = 0xFFFFFFFEu;            // LDS only: blocked or beyond the limits (kUnreached and the cap: map_dev.h)
 constexpr uint32_t kStraight = 0x10000u, kDiagonal = 1u;
 constexpr int kEmptyLo = 0x7fffffff;                 // an empty box: lo = kEmptyLo, hi = -1
-
-inline bool geometry_ok(int32_t nx, int32_t ny) { return nx > 0 && ny > 0 && ((int64_t)nx + 2) * ((int64_t)ny + 2) <= kMaxBorderedCells; }
 
 // exact: is a_p + b_p sqrt(2) < a_q + b_q sqrt(2)?  Where the signs of da and db agree, that sign; otherwise da^2 against 2 db^2.  The two "not
 // reached" labels need no case of their own: both halves of 0xFFFFFFFF and 0xFFFFFFFE exceed those of any label a field holds (a, b <= nx ny - 1 <
@@ -176,14 +172,14 @@ __global__ void __launch_bounds__(256) path_trace_kernel(const uint32_t *__restr
 using namespace mnf;
 
 extern "C" int64_t mnf_path_field_bytes(int32_t nx, int32_t ny, int32_t n_sources) {
-    if (!geometry_ok(nx, ny) || n_sources < 0) return 0;
+    if (!planner_geometry_ok(nx, ny) || n_sources < 0) return 0;
     return (int64_t)nx * ny * n_sources * (int64_t)sizeof(uint32_t);
 }
 
 extern "C" int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx, int32_t ny, int32_t lim_x, int32_t lim_y, const int32_t *sources,
                               int32_t n_sources, uint32_t *field, int64_t *info, mnf_stream_t stream) {
     MNF_REQUIRE(nx > 0 && ny > 0, "path_field: the map size must be positive (got %d x %d)", nx, ny);
-    MNF_REQUIRE(geometry_ok(nx, ny), "path_field: a %d x %d map is more than the %lld bordered cells one workgroup's LDS holds", nx, ny,
+    MNF_REQUIRE(planner_geometry_ok(nx, ny), "path_field: a %d x %d map is more than the %lld bordered cells one workgroup's LDS holds", nx, ny,
                 (long long)kMaxBorderedCells);
     MNF_REQUIRE(lim_x >= 0 && lim_x <= nx && lim_y >= 0 && lim_y <= ny, "path_field: limits %d x %d outside [0, %d] x [0, %d]", lim_x, lim_y, nx, ny);
     MNF_REQUIRE(n_sources >= 0, "path_field: n_sources is negative (%d)", n_sources);
@@ -192,7 +188,7 @@ extern "C" int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx
     MNF_REQUIRE(sources || n_sources == 0, "path_field: sources is null");
     MNF_REQUIRE(field || n_sources == 0, "path_field: field is null");
     MNF_REQUIRE(info || n_sources == 0, "path_field: info is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(info) & 7) == 0, "path_field: info must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(info), "path_field: info must be 8-byte aligned");
     if (n_sources == 0) return MNF_OK;
     const int lds = (nx + 2) * (ny + 2) * (int)sizeof(uint32_t);
     MNF_HIP(hipFuncSetAttribute((const void *)path_field_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxBorderedCells * 4));
@@ -206,13 +202,13 @@ extern "C" int mnf_path_field(const int32_t *blocked, int32_t n_maps, int32_t nx
 extern "C" int mnf_path_trace(const uint32_t *field, int32_t n_fields, int32_t nx, int32_t ny, const int32_t *goals, const int64_t *offsets, int64_t n_goals,
                               int32_t *paths, int64_t *info, mnf_stream_t stream) {
     MNF_REQUIRE(nx > 0 && ny > 0, "path_trace: the map size must be positive (got %d x %d)", nx, ny);
-    MNF_REQUIRE(geometry_ok(nx, ny), "path_trace: a %d x %d map is more than mnf_path_field makes fields of", nx, ny);
+    MNF_REQUIRE(planner_geometry_ok(nx, ny), "path_trace: a %d x %d map is more than mnf_path_field makes fields of", nx, ny);
     MNF_REQUIRE(n_fields >= 0, "path_trace: n_fields is negative (%d)", n_fields);
     MNF_REQUIRE(n_goals >= 0, "path_trace: n_goals is negative (%lld)", (long long)n_goals);
     MNF_REQUIRE(n_goals <= (int64_t)0x7fffffff * 256, "path_trace: n_goals is more than one launch holds (%lld)", (long long)n_goals);
     MNF_REQUIRE(info, "path_trace: info is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(info) & 7) == 0, "path_trace: info must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(offsets) & 7) == 0, "path_trace: offsets must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(info), "path_trace: info must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(offsets), "path_trace: offsets must be 8-byte aligned");
     MNF_REQUIRE(field || n_fields == 0, "path_trace: field is null");
     MNF_REQUIRE(goals || n_goals == 0, "path_trace: goals is null");
     MNF_REQUIRE(offsets || n_goals == 0, "path_trace: offsets is null");

@@ -19,24 +19,19 @@
 // No floating-point value is ever accumulated; every atomic is an integer max or add, so the result does not depend on the schedule.
 //
 // goal_map_kernel: one workgroup.  The minimum visit count over free cells (integer), vm from the caller's decay table, and the goal list by an
-// ordered prefix sum over tiles of 1024 cells (ballot ranks within a wave, wave totals through LDS): row-major order, the same bytes every time.
-#include "common.h"
+// ordered compaction over tiles of 1024 cells (map_dev.h: block_rank): row-major order, the same bytes every time.
+#include "map_dev.h"
 
 #include <cmath>
 
 namespace mnf {
 namespace {
 
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / 64;
-constexpr int64_t kMaxBorderedCells = 40000;          // the planner's cap (planning.hip): (nx + 2)(nz + 2)
+constexpr int kScanThreads = 1024;                    // the cap (nx + 2)(nz + 2) <= kMaxBorderedCells and kUnreached are the planner's: map_dev.h
 constexpr int32_t kFar = 1 << 30;                     // an end cell or centre beyond +-kFar is not drawn
 constexpr int32_t kMaxBeams = 1 << 24;                // keys 2 j + 2 stay far below 2^32
 constexpr int32_t kMaxViews = 1 << 20;                // view keys 2 (v + 1) + 1 likewise
-constexpr uint32_t kUnreached = 0xFFFFFFFFu;
 constexpr double kTwoPi = 2.0 * 3.141592653589793;    // 2 * np.pi
-
-inline bool geometry_ok(int32_t nx, int32_t nz) { return nx > 0 && nz > 0 && ((int64_t)nx + 2) * ((int64_t)nz + 2) <= kMaxBorderedCells; }
 
 // numpy's float remainder for a positive divisor: fmod, then the divisor's sign
 __device__ __forceinline__ double py_mod_pos(double a, double b) {
@@ -135,10 +130,8 @@ __global__ void __launch_bounds__(kScanThreads) goal_map_kernel(const int32_t *_
                                                                 int n_decay, double *__restrict__ vm, int32_t *__restrict__ cells_out,
                                                                 int64_t *__restrict__ count) {
     __shared__ int least;
-    __shared__ int wave_total[kScanWaves];
-    __shared__ int base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cells = nx * nz;
-    if (tid == 0) { least = 0x7fffffff; base = 0; }
+    const int tid = threadIdx.x, lane = tid & 63, cells = nx * nz;
+    if (tid == 0) least = 0x7fffffff;
     __syncthreads();
     int mine = 0x7fffffff;
     for (int i = tid; i < cells; i += kScanThreads)
@@ -148,6 +141,7 @@ __global__ void __launch_bounds__(kScanThreads) goal_map_kernel(const int32_t *_
     if (lane == 0 && mine != 0x7fffffff) atomicMin(&least, mine);
     __syncthreads();
     const int lo = least;
+    int n = 0;                                                                                    // the cells listed so far (uniform)
     for (int t0 = 0; t0 < cells; t0 += kScanThreads) {
         const int i = t0 + tid;
         bool keep = false;
@@ -160,21 +154,14 @@ __global__ void __launch_bounds__(kScanThreads) goal_map_kernel(const int32_t *_
             vm[i] = val;
             keep = val >= 0.0 && (field == nullptr || field[i] != kUnreached);                    // :298, and the goals planning() answers
         }
-        const unsigned long long votes = __ballot(keep);
-        const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_total[wave] = __popcll(votes);
-        __syncthreads();
-        int before = base, total = 0;
-        for (int w = 0; w < kScanWaves; ++w) { const int t = wave_total[w]; if (w < wave) before += t; total += t; }
+        int total;
+        const int pos = n + block_rank<kScanThreads>(keep, &total);
         if (keep) {
-            const int x = i / nz, pos = before + rank;
+            const int x = i / nz;
             cells_out[2 * pos] = x; cells_out[2 * pos + 1] = i - x * nz;
         }
-        __syncthreads();
-        if (tid == 0) base += total;
-        __syncthreads();
+        n += total;
     }
-    const int n = base;
     for (int i = n + tid; i < cells; i += kScanThreads) { cells_out[2 * i] = -1; cells_out[2 * i + 1] = -1; }
     if (tid == 0) count[0] = n;
 }
@@ -194,15 +181,13 @@ __global__ void __launch_bounds__(256) goal_pick_kernel(const int32_t *__restric
     goals[2 * i] = gx; goals[2 * i + 1] = gy;
 }
 
-inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 }  // namespace
 }  // namespace mnf
 
 using namespace mnf;
 
 extern "C" int64_t mnf_scan_map_bytes(int32_t nx, int32_t nz) {
-    if (!geometry_ok(nx, nz)) return 0;
+    if (!planner_geometry_ok(nx, nz)) return 0;
     return 3 * (int64_t)nx * nz * (int64_t)sizeof(int32_t);
 }
 
@@ -210,7 +195,7 @@ extern "C" int mnf_scan_map_update(void *state, int32_t nx, int32_t nz, const fl
                                    const double *align, const double *yaw, const double *loc, const int32_t *centre, const double *aabb_host,
                                    double res, int64_t *info, mnf_stream_t stream) {
     MNF_REQUIRE(nx > 0 && nz > 0, "scan_map_update: the grid size must be positive (got %d x %d)", nx, nz);
-    MNF_REQUIRE(geometry_ok(nx, nz), "scan_map_update: a %d x %d grid is more than the %lld bordered cells one workgroup's LDS holds", nx, nz,
+    MNF_REQUIRE(planner_geometry_ok(nx, nz), "scan_map_update: a %d x %d grid is more than the %lld bordered cells one workgroup's LDS holds", nx, nz,
                 (long long)kMaxBorderedCells);
     MNF_REQUIRE(n_views >= 0 && n_views <= kMaxViews, "scan_map_update: n_views outside [0, %d] (got %d)", kMaxViews, n_views);
     MNF_REQUIRE(height > 0, "scan_map_update: height must be positive (got %d)", height);
@@ -246,7 +231,7 @@ extern "C" int mnf_scan_map_update(void *state, int32_t nx, int32_t nz, const fl
 extern "C" int mnf_planner_goal_map(const int32_t *blocked, const int32_t *visits, const uint32_t *field, int32_t nx, int32_t nz, const double *decay,
                                     int32_t n_decay, double *vm, int32_t *cells, int64_t *count, mnf_stream_t stream) {
     MNF_REQUIRE(nx > 0 && nz > 0, "planner_goal_map: the map size must be positive (got %d x %d)", nx, nz);
-    MNF_REQUIRE(geometry_ok(nx, nz), "planner_goal_map: a %d x %d map is beyond the planner's cap of %lld bordered cells", nx, nz,
+    MNF_REQUIRE(planner_geometry_ok(nx, nz), "planner_goal_map: a %d x %d map is beyond the planner's cap of %lld bordered cells", nx, nz,
                 (long long)kMaxBorderedCells);
     MNF_REQUIRE(n_decay >= 1, "planner_goal_map: n_decay must be at least 1 (got %d)", n_decay);
     MNF_REQUIRE(blocked, "planner_goal_map: blocked is null");

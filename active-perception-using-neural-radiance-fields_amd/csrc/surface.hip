@@ -23,12 +23,12 @@
 // values from HBM and 4 B of words written in the count pass, 4 B of words read in the emit pass; everything else is per vertex or per
 // triangle.  The case table (which edges make the triangles of a tetrahedron, already oriented) is built at compile time from the
 // rule of the header and sits in constant memory.
-#include "common.h"
+#include "workspace.h"
 
 namespace mnf {
 namespace {
 
-constexpr int kThreads = 256;                        // = 1 << kBlockShift
+constexpr int kThreads = 256;                        // = 1 << kBlockShift, and what blocks_for counts in
 constexpr int kBlockShift = 8;
 constexpr int kMaxCells = 1024;                      // per axis: 1025^3 lattice points < 2^31
 
@@ -41,10 +41,6 @@ inline bool make_lattice(int32_t X, int32_t Y, int32_t Z, Lattice *l) {
     *l = {X + 1, Y + 1, Z + 1, sx, sy, (int)n, 1.0f / (float)sx, 1.0f / (float)sy};
     return true;
 }
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, kThreads); }
-inline int64_t scan_bytes(int64_t n) { return mnf_scan_workspace_bytes(n > 0 ? n : 1); }
-inline int64_t align8(int64_t b) { return (b + 7) & ~(int64_t)7; }
 
 // ---------------------------------------------------------------------------------------------------------------- the case table
 // A cube corner is the 3-bit number dx | dy << 1 | dz << 2.  Edge type t runs along the corner kTypeCorner[t]: (1,0,0), (0,1,0), (0,0,1),
@@ -454,32 +450,30 @@ __global__ void __launch_bounds__(kThreads) surface_attrs_kernel(const float *__
 struct ExtractWs { unsigned *words; int64_t *vblock, *tblock, *vbase, *tbase, *totals, *scan; int64_t bytes; };
 
 inline ExtractWs carve_extract(void *base, int64_t n, int64_t nb) {
-    char *p = (char *)base;
-    auto take = [&](int64_t bytes) { char *q = p; p += align8(bytes); return q; };
+    Carver c(base, 8);
     ExtractWs w;
-    w.words = (unsigned *)take(n * 4);
-    w.vblock = (int64_t *)take(nb * 8);
-    w.tblock = (int64_t *)take(nb * 8);
-    w.vbase = (int64_t *)take(nb * 8);
-    w.tbase = (int64_t *)take(nb * 8);
-    w.totals = (int64_t *)take(16);
-    w.scan = (int64_t *)take(scan_bytes(nb));
-    w.bytes = (int64_t)(p - (char *)base);
+    w.words = c.take<unsigned>(n);
+    w.vblock = c.take<int64_t>(nb);
+    w.tblock = c.take<int64_t>(nb);
+    w.vbase = c.take<int64_t>(nb);
+    w.tbase = c.take<int64_t>(nb);
+    w.totals = c.take<int64_t>(2);
+    w.scan = (int64_t *)c.take(scan_bytes(nb));
+    w.bytes = c.bytes();
     return w;
 }
 
 struct PointsWs { uint8_t *near; int64_t *pblock, *pbase, *total, *scan; int64_t bytes; };
 
 inline PointsWs carve_points(void *base, int64_t cells, int64_t nb) {
-    char *p = (char *)base;
-    auto take = [&](int64_t bytes) { char *q = p; p += align8(bytes); return q; };
+    Carver c(base, 8);
     PointsWs w;
-    w.near = (uint8_t *)take(cells);
-    w.pblock = (int64_t *)take(nb * 8);
-    w.pbase = (int64_t *)take(nb * 8);
-    w.total = (int64_t *)take(8);
-    w.scan = (int64_t *)take(scan_bytes(nb));
-    w.bytes = (int64_t)(p - (char *)base);
+    w.near = c.take<uint8_t>(cells);
+    w.pblock = c.take<int64_t>(nb);
+    w.pbase = c.take<int64_t>(nb);
+    w.total = c.take<int64_t>(1);
+    w.scan = (int64_t *)c.take(scan_bytes(nb));
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -514,9 +508,9 @@ extern "C" int mnf_surface_extract(const float *values, int32_t cells_x, int32_t
     MNF_REQUIRE(normals || max_vertices == 0, "surface_extract: normals is null");
     MNF_REQUIRE(triangles || max_triangles == 0, "surface_extract: triangles is null");
     MNF_REQUIRE(info, "surface_extract: info is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(info) & 7) == 0, "surface_extract: info must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(info), "surface_extract: info must be 8-byte aligned");
     MNF_REQUIRE(workspace, "surface_extract: workspace is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface_extract: workspace must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(workspace), "surface_extract: workspace must be 8-byte aligned");
     const int64_t nb = blocks_for(L.n);
     const ExtractWs w = carve_extract(workspace, L.n, nb);
     MNF_REQUIRE(workspace_bytes >= w.bytes, "surface_extract: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes);
@@ -544,7 +538,7 @@ extern "C" int mnf_surface_measure(const float *positions, const int32_t *triang
     MNF_REQUIRE(triangles || max_triangles == 0, "surface_measure: triangles is null");
     MNF_REQUIRE(info, "surface_measure: info is null");
     MNF_REQUIRE(out, "surface_measure: out is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(info) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "surface_measure: info and out must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(info) && aligned8(out), "surface_measure: info and out must be 8-byte aligned");
     hipStream_t s = as_stream(stream);
     ProfScope prof("surface_measure", s);
     MNF_HIP(hipMemsetAsync(out, 0, 2 * sizeof(double), s));
@@ -579,9 +573,9 @@ extern "C" int mnf_surface_lattice_points(const uint8_t *binaries, int32_t res_x
     MNF_REQUIRE(lin || max_points == 0, "surface_lattice_points: lin is null");
     MNF_REQUIRE(positions || max_points == 0, "surface_lattice_points: positions is null");
     MNF_REQUIRE(info, "surface_lattice_points: info is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(info) & 7) == 0, "surface_lattice_points: info must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(info), "surface_lattice_points: info must be 8-byte aligned");
     MNF_REQUIRE(workspace, "surface_lattice_points: workspace is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "surface_lattice_points: workspace must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(workspace), "surface_lattice_points: workspace must be 8-byte aligned");
     const int64_t cells = (int64_t)res_x * res_y * res_z, nb = blocks_for(G.L.n);
     const PointsWs w = carve_points(workspace, cells, nb);
     MNF_REQUIRE(workspace_bytes >= w.bytes, "surface_lattice_points: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)w.bytes);
@@ -606,7 +600,7 @@ extern "C" int mnf_surface_lattice_scatter(const float *density, const int32_t *
     MNF_REQUIRE(density || max_points == 0, "surface_lattice_scatter: density is null");
     MNF_REQUIRE(lin || max_points == 0, "surface_lattice_scatter: lin is null");
     MNF_REQUIRE(point_info, "surface_lattice_scatter: point_info is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(point_info) & 7) == 0, "surface_lattice_scatter: point_info must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(point_info), "surface_lattice_scatter: point_info must be 8-byte aligned");
     MNF_REQUIRE(values, "surface_lattice_scatter: values is null");
     hipStream_t s = as_stream(stream);
     ProfScope prof("surface_lattice_scatter", s);

@@ -3,38 +3,22 @@ a voxel grid (:170), which then says where space has been seen free, seen occupi
 frontier cells of that view (find_frontiers, :52-67), their clusters and the member nearest to the current pose of each (:191-214).  The
 same map gives explored volume per planning step, for the stored depth images (what was observed) or for depths rendered by the field
 (what the model believes).  The definition is in include/mi355nerf.h ("exploration map") and DESIGN.md."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import render as RD
-from .objects import grid_resolution, planar_to_ray_scale
+from .voxelmap import VoxelBitMap
 
 
-class ExplorationMap:
+class ExplorationMap(VoxelBitMap):
     """A persistent bit grid uint32 [2, words] over the voxels of `aabb`: plane 0 "a ray passed through", plane 1 "a ray ended here".
     Inserts accumulate over the steps of a run and do not depend on the order of the pixels.  Depths beyond `max_range` (and +inf)
     carve free space out to `max_range` and mark nothing occupied."""
 
     def __init__(self, aabb, voxel_size=0.1, max_range=10.0, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.MnfError("ExplorationMap lives on a GPU; there is no CPU fallback")
-        self.voxel_size = float(np.float32(voxel_size))
+        super().__init__(aabb, voxel_size, 2, lambda res: L.load_library().mnf_explore_map_bytes(*res), device)
         self.max_range = float(np.float32(max_range))
-        self.resolution = grid_resolution(aabb, voxel_size)
-        self.grid_min = np.asarray(aabb, np.float64).reshape(6)[:3].astype(np.float32)
-        self._gmin = (ctypes.c_float * 3)(*[float(v) for v in self.grid_min])
-        nbytes = int(L.load_library().mnf_explore_map_bytes(*self.resolution))
-        if nbytes <= 0:
-            raise ValueError(f"{self.resolution} voxels are more than the map indexes")
-        self.words_per_plane = nbytes // 8
-        self.bits = torch.zeros(2, self.words_per_plane, dtype=torch.int32, device=self.device)          # uint32 words
-
-    def clear(self):
-        self.bits.zero_()
 
     # ------------------------------------------------------------------ insert
     @torch.no_grad()
@@ -43,16 +27,7 @@ class ExplorationMap:
         tensors, one launch, no host copy, no synchronisation.  A pixel is skipped when its depth is NaN or <= min_depth, acc < min_acc,
         or its ray is not finite.  `stats`: an int64 device tensor [2] to which {voxel steps, atomic ORs} are added (measurements)."""
         L.require_gpu(rays_o, rays_d, depth, acc, stats)
-        o, d = L.contig(rays_o.reshape(-1, 3), torch.float32), L.contig(rays_d.reshape(-1, 3), torch.float32)
-        dep = L.contig(depth.reshape(-1), torch.float32)
-        n = int(dep.shape[0])
-        if int(o.shape[0]) != n or int(d.shape[0]) != n:
-            raise ValueError(f"{int(o.shape[0])} origins and {int(d.shape[0])} directions for {n} depths")
-        a = None
-        if acc is not None:
-            a = L.contig(acc.reshape(-1), torch.float32)
-            if int(a.shape[0]) != n:
-                raise ValueError(f"{int(a.shape[0])} acc values for {n} depths")
+        o, d, dep, a, n = self._flat_rays(rays_o, rays_d, depth, acc)
         if stats is not None and (stats.dtype != torch.int64 or stats.numel() != 2 or not stats.is_contiguous()):
             raise TypeError("stats is a contiguous int64 tensor of two elements")
         L.launch(L.load_library().mnf_explore_map_insert, L.ptr(self.bits), *self.resolution, self._gmin, self.voxel_size, self.max_range, L.ptr(o),
@@ -64,10 +39,7 @@ class ExplorationMap:
         """The map of what the field believes: `poses` are rendered exactly as `SemanticObjectMap.insert_views` renders them (the same
         rays, the same `render_views` call, background zeros) and the finished depth and acc planes go straight into `insert` with the
         rays that made them.  Returns the render's dict of device tensors."""
-        poses = np.asarray(poses)
-        o, d, h, w = RD._pose_rays(poses, width, height, focal, scale, self.device)
-        r = RD.render_views(radiance_field, estimator, o, d, h * w, 1024, near_plane=near_plane, render_step_size=render_step_size,
-                            render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, image_hw=(h, w), n_split=None)
+        o, d, r = self._render_poses(radiance_field, estimator, poses, width, height, focal, near_plane, render_step_size, scale, cone_angle, alpha_thre)
         self.insert(o, d, r["depth"], acc=r["acc"], **insert_kw)
         return r
 
@@ -76,18 +48,9 @@ class ExplorationMap:
         """The map of what was observed (the reference's own use): the stored depth images of views `image_ids` of a `Dataset`, either
         storage layout, with rays from `generate_image_rays` on the dataset's poses and K.  `depth_along` as in
         `SemanticObjectMap.insert_dataset`: "z" turns Habitat's planar depth into the ray length, "ray" takes it as stored."""
-        if depth_along not in ("z", "ray"):
-            raise ValueError('depth_along is "z" or "ray"')
-        ids = RD._eval_index_tensor(image_ids, self.device, len(dataset), "image_ids")
-        if int(ids.shape[0]) == 0:
-            return
-        L.require_gpu(dataset.depths, dataset.camtoworlds)
-        H, W = int(dataset.height), int(dataset.width)
-        rays = RD.generate_image_rays(dataset.camtoworlds[ids], W, H, dataset.K, self.device)
-        depth = dataset.depths[ids].reshape(-1, H * W).to(torch.float32)
-        if depth_along == "z":
-            depth = depth * planar_to_ray_scale(W, H, float(dataset.K[0, 0]), self.device)[None]
-        self.insert(rays.origins, rays.viewdirs, depth, **insert_kw)
+        got = self._dataset_rays(dataset, image_ids, depth_along)
+        if got is not None:
+            self.insert(got[1].origins, got[1].viewdirs, got[2], **insert_kw)
 
     # ------------------------------------------------------------------ read-outs
     @torch.no_grad()

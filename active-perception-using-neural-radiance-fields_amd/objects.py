@@ -5,48 +5,24 @@ ground-truth object positions (:45-70), which gives the "objects detected over p
 Voxels are linked on INTEGER offsets (dx^2 + dy^2 + dz^2 <= link_r2, default 4 = the reference's eps of two voxels), so the clusters
 are the connected components of that graph: DBSCAN(eps=sqrt(link_r2), min_samples=1) on the integer coordinates, deterministic and
 bit-reproducible (DESIGN.md, "Semantic object map")."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import render as RD
+from .voxelmap import VoxelBitMap, grid_resolution, planar_to_ray_scale  # noqa: F401  (both functions are part of this module's interface)
 
 
-def grid_resolution(aabb, voxel_size):
-    """Voxels per axis that cover `aabb` = (x0, y0, z0, x1, y1, z1) at `voxel_size`: ceil of the float64 quotient (a box that is a
-    whole number of voxels up to 1e-9 of a voxel gets exactly that many)."""
-    a = np.asarray(aabb, np.float64).reshape(6)
-    n = np.ceil((a[3:] - a[:3]) / float(voxel_size) - 1e-9).astype(np.int64)
-    if (n < 1).any():
-        raise ValueError(f"aabb {a.tolist()} is empty along an axis")
-    return tuple(int(v) for v in n)
-
-
-class SemanticObjectMap:
+class SemanticObjectMap(VoxelBitMap):
     """A persistent bit grid uint32 [C, words] over the voxels of `aabb` (include/mi355nerf.h: mnf_object_map_*).  Inserts accumulate,
     as the reference's grids do over the steps of a run; classes below `first_class` are never inserted (the reference skips label 0)."""
 
     def __init__(self, aabb, voxel_size=0.1, num_classes=29, first_class=1, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.MnfError("SemanticObjectMap lives on a GPU; there is no CPU fallback")
-        self.voxel_size = float(np.float32(voxel_size))
         self.num_classes, self.first_class = int(num_classes), int(first_class)
-        self.resolution = grid_resolution(aabb, voxel_size)
-        self.grid_min = np.asarray(aabb, np.float64).reshape(6)[:3].astype(np.float32)
         if not 0 <= self.first_class < self.num_classes:
             raise ValueError(f"first_class {first_class} outside [0, {num_classes})")
-        self._gmin = (ctypes.c_float * 3)(*[float(v) for v in self.grid_min])
-        nbytes = int(L.load_library().mnf_object_map_bytes(self.num_classes, *self.resolution))
-        if nbytes <= 0:
-            raise ValueError(f"{self.num_classes} classes of {self.resolution} voxels are more than the map indexes")
-        self.words_per_plane = nbytes // (4 * self.num_classes)
-        self.bits = torch.zeros(self.num_classes, self.words_per_plane, dtype=torch.int32, device=self.device)     # uint32 words
-
-    def clear(self):
-        self.bits.zero_()
+        super().__init__(aabb, voxel_size, self.num_classes, lambda res: L.load_library().mnf_object_map_bytes(self.num_classes, *res), device,
+                         what=f"{self.num_classes} classes of ")
 
     # ------------------------------------------------------------------ insert
     @torch.no_grad()
@@ -58,16 +34,7 @@ class SemanticObjectMap:
         if (sem is None) == (labels is None):
             raise ValueError("insert takes exactly one of sem (logits) and labels")
         L.require_gpu(rays_o, rays_d, depth, sem, labels, acc)
-        o, d = L.contig(rays_o.reshape(-1, 3), torch.float32), L.contig(rays_d.reshape(-1, 3), torch.float32)
-        dep = L.contig(depth.reshape(-1), torch.float32)
-        n = int(dep.shape[0])
-        if int(o.shape[0]) != n or int(d.shape[0]) != n:
-            raise ValueError(f"{int(o.shape[0])} origins and {int(d.shape[0])} directions for {n} depths")
-        a = None
-        if acc is not None:
-            a = L.contig(acc.reshape(-1), torch.float32)
-            if int(a.shape[0]) != n:
-                raise ValueError(f"{int(a.shape[0])} acc values for {n} depths")
+        o, d, dep, a, n = self._flat_rays(rays_o, rays_d, depth, acc)
         s = lab = None
         if sem is not None:
             if int(sem.shape[-1]) != self.num_classes:
@@ -91,10 +58,7 @@ class SemanticObjectMap:
         """The map of what the field believes: `poses` are rendered exactly as `render_image_from_pose` renders them (the same rays, the
         same `render_views` call, background zeros) and the finished device planes go straight into `insert` with the rays that made
         them.  Returns the render's dict of device tensors."""
-        poses = np.asarray(poses)
-        o, d, h, w = RD._pose_rays(poses, width, height, focal, scale, self.device)
-        r = RD.render_views(radiance_field, estimator, o, d, h * w, 1024, near_plane=near_plane, render_step_size=render_step_size,
-                            render_bkgd=torch.zeros(3), cone_angle=cone_angle, alpha_thre=alpha_thre, image_hw=(h, w), n_split=None)
+        o, d, r = self._render_poses(radiance_field, estimator, poses, width, height, focal, near_plane, render_step_size, scale, cone_angle, alpha_thre)
         self.insert(o, d, r["depth"], sem=r["sem"], acc=r["acc"], **insert_kw)
         return r
 
@@ -104,17 +68,11 @@ class SemanticObjectMap:
         of a `Dataset`, either storage layout, with rays from `generate_image_rays` on the dataset's poses and K.  `depth_along="z"`:
         the stored depth is Habitat's planar depth and the ray length is z * |cam|, cam = ((x - W/2 + 0.5) / f, (y - H/2 + 0.5) / f, 1)
         the camera-space direction of the pixel before normalisation; `"ray"`: the stored depth is the ray length."""
-        if depth_along not in ("z", "ray"):
-            raise ValueError('depth_along is "z" or "ray"')
-        ids = RD._eval_index_tensor(image_ids, self.device, len(dataset), "image_ids")
-        if int(ids.shape[0]) == 0:
+        got = self._dataset_rays(dataset, image_ids, depth_along)
+        if got is None:
             return
-        L.require_gpu(dataset.depths, dataset.semantics, dataset.camtoworlds)
-        H, W = int(dataset.height), int(dataset.width)
-        rays = RD.generate_image_rays(dataset.camtoworlds[ids], W, H, dataset.K, self.device)
-        depth = dataset.depths[ids].reshape(-1, H * W).to(torch.float32)
-        if depth_along == "z":
-            depth = depth * planar_to_ray_scale(W, H, float(dataset.K[0, 0]), self.device)[None]
+        ids, rays, depth = got
+        L.require_gpu(dataset.semantics)
         self.insert(rays.origins, rays.viewdirs, depth, labels=dataset.semantics[ids], **insert_kw)
 
     # ------------------------------------------------------------------ read-outs
@@ -201,12 +159,3 @@ class SemanticObjectMap:
         res["match"] = match[:len(res["class"])].cpu().numpy()
         res["gt_match"] = gt_match.cpu().numpy()
         return res
-
-
-def planar_to_ray_scale(width, height, focal, device):
-    """|cam| per pixel, row-major [H*W] float32 on `device`: the factor that turns a planar (z) depth into the length along the pixel's
-    normalised ray, cam = ((x - W/2 + 0.5) / f, (y - H/2 + 0.5) / f, 1)."""
-    f = float(np.float32(focal))
-    x = (torch.arange(width, device=device, dtype=torch.float32) - width / 2 + 0.5) / f
-    y = (torch.arange(height, device=device, dtype=torch.float32) - height / 2 + 0.5) / f
-    return torch.sqrt(x[None, :] * x[None, :] + y[:, None] * y[:, None] + 1.0).reshape(-1)

@@ -65,6 +65,11 @@ def test_byte_functions(lib):
     assert ws(16, 16, 100, 10) < ws(16, 16, 100, 20) and ws(16, 16, 100, 10) < ws(16, 32, 100, 10)
     for bad in [(0, 4, 10, 10), (4, 0, 10, 10), (4, 4, -1, 10), (4, 4, 10, -1), (-4, 4, 10, 10)]:
         assert ws(*bad) == 0, bad
+    # the layout, byte for byte: no capacity, counts that need padding to 8 bytes, a realistic map
+    pinned = {(16, 16, 0, 0): 1048, (16, 16, 100, 10): 3568, (16, 16, 1000, 10): 25168, (7, 9, 0, 0): 280, (7, 9, 33, 5): 1144, (7, 9, 33, 0): 1080,
+              (1, 1, 1, 1): 80, (196, 196, 38416, 38416): 1536808, (196, 196, 5001, 333): 277736}
+    for args, want in pinned.items():
+        assert ws(*args) == want, args
 
 
 GMIN = (ctypes.c_float * 3)(0.0, 0.0, 0.0)

@@ -304,9 +304,9 @@ def test_capacities_hit_exactly_and_exceeded():
     assert finfo.tolist() == [F, 1] and cinfo.tolist() == [0, 0]
 
 
-@pytest.mark.parametrize("shape", [(40, 33), (1, 1), (1, 70), (70, 1), (33, 32)])
+@pytest.mark.parametrize("shape", [(40, 33), (1, 1), (1, 70), (70, 1), (33, 32), (32, 32)])
 def test_frontiers_across_batches_and_shapes(shape):
-    """40 x 33 = 1320 cells: more than one batch of the ordered compaction; degenerate maps; and every eps2."""
+    """40 x 33 = 1320 cells: more than one batch of the ordered compaction; 32 x 32: exactly one full batch; degenerate maps; and every eps2."""
     grid = ER.seeded_map2d(99, shape, (0.2, 0.6, 0.2))
     F = int(ER.frontiers(grid)[2][0])
     for eps2 in range(1, 9):

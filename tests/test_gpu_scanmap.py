@@ -319,7 +319,7 @@ def _walled_map(shape, seed):
     return blocked, visits
 
 
-@pytest.mark.parametrize("shape", [(1, 1), (5, 4), (33, 31), (98, 98), (198, 198)])
+@pytest.mark.parametrize("shape", [(1, 1), (5, 4), (33, 31), (32, 32), (98, 98), (198, 198)])       # 32 x 32: exactly one full tile of the compaction
 def test_goal_map_without_a_field(shape):
     rng = np.random.default_rng(shape[0])
     blocked = (rng.random(shape) < 0.4).astype(np.int32) * rng.integers(1, 3, shape).astype(np.int32)

@@ -60,6 +60,11 @@ def test_byte_functions(lib):
     assert ws(5, 16, 8, 16, 100) < ws(6, 16, 8, 16, 100) < ws(6, 32, 8, 16, 100)
     for bad in [(0, 4, 4, 4, 10), (2, 0, 4, 4, 10), (2, 4, 4, 4, -1), (2, 4, 4, -4, 10)]:
         assert ws(*bad) == 0, bad
+    # the layout, byte for byte: no capacity, counts that need padding to 8 bytes, a realistic map
+    pinned = {(5, 16, 8, 16, 0): 5152, (5, 16, 8, 16, 100): 11952, (5, 16, 8, 16, 1000): 73152, (5, 7, 5, 9, 0): 832, (5, 7, 5, 9, 33): 3088,
+              (3, 3, 3, 3, 7): 616, (1, 1, 1, 1, 1): 144, (29, 196, 34, 196, 50001): 22344280}
+    for args, want in pinned.items():
+        assert ws(*args) == want, args
 
 
 GMIN = (ctypes.c_float * 3)(0.0, 0.0, 0.0)

@@ -29,6 +29,22 @@ def meshes():
     return get
 
 
+def test_workspace_byte_functions():
+    """The two workspace layouts of the device unit (csrc/surface.hip), byte for byte; the functions need no GPU."""
+    import __graft_entry__ as G
+    import apnrf_amd
+    G.build()
+    lib = apnrf_amd.load_library()
+    # a single cell, word counts that need padding to 8 bytes, a realistic lattice, the cap
+    extract = {(1, 1, 1): 96, (2, 2, 2): 176, (16, 12, 10): 10080, (6, 4, 10): 1640, (196, 34, 196): 5603104, (1024, 1024, 1024): 4442190328}
+    for cells, want in extract.items():
+        assert lib.mnf_surface_extract_workspace_bytes(*cells) == want, cells
+    points = {(1, 1, 1, 1): 48, (4, 3, 5, 2): 136, (3, 3, 3, 1): 72, (7, 5, 9, 4): 1768, (128, 128, 128, 1): 2231384, (196, 34, 196, 2): 1972392}
+    for args, want in points.items():
+        assert lib.mnf_surface_lattice_points_workspace_bytes(*args) == want, args
+    assert lib.mnf_surface_extract_workspace_bytes(0, 1, 1) == 0 and lib.mnf_surface_lattice_points_workspace_bytes(4, 3, 5, 3) == 0
+
+
 def _closed(m):
     return len(SR.boundary_edges(m["triangles"])) == 0
 

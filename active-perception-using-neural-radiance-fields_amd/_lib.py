@@ -223,6 +223,13 @@ SIGNATURES = {
                                              c_int64, c_void_p]),
     "mnf_surface_lattice_scatter": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "mnf_surface_vertex_attrs": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_cloud_sample_triangles_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "mnf_cloud_sample_triangles": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_void_p]),
+    "mnf_cloud_nearest_workspace_bytes": (c_int64, [c_int64, c_int64, POINTER(c_float), c_float]),
+    "mnf_cloud_nearest": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_float, POINTER(c_float), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_cloud_distance_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
 }
 
 

@@ -53,6 +53,11 @@ class SurfaceMesh:
         area, volume = (float(v) for v in self.measure_device().cpu().numpy())
         return {"area": area, "volume": volume}
 
+    def quality(self, gt_points, **kw):
+        """`cloud.mesh_quality(self, gt_points, ...)`: accuracy, completion, F-score and class confusion against a ground-truth cloud."""
+        from . import cloud
+        return cloud.mesh_quality(self, gt_points, **kw)
+
     def cpu(self):
         """The same mesh on the host."""
         return SurfaceMesh(*[None if t is None else t.cpu() for t in (self.positions, self.normals, self.triangles, self.info, self.colour, self.label,

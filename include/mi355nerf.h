@@ -1126,6 +1126,67 @@ int mnf_surface_lattice_scatter(const float *density, const int32_t *lin, const 
 int mnf_surface_vertex_attrs(const float *rgb, const float *sem, int64_t n, int32_t n_classes, const uint8_t *palette, uint8_t *colour,
                              int32_t *label, uint8_t *sem_colour, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- mesh quality */
+
+/* How good the map is as geometry: the surface mesh above against a ground-truth cloud such as simulator/build_point_cloud_from_mesh.py
+ * writes.  Three parts: points sampled on triangles (1), the nearest neighbour of every point of one cloud in another within a radius (2), the
+ * reduction of the distances to what accuracy, completion, precision, recall and a class confusion matrix are made of (3).
+ *
+ * 1. mnf_cloud_sample_triangles: the sampling of build_point_cloud_from_mesh.py:47-83.
+ * Input: positions [V,3] f32, triangles [T,3] int32 (V, T < 2^31), res > 0 (float64).  Per triangle (p1, p2, p3), widened to float64, every
+ * operation rounded on its own, |e| = sqrt((e_x e_x + e_y e_y) + e_z e_z):
+ *   the three vertices p1, p2, p3 as they are;
+ *   d1 = |p2 - p1|, n1 = (p2 - p1) / d1, d2 = |p3 - p1|, n2 = (p3 - p1) / d2;
+ *   for k = 0 .. count(d1 / res) - 1, i = (double)k * res:  b = ((d1 - i) * d2) / d1;
+ *     for l = 0 .. count(b / res) - 1, j = (double)l * res:  the point (p1 + i * n1) + j * n2, per component.
+ * count(x) = ceil(x) for x > 0, else 0 (numpy's arange), and it saturates at 2^31.  A triangle with d1 == 0, d2 == 0 or a vertex that is not
+ * finite gives its three vertices only; a triangle with an index outside [0, V) gives nothing.
+ * ROWS.  The work is laid out by row: row 0 of a triangle is its three vertices, row 1 + k the k-th pass of the outer loop; a triangle has 0
+ * (bad index), 1 (vertices only) or 1 + count(d1 / res) rows.  The caller gives the row capacity `max_rows` (< 2^31) the workspace is sized for.
+ * Outputs, in ascending (triangle, row, l): points [max_points,3] f32 = the double rounded to float32, face [max_points] int32 = the triangle
+ * the point came from, info [2] int64 = {points, points - max_points if positive else 0}.  Point r is written iff r < max_points; nothing is
+ * written past the capacity; max_points = 0 (points and face may be NULL) makes a counting call.  When the triangles have more rows than
+ * max_rows the points cannot be counted: nothing is written and info = {-1, rows}; call again with max_rows >= rows (max_rows = 0 asks for
+ * just that).  A mesh in which a count saturates has more than 2^31 - 1 points, which no capacity admits (max_points < 2^31): info[0] is then a
+ * lower bound and info[1] > 0.
+ * workspace: mnf_cloud_sample_triangles_workspace_bytes(T, max_rows) bytes (0 for a refused size; 16 B per triangle, 20 B per row and the
+ * scan's own), 8-byte aligned.
+ *
+ * 2. mnf_cloud_nearest.  query [n,3], target [m,3] f32 (n, m < 2^31), r_max >= 2^-60 with a finite float32 square (so that r_max * r_max
+ * is a normal float32 and no rounding of d2 is worse than relative), box six host floats (min, max).
+ * In float32, every operation rounded on its own: d2(q, t) = ((q_x - t_x)^2 + (q_y - t_y)^2) + (q_z - t_z)^2.  Per query:
+ *   index [n] int32 = the target with the smallest d2 among those with d2 <= r_max * r_max, the lowest index on a tie; -1 when there is none
+ *     or the query has a coordinate that is not finite.  A target with a coordinate that is not finite never matches.
+ *   dist [n] f32 = sqrtf(d2) of that target, r_max where index is -1.
+ * The result is the brute-force answer over all n m pairs, whatever the box: the box only places the cell list the search uses (cell edge
+ * max(r_max (1 + 2^-10), widest box side / 128), at most 128 cells per axis; a point outside the box falls into the border cell next to it).
+ * A box that hugs the targets is the fast one.
+ * workspace: mnf_cloud_nearest_workspace_bytes(n, m, box, r_max) bytes (0 for refused arguments; 20 B per target, 12 B per query, 32 B per cell
+ * and the scan's own), 16-byte aligned.
+ *
+ * 3. mnf_cloud_distance_stats.  dist, index [n] as (2) wrote them against m targets, query [n,3] or NULL, 0 <= thr <= r_max, and for the confusion
+ * matrix query_label [n], target_label [m] int32 and n_classes = C in 1 .. 1024.  A query COUNTS when it is finite (every query when `query` is
+ * NULL); it is FOUND when it counts and 0 <= index < m; it is WITHIN when it is found and dist <= thr.
+ *   counts [3] int64 = {counting, found, within};
+ *   sums [2] float64 = {sum of dist over the counting ones (an unmatched one adds the r_max that (2) wrote), sum of dist over the found ones},
+ *     each dist widened to float64; the order of the sums is not specified;
+ *   confusion [C,C] int64 or NULL: confusion[a][b] = the WITHIN queries with query_label = a and target_label[index] = b, both in [0, C).
+ *
+ * Argument errors (a null required pointer, a count outside [0, 2^31), a res, r_max or thr outside its range, a box that is not finite or has
+ * max < min, n_classes outside 1 .. 1024, an info, counts, sums, confusion or workspace that is misaligned, a workspace that is too small)
+ * return MNF_ERR_INVALID before any HIP call.  Profile labels: "cloud_sample_triangles", "cloud_nearest", "cloud_distance_stats".  Every call
+ * enqueues on `stream` and none synchronises. */
+int64_t mnf_cloud_sample_triangles_workspace_bytes(int64_t n_triangles, int64_t max_rows);
+int mnf_cloud_sample_triangles(const float *positions, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles, double res, int64_t max_rows,
+                               int64_t max_points, float *points, int32_t *face, int64_t *info, void *workspace, int64_t workspace_bytes,
+                               mnf_stream_t stream);
+int64_t mnf_cloud_nearest_workspace_bytes(int64_t n, int64_t m, const float *box_host, float r_max);
+int mnf_cloud_nearest(const float *query, int64_t n, const float *target, int64_t m, float r_max, const float *box_host, int32_t *index, float *dist,
+                      void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+int mnf_cloud_distance_stats(const float *dist, const int32_t *index, const float *query, int64_t n, float thr, float r_max, const int32_t *query_label,
+                             const int32_t *target_label, int64_t m, int32_t n_classes, int64_t *counts, double *sums, int64_t *confusion,
+                             mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

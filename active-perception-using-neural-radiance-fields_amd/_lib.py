@@ -230,6 +230,13 @@ SIGNATURES = {
     "mnf_cloud_nearest": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_float, POINTER(c_float), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mnf_cloud_distance_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    "mnf_clearance_field": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mnf_clearance_lookup": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_double), c_double, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "mnf_voxel_walk_count": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mnf_voxel_walk_fill": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mnf_voxel_walk_hits": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                      c_void_p, c_void_p]),
 }
 
 

@@ -1187,6 +1187,68 @@ int mnf_cloud_distance_stats(const float *dist, const int32_t *index, const floa
                              const int32_t *target_label, int64_t m, int32_t n_classes, int64_t *counts, double *sums, int64_t *confusion,
                              mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- trajectory clearance */
+
+/* How far a trajectory stays from what the map calls occupied: the exact squared distance field of the members' occupancy grids (1), samples
+ * looked up in it (2), and the reference's voxel walk between two points (3).  Grids are [X][Y][Z], lin = (x Y + y) Z + z, the estimator's
+ * layout; 1 <= X, Y, Z <= 2048 and the voxel count within the bit grids' bound (< 2^31 - 64).  LEVEL 0 of the estimator only.
+ *
+ * 1. mnf_clearance_field.  binaries [n_members][X][Y][Z] uint8 as mnf_planner_map takes them (non-zero = occupied).
+ *   d2 [X][Y][Z] int32 = the squared Euclidean distance, in voxels, from each voxel to the nearest voxel occupied in ANY member: 0 on an
+ *     occupied voxel, INT32_MAX everywhere when no member holds a voxel.  Integers throughout: the brute-force answer, the same bytes every time.
+ *   info [2] int64 = {occupied voxels of the union, the largest finite d2 or -1}; the call sets both itself.
+ * Three passes, along z, y and x, in place in d2: there is no workspace.
+ *
+ * 2. mnf_clearance_lookup.  points [n_points,3] float64 in the grid's axis order, trajectory t = points offsets[t] .. offsets[t+1]-1
+ * (offsets [n_traj+1] int64, ascending from 0 to n_points; an offset outside [0, n_points] is clamped, so nothing outside the arrays is
+ * touched).  origin_host three host doubles (aabb[:3]), voxel > 0.
+ *   The voxel of a point is numpy's  (p_k - origin_k) // voxel  in float64, cast to int: q = fmod-exact floor division, that is
+ *     mod = fmod(a, b); div = (a - mod) / b; if (mod != 0 and (b < 0) != (mod < 0)) div -= 1;
+ *     q = div == 0 ? copysign(0, a / b) : (f = floor(div), div - f > 0.5 ? f + 1 : f)
+ *   (1.0 // 0.2 is 4, not 5).  A quotient beyond +-2^30 is clamped there; one that is not finite gives INT32_MIN.
+ *   cells [n_points,3] int32; point_d2 [n_points] int32 = d2 of the voxel, -1 for a voxel outside the grid or a point that is not finite.
+ *   traj [n_traj,4] int64 = {the least point_d2 over the samples inside or -1, the index within the trajectory of the FIRST sample that
+ *     attains it or -1, samples outside (the non-finite ones included), samples}.  The minimum is taken over integer keys
+ *     (d2 << 32 | index): the same whatever the schedule.
+ *   info [2] int64 += {samples outside, samples not finite}: the caller clears it.
+ * Points that no trajectory covers are not looked at.  n_traj == 0 is a no-op.
+ *
+ * 3. mnf_voxel_walk_*: planning/planning_funcs.py:97-159, get_voxels_between_points(start_pos, end_pos, current_voxel, end_voxel,
+ * voxel_size), every statement in float64 / int32 as numpy evaluates it.  start, end [n,3] float64; current_voxel, end_voxel [n,3] int32:
+ * four separate arguments, as the function takes them, so a caller that mixes frames (collision_checker does) gets the reference's answer.
+ *   step_k = ray_k >= 0 ? +1 : -1, ray = end - start;  next_k = (current_k + step_k) * voxel_size;
+ *   t_max_k = (next_k - start_k) / ray_k, t_delta_k = voxel_size / ray_k * step_k, both inf where ray_k == 0;
+ *   range_sq = dist(end_voxel), dist(v) = ((a + b) + c) of the squares of (v_k - current_k) * voxel_size;
+ *   while dist(voxel) <= range_sq: step along x if t_max_x < t_max_y and t_max_x < t_max_z; along z if t_max_x < t_max_y otherwise; along y
+ *   if t_max_y < t_max_z; else along z; add t_delta to that t_max; LIST the voxel.
+ * So the start voxel is not listed, the walk overshoots the end voxel and may leave the grid, a negative direction crosses the far face
+ * of the previous voxel first, and a zero-length ray takes one step in +z.  These are the reference's and are kept.
+ * Every walk is bounded: one that would list more than max_steps (0 .. 2^31 - 1) voxels is cut there, and one with a start or end that is
+ * not finite has length 0.  info [3] int64 += {walks cut, walks not finite, slots that did not match (fill only)}: the caller clears it.
+ *   mnf_voxel_walk_count: counts [n] int64.
+ *   mnf_voxel_walk_fill: voxels [total,3] int32, walk w at rows offsets[w] .. offsets[w+1]-1 (offsets [n+1] int64, the exclusive sum of the
+ *     counts).  Nothing is written outside a walk's slot or outside [0, total); a walk whose length is not its slot is counted in info[2].
+ *   mnf_voxel_walk_hits: hits [n,5] int32 = {position in the list of the first voxel occupied in any of the n_members grids or -1, that
+ *     voxel's three indices as listed (unclipped; -1 each when there is none), the length of the list}.  Every index is clipped to the grid
+ *     before the look-up, as collision_checker clips (planning_funcs.py:174-178).  No list is built.
+ *
+ * Argument errors (a null required pointer, a size outside the limits, a voxel size that is not positive and finite, an origin that is not
+ * finite, a count or max_steps outside its range, an int64 or float64 array that is misaligned) return MNF_ERR_INVALID before any HIP call.
+ * n == 0 is a no-op.  Profile labels: "clearance_field", "clearance_lookup", "voxel_walk_count", "voxel_walk_fill", "voxel_walk_hits".  Every
+ * call enqueues on `stream` and none synchronises.  There is no CPU fallback. */
+int mnf_clearance_field(const uint8_t *binaries, int32_t n_members, int32_t X, int32_t Y, int32_t Z, int32_t *d2, int64_t *info, mnf_stream_t stream);
+int mnf_clearance_lookup(const int32_t *d2, int32_t X, int32_t Y, int32_t Z, const double *origin_host, double voxel, const double *points,
+                         int64_t n_points, const int64_t *offsets, int64_t n_traj, int32_t *cells, int32_t *point_d2, int64_t *traj, int64_t *info,
+                         mnf_stream_t stream);
+int mnf_voxel_walk_count(const double *start, const double *end, const int32_t *current_voxel, const int32_t *end_voxel, int64_t n,
+                         double voxel_size, int64_t max_steps, int64_t *counts, int64_t *info, mnf_stream_t stream);
+int mnf_voxel_walk_fill(const double *start, const double *end, const int32_t *current_voxel, const int32_t *end_voxel, int64_t n,
+                        double voxel_size, int64_t max_steps, const int64_t *offsets, int64_t total, int32_t *voxels, int64_t *info,
+                        mnf_stream_t stream);
+int mnf_voxel_walk_hits(const double *start, const double *end, const int32_t *current_voxel, const int32_t *end_voxel, int64_t n,
+                        double voxel_size, int64_t max_steps, const uint8_t *binaries, int32_t n_members, int32_t X, int32_t Y, int32_t Z,
+                        int32_t *hits, int64_t *info, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

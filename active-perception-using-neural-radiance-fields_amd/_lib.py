@@ -237,6 +237,13 @@ SIGNATURES = {
     "mnf_voxel_walk_fill": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mnf_voxel_walk_hits": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                       c_void_p, c_void_p]),
+    "mnf_minsnap_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "mnf_minsnap_solve": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, POINTER(c_double), c_double, c_double, c_double, c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_minsnap_sample_count": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_int64, c_void_p]),
+    "mnf_minsnap_sample_fill": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                          c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

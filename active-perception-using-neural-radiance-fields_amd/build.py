@@ -51,6 +51,7 @@ SOURCES = {
     "surface.hip": ["-ffp-contract=off"],   # a vertex is a chain of separately rounded float32 operations (numpy restates it)
     "cloud.hip": ["-ffp-contract=off"],     # a sampled point is a chain of separately rounded float64 operations, a squared distance of float32 ones
     "clearance.hip": ["-ffp-contract=off"], # a voxel index and a step of the voxel walk are chains of separately rounded float64 operations (numpy restates them)
+    "minsnap.hip": ["-ffp-contract=off"],   # the time allocation and the sample times are chains of separately rounded float64 operations (numpy restates them)
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
     "inputgrad.hip@bf16": ["-DMNF_BF16"],

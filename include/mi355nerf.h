@@ -1249,6 +1249,88 @@ int mnf_voxel_walk_hits(const double *start, const double *end, const int32_t *c
                         double voxel_size, int64_t max_steps, const uint8_t *binaries, int32_t n_members, int32_t X, int32_t Y, int32_t Z,
                         int32_t *hits, int64_t *info, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- min-snap candidate trajectories */
+
+/* The curve sample_traj (planning/planning_funcs.py:328-397) lays through a traced path, its samples and their view poses: the stretch between
+ * mnf_path_trace and mnf_clearance_lookup.  Everything is float64; the unit is built without FMA contraction.  Motor speeds, moments, cmd_w,
+ * cmd_a and the simulator are not restated: sample_traj uses cmd_q only.
+ *
+ * Trajectory t owns the waypoints offsets[t] .. offsets[t+1]-1 (offsets [n_traj+1] int64, ascending from 0 to n_waypoints; an offset outside
+ * [0, n_waypoints] is clamped).  Every per-segment and per-keyframe output is packed at the SAME offsets: a trajectory of W waypoints has at
+ * most W - 1 segments and W keyframes, so its segments are rows offsets[t] .. offsets[t] + n_segments[t] - 1 and its keyframes one more.  Rows
+ * past those, and every row of a refused trajectory, are left untouched.
+ *
+ * 1. mnf_minsnap_solve <- trajectories/minsnap.py:254-371 (MinSnap.__init__, initialize).  Give `points` [n_waypoints,3] float64, or `cells`
+ * [n_waypoints,2] int32 as mnf_path_trace lists them (goal first) with resolution, origin_host (three host doubles, aabb[:3]) and height: the
+ * cells of a trajectory are reversed and become (cx * resolution + origin[0], cy * resolution + origin[1], height + origin[2]), the
+ * reference's dij_waypoints (planning_funcs.py:328-340); the other of the two pointers is null.  In the reference's order of operations:
+ *   seg_dist[k] = sqrt((dx dx + dy dy) + dz dz) between ALL consecutive waypoints; a waypoint is kept if it is the first or seg_dist > 1e-2;
+ *   m = kept - 1;  total = np.sum(seg_dist) (numpy's pairwise order);  for i < m: cum += seg_dist[i] (the UNMASKED distances, as the
+ *   reference indexes them), vf = min(min(cum, v_avg), total - cum), delta_t[i] = seg_dist[i] * 2 / (vf + vi + 1e-4), vi = vf;
+ *   t_keyframes = {0, the sequential running sum of delta_t};  yaw_execute = t_keyframes / (t_keyframes[m] + 1e-4) * (yaw1 - yaw0) + yaw0
+ *   (sample_traj's np.linspace(2 pi, 0, n) enters the reference by its two ends only).
+ * The reference solves no QP: its curve is the solution of the square system A c = b of get_1d_equality_constraints (minsnap.py:63-245),
+ * the same A for x, y, z and yaw.  With the three start rows first, then per segment its two position rows and its six continuity rows, then
+ * the three end rows, A has lower and upper bandwidth 4.  The call assembles that band from delta_t (powers by repeated multiplication) and
+ * eliminates it with partial pivoting over the four right-hand sides; factored rows go through `workspace`.
+ *   coeffs [n_waypoints][4][8]: segment row, axis (x, y, z, yaw), power, LOWEST first, as c_opt holds them.
+ *   delta_t, t_keyframes, yaw_execute [n_waypoints];  n_segments [n_traj] int32 = m;  status [n_traj] int32:
+ *     MNF_MINSNAP_OK               a curve was written.
+ *     MNF_MINSNAP_NULL             one waypoint is left (or the trajectory is empty): the reference's `null`.  No curve, no samples.
+ *     MNF_MINSNAP_REJECTED_SHORT   two waypoints are left: the reference's time allocation gives that lone segment 2 d / 1e-4 seconds and
+ *                                  its rank test refuses the system (rank 3 of 8), always.  No curve, no samples.
+ *     MNF_MINSNAP_SINGULAR         a pivot fell below 8 m * eps * |A|_inf, a delta_t was not positive, or a coefficient is not finite.
+ *                                  THIS PROJECT'S criterion: the reference's SVD rank test is not reproduced.  From two segments on every
+ *                                  delta_t of a grid path is bounded and both accept.
+ *     MNF_MINSNAP_TOO_LONG         more than MNF_MINSNAP_MAX_SEGMENTS segments, or more than 4096 waypoints before the mask.
+ *     MNF_MINSNAP_NOT_FINITE       a waypoint is not finite.
+ *
+ * 2. mnf_minsnap_sample_count <- planning_funcs.py:352-370.  For every trajectory with status OK: t_final = np.sum(delta_t),
+ * N = max(int(t_final * rate), min_samples), t_step = t_final / N, and the sample times 0, then t_k = t_{k-1} + t_step as a sequential float64
+ * running sum, the last being the first with t_k >= t_final (N + 1 or N + 2 of them: the sum may fall an ulp short).  counts [n_traj] int64;
+ * the times are left in the workspace, max_samples per trajectory, for the fill.  A trajectory with more than max_samples samples gets count 0
+ * and sample_status MNF_MINSNAP_SAMPLE_OVERFLOW (MNF_MINSNAP_SAMPLE_INVALID for a trajectory record that contradicts itself); a refused
+ * trajectory gets count 0.  sample_status [n_traj] int32.
+ *
+ * 3. mnf_minsnap_sample_fill, with the same workspace, untouched since the count.  sample_offsets [n_traj+1] = the exclusive sum of counts,
+ * n_samples its last entry; pose_offsets [n_traj+1] = the exclusive sum of (count ? count + n_look : 0), n_poses its last entry.  Per sample
+ * <- minsnap.py:386-443 (update): t clipped to the keyframes, the first segment i with t_keyframes[i] + delta_t[i] >= t, Horner as np.polyval,
+ * derivative coefficients by np.polyder's successive integer multiples; quadrotor_control.py:104-124, :177: b3 = normalize(x_ddot + (0, 0,
+ * 9.81)), c1 = (cos yaw, sin yaw, 0), b2 = normalize(b3 x c1), b1 = b2 x b3, the quaternion (x, y, z, w) of R = [b1 b2 b3] by scipy's
+ * largest-of-diagonal-and-trace rule; planning_funcs.py:377-386: from_rotvec(P as_rotvec(q)) in closed form = (-x, z, -y, w) of q with the
+ * sign that makes w >= 0.
+ *   flat_x [n_samples,3] = flat["x"] (the planner's x, y, height);  times [n_samples];
+ *   derivatives [n_samples,12] = x_dot, x_ddot, x_dddot, x_ddddot (or null);  yaw [n_samples,3] = yaw, yaw_dot, yaw_ddot (or null);
+ *   poses [n_poses,7] = (x, height, y) + quaternion per sample, then n_look rows of the LAST sample's position with look_quats [n_look,4], the
+ *   caller's table (planning_funcs.py:391-395).
+ * A trajectory whose two slots do not agree with each other is left untouched; nothing is written outside [0, n_samples) and [0, n_poses).
+ *
+ * mnf_minsnap_workspace_bytes(n_traj, n_waypoints, max_samples): what any of the three calls needs (840 bytes per waypoint for the solve,
+ * 8 n_traj max_samples for the samples, the larger of the two), or -1 for a size outside [0, 2^31).
+ * Argument errors return MNF_ERR_INVALID before any HIP call.  n_traj == 0 is a no-op.  Profile labels: "minsnap_solve",
+ * "minsnap_sample_count", "minsnap_sample_fill".  Every call enqueues on `stream` and none synchronises.  There is no CPU fallback. */
+#define MNF_MINSNAP_MAX_SEGMENTS 1023
+#define MNF_MINSNAP_OK 0
+#define MNF_MINSNAP_NULL 1
+#define MNF_MINSNAP_REJECTED_SHORT 2
+#define MNF_MINSNAP_SINGULAR 4
+#define MNF_MINSNAP_TOO_LONG 8
+#define MNF_MINSNAP_NOT_FINITE 16
+#define MNF_MINSNAP_SAMPLE_OVERFLOW 32
+#define MNF_MINSNAP_SAMPLE_INVALID 64
+int64_t mnf_minsnap_workspace_bytes(int64_t n_traj, int64_t n_waypoints, int64_t max_samples);
+int mnf_minsnap_solve(const double *points, const int32_t *cells, const int64_t *offsets, int64_t n_traj, int64_t n_waypoints, double resolution,
+                      const double *origin_host, double height, double yaw0, double yaw1, double v_avg, double *coeffs, double *delta_t,
+                      double *t_keyframes, double *yaw_execute, int32_t *n_segments, int32_t *status, void *workspace, int64_t workspace_bytes,
+                      mnf_stream_t stream);
+int mnf_minsnap_sample_count(const double *delta_t, const int64_t *offsets, int64_t n_waypoints, const int32_t *n_segments, const int32_t *status,
+                             int64_t n_traj, double rate, int64_t min_samples, int64_t max_samples, int64_t *counts, int32_t *sample_status,
+                             void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+int mnf_minsnap_sample_fill(const double *coeffs, const double *delta_t, const double *t_keyframes, const int64_t *offsets, int64_t n_waypoints,
+                            const int32_t *n_segments, int64_t n_traj, int64_t max_samples, const int64_t *sample_offsets, int64_t n_samples,
+                            const int64_t *pose_offsets, int64_t n_poses, const double *look_quats, int32_t n_look, double *flat_x, double *times,
+                            double *derivatives, double *yaw, double *poses, const void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,12 @@ SIGNATURES = {
                                            c_int64, c_void_p]),
     "mnf_minsnap_sample_fill": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                           c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mnf_sensor_bricks_words": (c_int64, [c_int32, c_int32, c_int32]),
+    "mnf_sensor_build_bricks": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mnf_sensor_cast_rays": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, POINTER(c_double), c_double, c_void_p, c_void_p, c_int64, c_double,
+                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_sensor_views": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, POINTER(c_double), c_double, c_void_p, c_int32, c_int32, c_int32, c_double,
+                                   c_double, c_double, c_int32, POINTER(ctypes.c_uint8), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

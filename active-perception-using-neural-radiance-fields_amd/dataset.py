@@ -46,18 +46,21 @@ class Dataset(torch.utils.data.Dataset):
 
     def update_data(self, images, depths, semantics, camtoworlds):
         """habitat_to_data.py:89-153 (uint8 images [N,H,W,C], f32 depths, int64 semantics, f32 poses, on device)."""
-        img_np = np.asarray(images)
-        if img_np.ndim != 4 or img_np.shape[-1] != 3:
-            # the pixel gather reads 3 bytes per pixel (mnf_gather_pixels); an RGBA capture (Habitat's colour sensor before pipeline.py's
-            # [..., :3] slice) would be read with the wrong stride and give garbage colours without any error
-            raise ValueError(f"Dataset.update_data expects uint8 images [N,H,W,3] (got shape {tuple(img_np.shape)}): slice RGBA captures with [..., :3]")
-        new_images = torch.from_numpy(img_np).to(torch.uint8).to(self.device)
-        new_depths = torch.from_numpy(np.asarray(depths)).to(torch.float16 if self.packed else torch.float32).to(self.device)
-        sem_np = np.asarray(semantics)
-        if self.packed and (sem_np.min() < 0 or sem_np.max() > 255):
-            raise ValueError("packed dataset layout stores class ids as uint8: ids must be in [0, 255]")
-        new_sems = torch.from_numpy(sem_np.astype(np.uint8 if self.packed else np.int64)).to(self.device)
-        new_c2w = torch.from_numpy(np.asarray(camtoworlds)).to(torch.float32).to(self.device)
+        if any(torch.is_tensor(a) for a in (images, depths, semantics, camtoworlds)):
+            new_images, new_depths, new_sems, new_c2w = self._device_captures(images, depths, semantics, camtoworlds)
+        else:
+            img_np = np.asarray(images)
+            if img_np.ndim != 4 or img_np.shape[-1] != 3:
+                # the pixel gather reads 3 bytes per pixel (mnf_gather_pixels); an RGBA capture (Habitat's colour sensor before pipeline.py's
+                # [..., :3] slice) would be read with the wrong stride and give garbage colours without any error
+                raise ValueError(f"Dataset.update_data expects uint8 images [N,H,W,3] (got shape {tuple(img_np.shape)}): slice RGBA captures with [..., :3]")
+            new_images = torch.from_numpy(img_np).to(torch.uint8).to(self.device)
+            new_depths = torch.from_numpy(np.asarray(depths)).to(torch.float16 if self.packed else torch.float32).to(self.device)
+            sem_np = np.asarray(semantics)
+            if self.packed and (sem_np.min() < 0 or sem_np.max() > 255):
+                raise ValueError("packed dataset layout stores class ids as uint8: ids must be in [0, 255]")
+            new_sems = torch.from_numpy(sem_np.astype(np.uint8 if self.packed else np.int64)).to(self.device)
+            new_c2w = torch.from_numpy(np.asarray(camtoworlds)).to(torch.float32).to(self.device)
         for i, arr in enumerate(self.bootstrap_indices):
             ids = np.random.choice(len(images), size=(int(len(images) * self.boot_scale),), replace=True)
             self.bootstrap_indices[i] = np.concatenate([arr, self.size + ids], axis=0)
@@ -74,6 +77,22 @@ class Dataset(torch.utils.data.Dataset):
             self.semantics = torch.cat([self.semantics, new_sems], dim=0)
             self.camtoworlds = torch.cat([self.camtoworlds, new_c2w], dim=0)
         self.size = self.size + len(images)
+
+    def _device_captures(self, images, depths, semantics, camtoworlds):
+        """`update_data` for captures that are torch tensors (the device sensor's, `sensor.VoxelSim`): the same storage as the host route
+        builds, with no host round trip for a tensor that is on the device already.  Arguments that are host arrays go up as they always
+        do.  A uint8 class image needs no range check; any other one is checked on the device (one small read) for the packed layout."""
+        t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+        images, depths, semantics, camtoworlds = t(images), t(depths), t(semantics), t(camtoworlds)
+        if images.dim() != 4 or images.shape[-1] != 3:
+            raise ValueError(f"Dataset.update_data expects uint8 images [N,H,W,3] (got shape {tuple(images.shape)}): slice RGBA captures with [..., :3]")
+        new_images = images.to(torch.uint8).to(self.device).contiguous()               # a [..., :3] slice of an RGBA capture is packed here
+        new_depths = depths.to(self.device).to(torch.float16 if self.packed else torch.float32).contiguous()
+        if self.packed and semantics.dtype != torch.uint8 and semantics.numel() and (int(semantics.min()) < 0 or int(semantics.max()) > 255):
+            raise ValueError("packed dataset layout stores class ids as uint8: ids must be in [0, 255]")
+        new_sems = semantics.to(self.device).to(torch.uint8 if self.packed else torch.int64).contiguous()
+        new_c2w = camtoworlds.to(self.device).to(torch.float32).contiguous()
+        return new_images, new_depths, new_sems, new_c2w
 
     def __len__(self):
         return self.size

@@ -1331,6 +1331,69 @@ int mnf_minsnap_sample_fill(const double *coeffs, const double *delta_t, const d
                             const int64_t *pose_offsets, int64_t n_poses, const double *look_quats, int32_t n_look, double *flat_x, double *times,
                             double *derivatives, double *yaw, double *poses, const void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- scene sensor */
+
+/* What the reference takes from habitat_sim (simulator/sim.py:169-196, HabitatSim.sample_images_from_poses): colour, planar depth and class
+ * images of a ground-truth world at given poses.  The world here is a labelled, coloured voxel grid; one launch renders a batch of poses and
+ * the images stay on the device.  This comment is the definition: every output byte follows from it (tests/sensor_ref.py restates it).
+ *
+ * Scene.  voxels [X][Y][Z] uint32, lin = (x Y + y) Z + z, the estimator's layout.  Bits 0-7, 8-15, 16-23 of a word are r, g, b; bits 24-31
+ * the class; class 0xFF means FREE (the colour bits of a free voxel mean nothing).  The grid's origin lo_host (three host doubles) and the
+ * voxel edge voxel_size (> 0) are host float64.  The brick mask `bricks` holds one bit per 8 x 8 x 8 brick, set where any voxel of the
+ * brick is occupied: a one-plane bit grid over ceil(X/8) x ceil(Y/8) x ceil(Z/8) bricks laid out as every bit grid here (brick
+ * (bx, by, bz) is bit (b & 31) of word b >> 5, b = (bx BY + by) BZ + bz; the word count is rounded up to even).
+ *   mnf_sensor_bricks_words(X, Y, Z): the words of the mask, or -1 for a scene outside the limits.
+ *   mnf_sensor_build_bricks: clears the mask and fills it from voxels, on `stream`.
+ * Limits: those of a bit grid (axes <= 2^24, X Y Z < 2^31 - 64) and a mask of at most 16384 words = 64 KiB, which a workgroup stages in LDS
+ * (524288 bricks: 540 x 84 x 560 voxels take 1638 words).  A caller that edits voxels rebuilds the mask; a mask with a bit missing hides
+ * that brick's voxels, a bit too many costs time only.
+ *
+ * The walk, in float64, every operation rounded separately (the unit is built without FMA contraction).  A ray is o + t d, t >= 0, d NOT
+ * normalised, limited to near <= t <= far (0 <= near <= far, far finite).  With N = (X, Y, Z) and a = 0, 1, 2:
+ *   g_a = (o_a - lo_a) / s,  e_a = d_a / s,  step_a = sign(e_a) (0 for e_a = 0),  inv_a = 1 / e_a.
+ *   A ray with an o_a, d_a, g_a or e_a that is not finite is a MISS and is counted as not finite.
+ *   Box: for step_a != 0, t0_a = ((step_a > 0 ? 0 : N_a) - g_a) inv_a and t1_a the same with the other face; for step_a = 0 the ray misses
+ *   unless 0 <= g_a < N_a.  t_in = near, face 6; then for a = 0, 1, 2: if t0_a > t_in, t_in = t0_a and face = 2 a + (step_a < 0).
+ *   t_out = the least of far and the t1_a.  The ray misses unless t_in <= t_out.
+ *   Start: c_a = clamp(floor(g_a + e_a t_in), 0, N_a - 1), t = t_in.
+ *   Loop: if voxel c is occupied: HIT, t_hit = max(t, t_in), the voxel lin(c), the face as last set.  Otherwise
+ *     f_a = ((c_a + (step_a > 0)) - g_a) inv_a (+inf where step_a = 0); a = the axis of the least f_a, the lowest on a tie (a = 0; if
+ *     f_1 < f_a, a = 1; if f_2 < f_a, a = 2); the ray misses unless f_a <= t_out; c_a += step_a and the ray misses if that leaves the
+ *     grid; t = f_a, face = 2 a + (step_a < 0).
+ * f_a is formed from the integer cell every time and never accumulated: a monotone function of c_a, so the walk cannot drift, and it ends
+ * after at most X + Y + Z steps.  Faces: 0 / 1 the voxel's low / high x face (the ray came in moving towards +x / -x), 2 / 3 for y, 4 / 5
+ * for z, 6 the near plane (the ray started inside the voxel), 255 no hit.
+ *
+ * mnf_sensor_cast_rays.  origins, dirs [n,3] float64 -> t_hit [n] float64 (-1 on a miss), hit [n] int32 (lin or -1), face [n] uint8.
+ *
+ * mnf_sensor_views.  c2w [n_views][3][4] float64 (rotation columns and position), a pinhole camera looking along -z as the dataset's
+ * (habitat_to_data.py:274-301), pixel (x, y) of a width x height image, in the order mnf_generate_rays uses but in float64:
+ *   cam = (((x - width/2) + 0.5) / focal, ((y - height/2) + 0.5) / focal * (-1), -1);  d_i = (cam_0 R_i0 + cam_1 R_i1) + cam_2 R_i2;  o = c2w[:, 3].
+ *   rgba  [n_views][height][width][4] uint8: channel k = (c_k shade[face] + 127) / 255 in integers, alpha 255; shade_host is seven host bytes,
+ *         one per face 0 .. 6.  A miss gets `background` (r in bits 0-7, g 8-15, b 16-23, alpha 24-31).  One 32-bit store per pixel.
+ *   depth [n_views][height][width] float32: MNF_SENSOR_DEPTH_PLANAR: (float)t_hit, since cam_2 = -1 makes t the distance along the
+ *         camera's axis, Habitat's depth; MNF_SENSOR_DEPTH_RAY: (float)(t_hit sqrt((cam_0 cam_0 + cam_1 cam_1) + 1)), the length along the
+ *         normalised ray of the dataset.  0 on a miss.
+ *   sem   [n_views][height][width] uint8: the voxel's class; 0 on a miss.
+ *   hit   [n_views][height][width] int32 or null: lin or -1.
+ * info [2] int64 += {misses (the rays that are not finite included), rays not finite}: the caller clears it (both calls).
+ *
+ * Argument errors (a null required pointer, a scene outside the limits, an origin, voxel size, focal, near or far outside its range, an
+ * image wider or higher than 16384, an unknown depth_mode, a misaligned array) return MNF_ERR_INVALID before any HIP call.  n == 0 and
+ * n_views == 0 are no-ops.  Profile labels: "sensor_build_bricks", "sensor_cast_rays", "sensor_views".  Every call enqueues on `stream` and
+ * none synchronises.  There is no CPU fallback. */
+#define MNF_SENSOR_DEPTH_PLANAR 0
+#define MNF_SENSOR_DEPTH_RAY 1
+int64_t mnf_sensor_bricks_words(int32_t X, int32_t Y, int32_t Z);
+int mnf_sensor_build_bricks(const uint32_t *voxels, int32_t X, int32_t Y, int32_t Z, uint32_t *bricks, mnf_stream_t stream);
+int mnf_sensor_cast_rays(const uint32_t *voxels, int32_t X, int32_t Y, int32_t Z, const uint32_t *bricks, const double *lo_host, double voxel_size,
+                         const double *origins, const double *dirs, int64_t n, double near, double far, double *t_hit, int32_t *hit, uint8_t *face,
+                         int64_t *info, mnf_stream_t stream);
+int mnf_sensor_views(const uint32_t *voxels, int32_t X, int32_t Y, int32_t Z, const uint32_t *bricks, const double *lo_host, double voxel_size,
+                     const double *c2w, int32_t n_views, int32_t width, int32_t height, double focal, double near, double far, int32_t depth_mode,
+                     const uint8_t *shade_host, uint32_t background, uint8_t *rgba, float *depth, uint8_t *sem, int32_t *hit, int64_t *info,
+                     mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,158 @@
+"""The reference's active-mapping loop (scripts/pipeline.py:1025-1224) at small sizes, from public calls only, with the scene sensor in the
+place of habitat_sim: a closed procedural room, 64 x 64 captures, one field, a 2^14 hash table.
+
+  1. the initial yaw sweep at the start pose -> `Dataset.update_data` (device tensors) and `ScanCostMap.update`;
+  2. training on it;
+  3. per planning step: the planner's map from the estimator, `goal_cells` + `draw_goals`, `candidate_trajectories` (grid search, min-snap
+     curves, samples, view poses) with `trajectory_clearance`, `score_views` per candidate and the argmax, captures along the winner,
+     `update_data` and `ScanCostMap.update`, `train_step`s, `evaluate_views` on held-out captures.
+
+One line per planning step.  The whole run is one child process under `timeout`; the driver starts no GPU work itself.  Nothing here is a
+measurement of speed and nothing is asserted: it shows the stages joined end to end on the device.
+
+    python tools/active_loop.py [--steps 3] [--out profiles/active_loop.txt]
+"""
+import argparse
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+DEV = "cuda:0"
+AABB = np.array([-4.0, -0.2, -4.0, 4.0, 2.2, 4.0])                                      # x, y, z: 40 x 12 x 40 cells of 0.2 m, walls every 4 m with doors
+CELL, SIDE = 0.2, 64
+START = np.array([-2.0, 1.0, -2.0])
+KW = dict(near_plane=0.1, render_step_size=5e-3, cone_angle=0.004, alpha_thre=0.01)
+
+
+def run(steps, train_steps, n_goals, seed):
+    import torch
+    from apnrf_amd import clearance as CL
+    from apnrf_amd import nerfacc as NA
+    from apnrf_amd import planning as PL
+    from apnrf_amd import render as RD
+    from apnrf_amd import sensor as SN
+    from apnrf_amd import synthetic as S
+    from apnrf_amd.dataset import Dataset, planner_path_finding_map
+    from apnrf_amd.ngp import NGPRadianceField
+    from apnrf_amd.optim import FusedAdam
+    from apnrf_amd.trajectory import candidate_trajectories
+    rng = np.random.default_rng(seed)
+    torch.manual_seed(seed)
+    res = [int(round((AABB[3 + k] - AABB[k]) / CELL)) for k in range(3)]
+    occ = S.make_occupancy(res, seed=seed, clutter=0.01, aabb=AABB, free_at=[START])
+    world = SN.VoxelScene.from_occupancy(occ, AABB, cell=CELL, refine=2, closed=True, device=DEV)
+    sim = SN.VoxelSim(world, SIDE, SIDE)
+    aabb_xzy = AABB[[0, 2, 1, 3, 5, 4]]
+    aabb32 = torch.from_numpy(AABB.astype(np.float32))
+    field = NGPRadianceField(aabb=aabb32, neurons=128, layers=2, num_semantic_classes=29, log2_hashmap_size=14, seed=seed).to(DEV)
+    est = NA.OccGridEstimator(aabb32, resolution=res, levels=1).to(DEV)
+    opt = FusedAdam(field.parameters(), lr=2e-3, eps=1e-15).bind_field(field)
+    data = Dataset(training=True, save_fp="", num_rays=1024, device=DEV)
+    cost = PL.ScanCostMap(AABB, CELL, device=DEV)
+    c2w_of = lambda poses: torch.from_numpy(np.stack([RD.pose_to_c2w(p) for p in np.asarray(poses, np.float64).reshape(-1, 7)])).to(DEV)
+
+    def capture(poses):
+        """What the reference does with a batch of captures: the dataset takes colour, depth (along the ray, what the field renders) and
+        classes; the cost map takes the planar depth's middle rows."""
+        c2w = c2w_of(poses)
+        rgba, depth_ray, sem = sim.sample_images_from_poses(poses, depth="ray")
+        planar = sim.sample_images_from_poses(poses)[1]
+        data.update_data(rgba[..., :3], depth_ray, sem, c2w)
+        cost.update(planar, c2w)
+        return rgba, depth_ray, sem, c2w
+
+    done = [0]
+
+    def train(n):
+        for _ in range(n):
+            b = data[0]
+            RD.train_step(field, est, opt, b["rays"], b["pixels"], b["dep"], b["sem"], b["color_bkgd"], step=done[0], occ_thre=1e-2, deterministic=True, **KW)
+            done[0] += 1
+
+    # held-out views: a sweep at another place of the start room
+    held = Dataset(training=False, save_fp="", device=DEV)
+    hp = S.camera_poses(START + [0.6, 0.0, 0.5], 4)
+    hr, hd, hs = sim.sample_images_from_poses(hp, depth="ray")
+    held.update_data(hr[..., :3], hd, hs, c2w_of(hp))
+    # 1. + 2.
+    capture(S.camera_poses(START, 12))
+    train(train_steps)
+    ev = RD.evaluate_views(field.eval(), est.eval(), held, [0, 1, 2, 3], **KW)["mean"]
+    print(f"sweep      12 views, {done[0]} train steps: held-out PSNR {ev['psnr']:.2f}, depth MSE {ev['depth_mse']:.4f}; cost map {cost.info()}", flush=True)
+    current = START.copy()
+    focal = sim.focal
+    for step in range(steps):
+        state_xzy = current[[0, 2, 1]]
+        blocked = planner_path_finding_map([est], state_xzy, aabb_xzy, CELL, y_slice=int((current[1] - AABB[1]) / CELL))
+        cx, cz = int((current[0] - AABB[0]) / CELL), int((current[2] - AABB[2]) / CELL)
+        blocked[max(cx - 1, 0):cx + 2, max(cz - 1, 0):cz + 2] = 0                         # the vehicle stands in free space, whatever the field believes so far
+        dij = PL.Dijkstra(aabb_xzy, blocked, CELL, 0.1, device=DEV)
+        start_xy = (float(current[0] - AABB[0]), float(current[2] - AABB[2]))
+        gc = PL.goal_cells(dij.blocked, cost.visits, dij, start_xy)
+        goals = PL.draw_goals(gc["cells"], gc["count"], rng.random(n_goals)).cpu().numpy()
+        goals = goals[(goals >= 0).all(axis=1)]
+        if goals.shape[0] == 0:
+            print(f"step {step}     no free cell is reached from the current pose on the estimator's map: nothing to plan", flush=True)
+            break
+        clear = CL.clearance_field([est], voxel=CELL)
+        cand = candidate_trajectories(dij, start_xy, [(float(g[0]) * CELL, float(g[1]) * CELL) for g in goals], aabb_xzy, height=float(current[1] - AABB[1]),
+                                      clearance=clear, radius=0.1, host=True)
+        if not cand["trajectories"]:
+            print(f"step {step}     every one of the {goals.shape[0]} goals was refused (status {cand['curves'].status.tolist()})", flush=True)
+            break
+        certified = cand["certified"].cpu().numpy()
+        scores = []
+        for traj in cand["trajectories"]:
+            views = traj[np.linspace(0, len(traj) - 1, 6).astype(int)]
+            scores.append(float(RD.score_views([field.eval()], [est.eval()], views, SIDE, SIDE, focal, KW["near_plane"], KW["render_step_size"], 0.25, KW["cone_angle"],
+                                               KW["alpha_thre"], device=DEV, group=False)[1]))
+        best = int(np.argmax(scores))
+        traj = cand["trajectories"][best]
+        views = traj[np.linspace(0, len(traj) - 1, 6).astype(int)]
+        capture(views)
+        current = views[-1][:3].copy()
+        train(train_steps // 2)
+        ev = RD.evaluate_views(field.eval(), est.eval(), held, [0, 1, 2, 3], **KW)["mean"]
+        print(f"step {step}     {goals.shape[0]} goals, {len(cand['trajectories'])} curves ({int(certified.sum())} certified at 0.1 m), scores "
+              f"{min(scores):.3f} .. {max(scores):.3f}, flew curve {cand['kept'][best]} of {len(traj)} poses to ({current[0]:.2f}, {current[1]:.2f}, {current[2]:.2f}); "
+              f"{len(data)} views, {done[0]} train steps: held-out PSNR {ev['psnr']:.2f}, depth MSE {ev['depth_mse']:.4f}; sensor misses {int(sim.info[0])}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--train-steps", type=int, default=200)
+    ap.add_argument("--goals", type=int, default=6)
+    ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", action="store_true", help="(internal) run the loop in this process")
+    a = ap.parse_args()
+    if a.child:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("active_loop needs a GPU")
+        import apnrf_amd  # noqa: F401
+        run(a.steps, a.train_steps, a.goals, a.seed)
+        return
+    r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--child", "--steps", str(a.steps), "--train-steps", str(a.train_steps),
+                        "--goals", str(a.goals), "--seed", str(a.seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    body = [ln for ln in r.stdout.splitlines() if ln.strip() and "amdgpu.ids" not in ln]
+    head = (f"# the active-mapping loop at small sizes: a closed {AABB[3] - AABB[0]:.0f} x {AABB[4] - AABB[1]:.1f} x {AABB[5] - AABB[2]:.0f} m procedural world at 10 cm voxels, "
+            f"{SIDE} x {SIDE} captures, one 128 x 2 field with a 2^14 table; {a.steps} planning steps, seed {a.seed}")
+    text = "\n".join([head] + (body if r.returncode == 0 else body[-25:] + [f"# the loop ended with status {r.returncode}"]))
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    if r.returncode != 0:
+        raise SystemExit(1)
+
+
+if __name__ == "__main__":
+    main()

@@ -37,6 +37,11 @@ class TrainOpts(_Sized):
                 ("presampled", c_void_p)]
 
 
+class PoseOpts(_Sized):
+    _fields_ = [("struct_size", c_uint32), ("w_rgb", c_float), ("w_dep", c_float), ("w_sem", c_float), ("lr_rot", c_double), ("lr_trans", c_double),
+                ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("seed", c_uint64)]
+
+
 class VanillaConfig(_Sized):
     _fields_ = [("struct_size", c_uint32), ("net_depth", c_int32), ("net_width", c_int32), ("skip_layer", c_int32), ("net_depth_condition", c_int32),
                 ("net_width_condition", c_int32)]
@@ -250,6 +255,17 @@ SIGNATURES = {
                                        c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mnf_sensor_views": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, POINTER(c_double), c_double, c_void_p, c_int32, c_int32, c_int32, c_double,
                                    c_double, c_double, c_int32, POINTER(ctypes.c_uint8), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_pose_rays": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p,
+                                c_int32, c_int32, c_int64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_pose_loss": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(PoseOpts), c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_pose_update": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, POINTER(PoseOpts), c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_pose_refine_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_int64]),
+    "mnf_pose_refine_workspace_offset": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_int64, c_int32]),
+    "mnf_pose_refine": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                  c_int64, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                  POINTER(TrainOpts), POINTER(PoseOpts), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 

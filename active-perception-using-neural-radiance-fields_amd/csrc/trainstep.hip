@@ -487,6 +487,12 @@ int sample_stage(const StepCall &c, const SampleWs &w, float *losses, const Step
 }
 
 }  // namespace
+
+// For the pose refiner (localize.hip), which decides per VIEW whether anything was rendered: where a step's workspace keeps every ray's surviving-sample
+// count (visibility_kernel's; zeroed by the guards).  Intact from the forward to behind its backward.
+const int64_t *train_step_kept_counts(void *workspace, mnf_field_t f, int32_t n_rays, int64_t max_marched, int64_t max_kept) {
+    return carve_step(workspace, f, n_rays, scratch_cap(n_rays), max_marched, max_kept).kept_cnts;
+}
 }  // namespace mnf
 
 using namespace mnf;

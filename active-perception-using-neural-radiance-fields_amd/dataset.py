@@ -94,6 +94,18 @@ class Dataset(torch.utils.data.Dataset):
         new_c2w = camtoworlds.to(self.device).to(torch.float32).contiguous()
         return new_images, new_depths, new_sems, new_c2w
 
+    def set_camtoworlds(self, image_ids, c2w):
+        """Write poses back for stored images (refined ones: `localize.PoseRefiner`): `c2w` [n,3|4,4], host array or tensor on any device, for
+        `image_ids` [n].  Stored in the dataset's own dtype and shape; a device tensor goes in with no host round trip."""
+        if self.camtoworlds is None:
+            raise ValueError("Dataset.set_camtoworlds: the dataset holds no captures yet")
+        ids = torch.as_tensor(image_ids).reshape(-1).to(device=self.camtoworlds.device, dtype=torch.int64)
+        c2w = (c2w if torch.is_tensor(c2w) else torch.from_numpy(np.asarray(c2w))).to(device=self.camtoworlds.device, dtype=self.camtoworlds.dtype)
+        rows = self.camtoworlds.shape[1]
+        if c2w.dim() != 3 or c2w.shape[0] != ids.numel() or c2w.shape[1] < min(rows, 3) or c2w.shape[2] != 4:
+            raise ValueError(f"Dataset.set_camtoworlds expects [{ids.numel()},3|4,4] poses (got {tuple(c2w.shape)})")
+        self.camtoworlds[ids, :c2w.shape[1]] = c2w[:, :rows]
+
     def __len__(self):
         return self.size
 

@@ -1394,6 +1394,91 @@ int mnf_sensor_views(const uint32_t *voxels, int32_t X, int32_t Y, int32_t Z, co
                      const uint8_t *shade_host, uint32_t background, uint8_t *rgba, float *depth, uint8_t *sem, int32_t *hit, int64_t *info,
                      mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- pose refinement against the frozen map (csrc/localize.hip)
+ *
+ * State estimation for a capture whose pose comes from odometry: B views of the dataset, each with its own correction xi[b] = (rotvec [3] axis-angle,
+ * trans [3]) of its initial pose c2w0[b], refined against the field with its parameters frozen (iNeRF-style).  What render.transform_rays +
+ * fused_train_render_rays + torch.optim.Adam do for one view and one iteration per host round, here for B views and a whole run of iterations in ONE C call
+ * that never synchronises.  xi and Adam's two moments adam_m, adam_v are float64 [B,6] on the device and stay there between calls.
+ *
+ * mnf_pose_rays.  Rays and targets of B views x n rays (ray i = b n + r).
+ *   Pixel: pix_idx[b n + r] (flat id y W + x, int64; clamped into the image) or, with pix_idx NULL, drawn: (u0, u1, .., ..) = Philox4x32-10 of counter
+ *     (r, b, iteration, 0x706F7365) with key (seed low, seed high); x = (u0 W) >> 32, y = (u1 H) >> 32 in 64-bit integers, pix = y W + x.  pix_out [B,n]
+ *     receives the ids either way.
+ *   Ray: d = mnf_generate_rays' direction of that pixel from c2w0[b] ([B,3,4] f32), in its fp32 operation order.  R = I + a K + b K^2 of rotvec in float64
+ *     (a = sin t / t, b = (1 - cos t) / t^2, t = |rotvec|; below t^2 = 1e-6 the series a = 1 - t^2/6 + t^4/120, b = 1/2 - t^2/24 + t^4/720: transform_rays'
+ *     branches), rounded ONCE to fp32 (rot_out [B,9], optional).  d' = ((R_j0 d_0 + R_j1 d_1) + R_j2 d_2)_j in fp32;  o' = (float)((double)c + trans), c the
+ *     camera centre c2w0[b][:,3]: every ray of a view starts there, so transform_rays' rotation about the common origin drops out.
+ *   Targets: mnf_gather_pixels' of image image_ids[b] (device int64 [B], clamped to [0, n_images)) for either storage layout: target_rgb [B n,3] f32,
+ *     target_depth [B n] f32, target_label [B n] int64.
+ *
+ * mnf_pose_loss.  Per view b, from the four rendered planes of its n rays:  loss[b] = w_rgb mean smooth_l1(rgb - target_rgb) + w_dep mean
+ *   smooth_l1(depth - target_depth) + w_sem mean CE(sem, target_label)  (pipeline.py:506-511's forms; every mean over the VIEW's own rays; float64 [B]), and
+ *   its gradients g_rgb [B n,3], g_depth [B n], g_sem [B n,C] (fp32, dense: what mnf_train_render_backward_rays reads with strides (3,1), 1, (C,1)).  A label
+ *   outside [0, C) in a view sets view_status[b] = 8 (else 0), ORs 8 into *status_word (optional) and zeroes that view's gradients; such a ray adds nothing
+ *   to the loss.  n_classes 0: no semantic term, sem / g_sem may be NULL.  One workgroup per view, sums in a fixed order.
+ *
+ * mnf_pose_update.  Per view, one workgroup:  S_o = sum_r g_rays_o[r],  S_w = sum_r rays_d[r] x g_rays_d[r]  over the view's rays in float64 in a fixed
+ *   order (no atomics: the same inputs give the same bytes);  dL/dtrans = S_o,  dL/drotvec = J_l(rotvec)^T S_w,  J_l = I + b K + c K^2,
+ *   b = (1 - cos t) / t^2, c = (t - sin t) / t^3 (below t^2 = 1e-6: b = 1/2 - t^2/24 + t^4/720, c = 1/6 - t^2/120 + t^4/5040);  grad_out [B,6]
+ *   (optional) receives (dL/drotvec, dL/dtrans).  Then one Adam step on the six numbers: learning rates lr_rot / lr_trans, bias-corrected moments, the
+ *   view's step number iteration + 1 - stalled[b].  A view is LEFT ALONE — xi and moments untouched, stalled[b] += 1 — when none of its rays kept a sample
+ *   (kept_cnts [B n] int64; NULL: every ray counts as kept), when view_status[b] != 0 (NULL: none), when *skip_dev > 0 (NULL: never), or when its gradient
+ *   is not finite.  `stalled` is cumulative over a refinement: the caller zeroes it once, with xi and the moments.
+ *
+ * mnf_pose_refine.  For iteration first_iter + it, it = 0 .. n_iters - 1, enqueues in order: mnf_pose_rays; mnf_train_render_forward's launches on all B n
+ *   rays (the caller's `opts` with stratified = 0 and presampled = NULL: the sample set is a constant of each render, no gradient passes through the sample
+ *   positions); mnf_pose_loss; mnf_train_render_backward_rays' launches with the three parameter pointers NULL (frozen: the field's parameters are read, never
+ *   written); mnf_pose_update with the forward's per-ray kept counts, the loss' view bits and the render's skip flag (a sample bound exceeded, a ray past the
+ *   scratch row, no sample at all, a non-finite gradient).  loss_trace [n_iters,B] float64 and counts_dev [n_iters,4] int64 (mnf_train_step's four counters
+ *   of each iteration's render; a bad label ORs 8 into its status word) are indexed from THIS call's first iteration.  After status bit 1 or 4 the caller
+ *   raises max_marched / max_kept and calls again: the views stalled meanwhile.  No hand-over to the call-by-call route happens inside: at most four
+ *   occupancy levels, no ray past the scratch row (status bit 2 stalls every view).  workspace: mnf_pose_refine_workspace_bytes(f, n_views, rays_per_view,
+ *   max_marched, max_kept) device bytes, 256-byte aligned; mnf_pose_refine_workspace_offset gives the byte offset of what the LAST iteration left there
+ *   (MNF_POSE_WS_*: rays [B n,3], pixel ids, the four planes, the ray gradients, the 6-vector gradients [B,6] f64, R [B,9] f32, the render's
+ *   kept-sample count of every ray [B n] int64), for tests and tools.
+ *
+ * mnf_pose_opts starts with struct_size (MNF_INIT).  Argument errors (a null required pointer, a wrong struct_size, sizes <= 0 or B n > 2^31 - 1, a
+ * misaligned float64 / int64 array, learning rates < 0, betas outside [0, 1), eps <= 0) return MNF_ERR_INVALID before any HIP call; a NULL or short workspace
+ * MNF_ERR_WORKSPACE.  Profile labels: "pose_rays", "pose_loss", "pose_update".  Every call enqueues on `stream`, none synchronises.  There is no CPU fallback. */
+typedef struct mnf_pose_opts_s {
+    uint32_t struct_size;          /* sizeof(mnf_pose_opts) */
+    float w_rgb, w_dep, w_sem;     /* the loss weights (pipeline.py:511: 10, 1/5, 1/2) */
+    double lr_rot, lr_trans;       /* Adam's learning rate for rotvec and for trans */
+    double beta1, beta2, eps;      /* Adam (the project's optimizers: 0.9, 0.999, 1e-15) */
+    uint64_t seed;                 /* key of the pixel draw */
+} mnf_pose_opts;
+#define MNF_POSE_WS_RAYS_O 0
+#define MNF_POSE_WS_RAYS_D 1
+#define MNF_POSE_WS_PIX 2
+#define MNF_POSE_WS_RGB 3
+#define MNF_POSE_WS_ACC 4
+#define MNF_POSE_WS_DEPTH 5
+#define MNF_POSE_WS_SEM 6
+#define MNF_POSE_WS_G_RAYS_O 7
+#define MNF_POSE_WS_G_RAYS_D 8
+#define MNF_POSE_WS_GRAD 9
+#define MNF_POSE_WS_ROT 10
+#define MNF_POSE_WS_KEPT 11
+int mnf_pose_rays(const uint8_t *images, const void *depths, int32_t depth_is_f16, const void *semantics, int32_t sem_is_u8, int64_t n_images,
+                  const int64_t *image_ids, const float *c2w0, float focal, int32_t width, int32_t height, const int64_t *pix_idx, const double *xi,
+                  int32_t n_views, int32_t rays_per_view, int64_t iteration, uint64_t seed, float *rays_o, float *rays_d, int64_t *pix_out, float *rot_out,
+                  float *target_rgb, float *target_depth, int64_t *target_label, mnf_stream_t stream);
+int mnf_pose_loss(const float *rgb, const float *depth, const float *sem, const float *target_rgb, const float *target_depth, const int64_t *target_label,
+                  int32_t n_views, int32_t rays_per_view, int32_t n_classes, const mnf_pose_opts *pose, double *loss, float *g_rgb, float *g_depth, float *g_sem,
+                  int32_t *view_status, int64_t *status_word, mnf_stream_t stream);
+int mnf_pose_update(const float *g_rays_o, const float *g_rays_d, const float *rays_d, const int64_t *kept_cnts, const int32_t *view_status,
+                    const int32_t *skip_dev, int32_t n_views, int32_t rays_per_view, int64_t iteration, const mnf_pose_opts *pose, double *xi, double *adam_m,
+                    double *adam_v, int32_t *stalled, double *grad_out, mnf_stream_t stream);
+int64_t mnf_pose_refine_workspace_bytes(mnf_field_t f, int32_t n_views, int32_t rays_per_view, int64_t max_marched, int64_t max_kept);
+int64_t mnf_pose_refine_workspace_offset(mnf_field_t f, int32_t n_views, int32_t rays_per_view, int64_t max_marched, int64_t max_kept, int32_t what);
+int mnf_pose_refine(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitgrid, const float *occs, int32_t res_x, int32_t res_y, int32_t res_z,
+                    const float *aabb_host, const uint8_t *images, const void *depths, int32_t depth_is_f16, const void *semantics, int32_t sem_is_u8,
+                    int64_t n_images, const int64_t *image_ids, const float *c2w0, float focal, int32_t width, int32_t height, const int64_t *pix_idx,
+                    int32_t n_views, int32_t rays_per_view, double *xi, double *adam_m, double *adam_v, int64_t first_iter, int32_t n_iters,
+                    const mnf_train_opts *opts, const mnf_pose_opts *pose, double *loss_trace, int32_t *stalled, int64_t *counts_dev, int64_t max_marched,
+                    int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

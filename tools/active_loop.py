@@ -7,10 +7,15 @@ place of habitat_sim: a closed procedural room, 64 x 64 captures, one field, a 2
      curves, samples, view poses) with `trajectory_clearance`, `score_views` per candidate and the argmax, captures along the winner,
      `update_data` and `ScanCostMap.update`, `train_step`s, `evaluate_views` on held-out captures.
 
+With `--pose-noise DEG,CM` every capture of a planning step arrives with a drifted pose (a rotation of DEG degrees about a random axis, CM centimetres
+along a random direction) and is relocalised against the current field before it is trained on (`localize.PoseRefiner`, all views of the step in one batch);
+the step's line then carries the mean pose error before and after.  The initial sweep keeps its poses: there is no map to relocalise against yet.
+
 One line per planning step.  The whole run is one child process under `timeout`; the driver starts no GPU work itself.  Nothing here is a
 measurement of speed and nothing is asserted: it shows the stages joined end to end on the device.
 
     python tools/active_loop.py [--steps 3] [--out profiles/active_loop.txt]
+    python tools/active_loop.py --pose-noise 1,3 --out profiles/active_loop_pose_noise.txt
 """
 import argparse
 import os
@@ -29,8 +34,17 @@ START = np.array([-2.0, 1.0, -2.0])
 KW = dict(near_plane=0.1, render_step_size=5e-3, cone_angle=0.004, alpha_thre=0.01)
 
 
-def run(steps, train_steps, n_goals, seed):
+def pose_errors(c2w, truth):
+    """(mean rotation error in degrees, mean translation error in cm) of poses [n,4,4] against `truth`"""
+    c2w, truth = np.asarray(c2w, np.float64), np.asarray(truth, np.float64)
+    rel = np.einsum("nij,nkj->nik", c2w[:, :3, :3], truth[:, :3, :3])
+    ang = np.degrees(np.arccos(np.clip((np.trace(rel, axis1=1, axis2=2) - 1.0) / 2.0, -1.0, 1.0)))
+    return float(ang.mean()), float(100.0 * np.linalg.norm(c2w[:, :3, 3] - truth[:, :3, 3], axis=1).mean())
+
+
+def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40):
     import torch
+    from apnrf_amd import localize as LZ
     from apnrf_amd import clearance as CL
     from apnrf_amd import nerfacc as NA
     from apnrf_amd import planning as PL
@@ -56,15 +70,33 @@ def run(steps, train_steps, n_goals, seed):
     cost = PL.ScanCostMap(AABB, CELL, device=DEV)
     c2w_of = lambda poses: torch.from_numpy(np.stack([RD.pose_to_c2w(p) for p in np.asarray(poses, np.float64).reshape(-1, 7)])).to(DEV)
 
-    def capture(poses):
+    noise_rng = np.random.default_rng(seed + 1)      # (its own stream: the loop's draws are the same with and without the leg)
+
+    def capture(poses, drift=None):
         """What the reference does with a batch of captures: the dataset takes colour, depth (along the ray, what the field renders) and
-        classes; the cost map takes the planar depth's middle rows."""
+        classes; the cost map takes the planar depth's middle rows.  `drift` (degrees, cm): the poses arrive perturbed and are refined
+        against the current field before anything trains on them -> the pose errors before and after."""
         c2w = c2w_of(poses)
         rgba, depth_ray, sem = sim.sample_images_from_poses(poses, depth="ray")
         planar = sim.sample_images_from_poses(poses)[1]
-        data.update_data(rgba[..., :3], depth_ray, sem, c2w)
+        report = None
+        if drift is not None:
+            truth = c2w.cpu().numpy()
+            n = truth.shape[0]
+            axes, dirs = noise_rng.standard_normal((n, 3)), noise_rng.standard_normal((n, 3))
+            axes, dirs = axes / np.linalg.norm(axes, axis=1, keepdims=True), dirs / np.linalg.norm(dirs, axis=1, keepdims=True)
+            noisy = LZ.compose_c2w(truth, np.concatenate([axes * np.deg2rad(drift[0]), dirs * drift[1] * 1e-2], 1))
+            first = len(data)
+            data.update_data(rgba[..., :3], depth_ray, sem, torch.from_numpy(noisy).to(DEV))
+            ids = list(range(first, first + n))
+            out = LZ.refine_poses(field, est, data, ids, n_iters=refine_iters, rays_per_view=1024, lr_rot=1e-3, lr_trans=2e-3, seed=seed, **KW)
+            data.set_camtoworlds(ids, out["c2w"])
+            c2w = torch.from_numpy(out["c2w"]).to(DEV)
+            report = pose_errors(noisy, truth) + pose_errors(out["c2w"], truth) + (int(out["stalled"].max()), out["status"])
+        else:
+            data.update_data(rgba[..., :3], depth_ray, sem, c2w)
         cost.update(planar, c2w)
-        return rgba, depth_ray, sem, c2w
+        return report
 
     done = [0]
 
@@ -114,13 +146,15 @@ def run(steps, train_steps, n_goals, seed):
         best = int(np.argmax(scores))
         traj = cand["trajectories"][best]
         views = traj[np.linspace(0, len(traj) - 1, 6).astype(int)]
-        capture(views)
+        report = capture(views, pose_noise)
         current = views[-1][:3].copy()
         train(train_steps // 2)
         ev = RD.evaluate_views(field.eval(), est.eval(), held, [0, 1, 2, 3], **KW)["mean"]
         print(f"step {step}     {goals.shape[0]} goals, {len(cand['trajectories'])} curves ({int(certified.sum())} certified at 0.1 m), scores "
               f"{min(scores):.3f} .. {max(scores):.3f}, flew curve {cand['kept'][best]} of {len(traj)} poses to ({current[0]:.2f}, {current[1]:.2f}, {current[2]:.2f}); "
-              f"{len(data)} views, {done[0]} train steps: held-out PSNR {ev['psnr']:.2f}, depth MSE {ev['depth_mse']:.4f}; sensor misses {int(sim.info[0])}", flush=True)
+              f"{len(data)} views, {done[0]} train steps: held-out PSNR {ev['psnr']:.2f}, depth MSE {ev['depth_mse']:.4f}; sensor misses {int(sim.info[0])}"
+              + ("" if report is None else f"; pose error of the {len(views)} captures {report[0]:.2f} deg, {report[1]:.2f} cm -> {report[2]:.2f} deg, {report[3]:.2f} cm after "
+                 f"{refine_iters} iterations (stalled at most {report[4]}, status {report[5]})"), flush=True)
 
 
 def main():
@@ -129,6 +163,7 @@ def main():
     ap.add_argument("--train-steps", type=int, default=200)
     ap.add_argument("--goals", type=int, default=6)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--pose-noise", default=None, metavar="DEG,CM", help="perturb the pose of every capture of a planning step and refine it against the field first")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help="(internal) run the loop in this process")
     a = ap.parse_args()
@@ -137,13 +172,14 @@ def main():
         if not torch.cuda.is_available():
             raise SystemExit("active_loop needs a GPU")
         import apnrf_amd  # noqa: F401
-        run(a.steps, a.train_steps, a.goals, a.seed)
+        run(a.steps, a.train_steps, a.goals, a.seed, tuple(float(x) for x in a.pose_noise.split(",")) if a.pose_noise else None)
         return
     r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--child", "--steps", str(a.steps), "--train-steps", str(a.train_steps),
-                        "--goals", str(a.goals), "--seed", str(a.seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                        "--goals", str(a.goals), "--seed", str(a.seed)] + (["--pose-noise", a.pose_noise] if a.pose_noise else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     body = [ln for ln in r.stdout.splitlines() if ln.strip() and "amdgpu.ids" not in ln]
     head = (f"# the active-mapping loop at small sizes: a closed {AABB[3] - AABB[0]:.0f} x {AABB[4] - AABB[1]:.1f} x {AABB[5] - AABB[2]:.0f} m procedural world at 10 cm voxels, "
-            f"{SIDE} x {SIDE} captures, one 128 x 2 field with a 2^14 table; {a.steps} planning steps, seed {a.seed}")
+            f"{SIDE} x {SIDE} captures, one 128 x 2 field with a 2^14 table; {a.steps} planning steps, seed {a.seed}"
+            + (f"; captures arrive with {a.pose_noise} (deg, cm) of pose noise and are relocalised first" if a.pose_noise else ""))
     text = "\n".join([head] + (body if r.returncode == 0 else body[-25:] + [f"# the loop ended with status {r.returncode}"]))
     print(text)
     if a.out:

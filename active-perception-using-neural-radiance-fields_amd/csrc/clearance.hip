@@ -103,9 +103,9 @@ __global__ void __launch_bounds__(kEdtThreads) edt_pass_kernel(const uint8_t *__
         d2[at] = best;
     }
     if (kLast) {
+        occupied = wave_sum(occupied);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            occupied += __shfl_down(occupied, off, 64);
             const int other = __shfl_down(largest, off, 64);
             largest = other > largest ? other : largest;
         }
@@ -175,9 +175,8 @@ __global__ void __launch_bounds__(kLookupThreads) lookup_kernel(const int32_t *_
     for (int off = 32; off > 0; off >>= 1) {
         const unsigned long long other = __shfl_down(key, off, 64);
         key = other < key ? other : key;
-        outside += __shfl_down(outside, off, 64);
-        bad += __shfl_down(bad, off, 64);
     }
+    wave_sum_each(outside, bad);
     if ((tid & 63) == 0) { wave_key[tid >> 6] = key; wave_out[tid >> 6] = outside; wave_bad[tid >> 6] = bad; }
     __syncthreads();
     if (tid == 0) {
@@ -371,7 +370,7 @@ extern "C" int mnf_clearance_lookup(const int32_t *d2, int32_t X, int32_t Y, int
     MNF_REQUIRE(field_geometry_ok(1, X, Y, Z, &grid), "clearance_lookup: %d x %d x %d is outside the limits of a clearance field", X, Y, Z);
     MNF_REQUIRE(origin_host, "clearance_lookup: origin_host is null");
     MNF_REQUIRE(voxel > 0.0 && voxel <= 1.79e308, "clearance_lookup: voxel must be positive and finite (got %g)", voxel);
-    for (int k = 0; k < 3; ++k) MNF_REQUIRE(origin_host[k] - origin_host[k] == 0.0, "clearance_lookup: origin_host[%d] is not finite", k);
+    for (int k = 0; k < 3; ++k) MNF_REQUIRE(finite_d(origin_host[k]), "clearance_lookup: origin_host[%d] is not finite", k);
     MNF_REQUIRE(n_points >= 0 && n_points < ((int64_t)1 << 31), "clearance_lookup: n_points outside [0, 2^31) (%lld)", (long long)n_points);
     MNF_REQUIRE(n_traj >= 0 && n_traj < ((int64_t)1 << 31), "clearance_lookup: n_traj outside [0, 2^31) (%lld)", (long long)n_traj);
     MNF_REQUIRE(info, "clearance_lookup: info is null");

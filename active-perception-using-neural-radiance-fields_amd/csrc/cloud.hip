@@ -30,6 +30,7 @@
 //                         so the order inside a run (which the atomics of the sort decide) cannot change a result.  Answers go back to the
 //                         queries' original places.
 // Every loop is bounded by counts read once from the scans; no lane waits for another workgroup.
+#include "reduce_dev.h"
 #include "workspace.h"
 
 namespace mnf {
@@ -43,7 +44,6 @@ constexpr int kStage = 1024;                         // targets staged in LDS at
 constexpr int kMaxClasses = 1024;
 
 inline bool finite_f(float v) { return v - v == 0.0f; }
-inline bool finite_d(double v) { return v - v == 0.0; }
 
 // ---------------------------------------------------------------------------------------------------------------- sampling
 // ceil(x) as a count: 0 for x <= 0 (numpy's arange of a non-positive length is empty) and for NaN, saturating at kCountCap
@@ -384,11 +384,7 @@ __global__ void __launch_bounds__(kThreads) cloud_stats_kernel(const float *__re
             if (a >= 0 && a < C && b >= 0 && b < C) atomicAdd((unsigned long long *)(confusion + (int64_t)a * C + b), 1ull);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        c0 += __shfl_down(c0, off, 64); c1 += __shfl_down(c1, off, 64); c2 += __shfl_down(c2, off, 64);
-        s0 += __shfl_down(s0, off, 64); s1 += __shfl_down(s1, off, 64);
-    }
+    wave_sum_each(c0, c1, c2, s0, s1);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { red_c[wave][0] = c0; red_c[wave][1] = c1; red_c[wave][2] = c2; red_s[wave][0] = s0; red_s[wave][1] = s1; }
     __syncthreads();

@@ -59,6 +59,12 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline unsigned blocks_for(int64_t n, int threads = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, threads); }
 
 inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// the byte of its 4-byte word that p points at: 0 when p is 4-byte aligned
+__host__ __device__ inline int byte_in_word(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3); }
+inline bool aligned4(const void *p) { return byte_in_word(p) == 0; }
+
+// neither NaN nor an infinity
+__host__ __device__ inline bool finite_d(double x) { return x - x == 0.0; }
 
 // Diagnostic knobs (tools/README.md) exist only in the -DMNF_DIAG build (libmi355nerf_diag.so): the product library never
 // reads the environment, so no stray variable can change its results, its round schedule or its timings.

@@ -124,9 +124,9 @@ extern "C" int mnf_score_ensemble_views(const float *rgb, const float *depth, co
     }
     if (n_views == 0) return MNF_OK;
     MNF_REQUIRE(rgb && depth && acc && sem && terms && workspace, "score_ensemble_views: null pointer");
-    MNF_REQUIRE(((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(sem)) & 3) == 0,
+    MNF_REQUIRE(aligned4(rgb) && aligned4(depth) && aligned4(acc) && aligned4(sem),
                 "score_ensemble_views: the fp32 stacks must be 4-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(terms) & 7) == 0,
+    MNF_REQUIRE(aligned8(workspace) && aligned8(terms),
                 "score_ensemble_views: workspace and terms must be 8-byte aligned");
     MNF_REQUIRE(n_views <= 65535, "score_ensemble_views: at most 65535 views per call (got %d)", n_views);
     const ViewPlan pl = view_plan(n_pix, stage_tile_pixels(n_classes));      // a tile of >= 8 pixels for C <= MNF_SCORE_ENSEMBLE_MAX_CLASSES

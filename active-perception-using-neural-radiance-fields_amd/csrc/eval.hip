@@ -4,11 +4,12 @@
 //                      [H, W, C] host stack for the label image)
 //
 // One pass over the finished renders of V views of P pixels.  Ground truth is read straight from the dataset's storage (u8 images,
-// f32 / f16 depths, i64 / u8 labels: the two layouts of gather_pixels_kernel, march.hip); no fp32 ground-truth image is written.
+// f32 / f16 depths, i64 / u8 labels: the two layouts of pixel_dev.h); no fp32 ground-truth image is written.
 //
 // The work split, the logit staging and the reduction of the six sums are view_dev.h's.  Per pixel (3 + 1 + C) * 4 bytes of render and 15
 // (u8 / f32 / i64) or 6 (u8 / f16 / u8) bytes of ground truth are read, once.  The confusion matrix is counted with integer atomics (an LDS
 // histogram per workgroup for C <= 64, flushed with one 64-bit global atomic per non-zero cell; straight to global above that).
+#include "pixel_dev.h"
 #include "view_dev.h"
 
 namespace mnf {
@@ -44,14 +45,14 @@ __global__ void __launch_bounds__(kViewThreads) eval_views_kernel(
             const int64_t g = gt_base + (pix_idx ? pix_idx[p] : p);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const float gt = (float)images[3 * g + k] / 255.0f;  // gather_pixels_kernel's expression
+                const float gt = unit_u8(images[3 * g + k]);
                 const double d = (double)rgb[3 * i + k] - (double)gt;
                 s_rgb += d * d;
             }
-            const float gd = depth_f16 ? (float)reinterpret_cast<const _Float16 *>(depths)[g] : reinterpret_cast<const float *>(depths)[g];
+            const float gd = load_depth(depths, depth_f16, g);
             const double dd = (double)depth[i] - (double)gd;
             s_dep += dd * dd;
-            const int64_t label = sem_u8 ? (int64_t)reinterpret_cast<const uint8_t *>(sems)[g] : reinterpret_cast<const int64_t *>(sems)[g];
+            const int64_t label = load_label(sems, sem_u8, g);
             const float *row = stage + tid * Cs;
             float best;
             const int arg = first_argmax(row, C, &best);
@@ -132,7 +133,7 @@ extern "C" int mnf_eval_views(const float *rgb, const float *depth, const float 
     MNF_REQUIRE(image_ids, "eval_views: image_ids is null");
     MNF_REQUIRE(metrics, "eval_views: metrics is null");
     MNF_REQUIRE(workspace, "eval_views: workspace is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "eval_views: workspace must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(workspace), "eval_views: workspace must be 8-byte aligned");
     const int tp = stage_tile_pixels(n_classes);
     if (tp < 1) {
         set_error("eval_views: n_classes = %d is more than one LDS tile holds (%d)", n_classes, kStageBytes / 4 - 1);

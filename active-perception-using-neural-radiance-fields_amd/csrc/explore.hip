@@ -118,8 +118,7 @@ __global__ void __launch_bounds__(256) explore_insert_kernel(
     } while (false);
     if (stats) {                                                     // (uniform) the measurement's counters: voxel steps walked, ORs issued
         unsigned long long a = (unsigned long long)steps, b = (unsigned long long)ors;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
+        wave_sum_each(a, b);
         if ((threadIdx.x & 63) == 0) { atomicAdd(stats, a); atomicAdd(stats + 1, b); }
     }
 }
@@ -136,8 +135,7 @@ __global__ void __launch_bounds__(256) explore_count_kernel(const unsigned int *
         const int o = __popc(p1 & valid), f = __popc(p0 & ~p1 & valid);
         oc += o; fr += f; un += __popc(valid) - o - f;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { fr += __shfl_down(fr, off, 64); oc += __shfl_down(oc, off, 64); un += __shfl_down(un, off, 64); }
+    wave_sum_each(fr, oc, un);
     if ((tid & 63) == 0) { red[tid >> 6][0] = fr; red[tid >> 6][1] = oc; red[tid >> 6][2] = un; }
     __syncthreads();
     if (tid < 3) {
@@ -435,7 +433,7 @@ extern "C" int mnf_explore_map_frontier_clusters(const int32_t *cells, const int
                 (long long)max_frontiers);
     MNF_REQUIRE(max_clusters >= 0 && max_clusters <= 0x7fffffff, "explore_map_frontier_clusters: max_clusters outside [0, 2^31) (got %lld)",
                 (long long)max_clusters);
-    MNF_REQUIRE(current_x - current_x == 0.0 && current_z - current_z == 0.0, "explore_map_frontier_clusters: current is not finite");
+    MNF_REQUIRE(finite_d(current_x) && finite_d(current_z), "explore_map_frontier_clusters: current is not finite");
     MNF_REQUIRE(cells || max_frontiers == 0, "explore_map_frontier_clusters: cells is null");
     MNF_REQUIRE(mult || max_frontiers == 0, "explore_map_frontier_clusters: mult is null");
     MNF_REQUIRE(frontier_info, "explore_map_frontier_clusters: frontier_info is null");

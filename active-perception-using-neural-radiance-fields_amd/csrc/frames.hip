@@ -34,7 +34,7 @@ struct FrameDepth { double mul, div, hi, gain; };
 
 // Store the n bytes buf[mis .. mis + n) to dst[0 .. n), mis = dst & 3: dword w of `buf` is the aligned global dword at dst - mis + 4 w.
 __device__ __forceinline__ void flush_plane(const uint32_t *buf, uint8_t *__restrict__ dst, int n, int tid) {
-    const int mis = (int)(reinterpret_cast<uintptr_t>(dst) & 3);
+    const int mis = byte_in_word(dst);
     const int end = mis + n, nw = (end + 3) >> 2;
     uint8_t *base = dst - mis;
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(buf);
@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(kViewThreads) frames_views_kernel(
         if (tid < np) {
             const int64_t i = i0 + tid;
             if (rgb8) {
-                uint8_t *o = reinterpret_cast<uint8_t *>(out3[0]) + (reinterpret_cast<uintptr_t>(d_rgb) & 3) + 3 * tid;
+                uint8_t *o = reinterpret_cast<uint8_t *>(out3[0]) + byte_in_word(d_rgb) + 3 * tid;
                 o[c0] = sat8(rgb[3 * i] * 255.0f);
                 o[1] = sat8(rgb[3 * i + 1] * 255.0f);
                 o[c2] = sat8(rgb[3 * i + 2] * 255.0f);
@@ -83,15 +83,15 @@ __global__ void __launch_bounds__(kViewThreads) frames_views_kernel(
                 const double x = ((double)depth[i] * dm.mul) / dm.div;
                 const double lo = x < 0.0 ? 0.0 : x;               // np.maximum(x, 0): a NaN fails the comparison and stays
                 const double cl = lo > dm.hi ? dm.hi : lo;         // np.minimum(., hi)
-                reinterpret_cast<uint8_t *>(out1[0])[(reinterpret_cast<uintptr_t>(d_dep) & 3) + tid] = sat8(cl * dm.gain);
+                reinterpret_cast<uint8_t *>(out1[0])[byte_in_word(d_dep) + tid] = sat8(cl * dm.gain);
             }
-            if (occ8) reinterpret_cast<uint8_t *>(out1[1])[(reinterpret_cast<uintptr_t>(d_occ) & 3) + tid] = sat8((double)acc[i] * 255.0);
+            if (occ8) reinterpret_cast<uint8_t *>(out1[1])[byte_in_word(d_occ) + tid] = sat8((double)acc[i] * 255.0);
             if (want_label) {
                 float best;
                 const int arg = first_argmax(stage + tid * Cs, C, &best);
-                if (labels) reinterpret_cast<uint8_t *>(out1[2])[(reinterpret_cast<uintptr_t>(d_lab) & 3) + tid] = (uint8_t)arg;
+                if (labels) reinterpret_cast<uint8_t *>(out1[2])[byte_in_word(d_lab) + tid] = (uint8_t)arg;
                 if (sem8) {
-                    uint8_t *o = reinterpret_cast<uint8_t *>(out3[1]) + (reinterpret_cast<uintptr_t>(d_sem) & 3) + 3 * tid;
+                    uint8_t *o = reinterpret_cast<uint8_t *>(out3[1]) + byte_in_word(d_sem) + 3 * tid;
                     o[c0] = palette[3 * arg];
                     o[1] = palette[3 * arg + 1];
                     o[c2] = palette[3 * arg + 2];

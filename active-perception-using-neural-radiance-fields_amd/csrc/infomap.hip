@@ -188,16 +188,16 @@ extern "C" int mnf_score_view_maps(const float *rgb_var, const float *depth_var,
         }
     }
     MNF_REQUIRE(rgb_var && depth_var && acc && sem, "score_view_maps: null input pointer");
-    MNF_REQUIRE(((reinterpret_cast<uintptr_t>(rgb_var) | reinterpret_cast<uintptr_t>(depth_var) | reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(sem)) & 3) == 0,
+    MNF_REQUIRE(aligned4(rgb_var) && aligned4(depth_var) && aligned4(acc) && aligned4(sem),
                 "score_view_maps: the fp32 stacks must be 4-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(maps) & 7) == 0, "score_view_maps: maps must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(heat8) & 3) == 0, "score_view_maps: heat8 must be 4-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(terms) & 7) == 0, "score_view_maps: terms must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(maps), "score_view_maps: maps must be 8-byte aligned");
+    MNF_REQUIRE(aligned4(heat8), "score_view_maps: heat8 must be 4-byte aligned");
+    MNF_REQUIRE(aligned8(terms), "score_view_maps: terms must be 8-byte aligned");
     MNF_REQUIRE(n_views <= 65535, "score_view_maps: at most 65535 views per call (got %d)", n_views);
     const ViewPlan pl = view_plan(n_pix, stage_tile_pixels(n_classes, kMapEntryBytes, kMapLdsBytes));
     if (terms) {                                                     // the partial sums exist for the per-view means only
         const int64_t need = view_partials_bytes(n_views, pl.nb, kMapTerms);
-        MNF_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "score_view_maps: terms needs an 8-byte aligned workspace");
+        MNF_REQUIRE(workspace && aligned8(workspace), "score_view_maps: terms needs an 8-byte aligned workspace");
         MNF_REQUIRE(workspace_bytes >= need, "score_view_maps: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     }
     hipStream_t s = as_stream(stream);

@@ -16,6 +16,9 @@
 #include <cstring>
 
 #include "field.h"
+#include "philox_dev.h"
+#include "pixel_dev.h"
+#include "reduce_dev.h"
 #include "workspace.h"
 
 namespace mnf {
@@ -26,17 +29,6 @@ namespace {
 
 constexpr int kLossThreads = 1024, kUpdateThreads = 256;
 constexpr uint32_t kPixelTag = 0x706F7365u;      // the draw's own Philox tag ("pose")
-
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * ctr.x, p1 = (uint64_t)0xCD9E8D57u * ctr.z;
-        ctr = {(uint32_t)(p1 >> 32) ^ ctr.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ ctr.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return ctr;
-}
 
 // Rodrigues in float64, transform_rays' branches: R = I + a K + b K^2, a = sin t / t, b = (1 - cos t) / t^2, their Taylor series below t^2 = 1e-6
 __device__ __forceinline__ void rodrigues(const double *k, double *R) {
@@ -69,7 +61,6 @@ struct PoseRaysArgs {
 
 __global__ void __launch_bounds__(256) pose_rays_kernel(const PoseRaysArgs a) {
     const int64_t total = (int64_t)a.B * a.n, pixels = (int64_t)a.W * a.H;
-    const float cx = (float)a.W * 0.5f, cy = (float)a.H * 0.5f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)blockDim.x * gridDim.x) {
         const int32_t b = (int32_t)(i / a.n), r = (int32_t)(i - (int64_t)b * a.n);
         int64_t pix;
@@ -82,17 +73,12 @@ __global__ void __launch_bounds__(256) pose_rays_kernel(const PoseRaysArgs a) {
             pix = y * a.W + x;
         }
         a.pix_out[i] = pix;
-        // ---- the ray of raygen_kernel (march.hip) from c2w0[b], in its fp32 operation order
-        const float x = (float)(pix % a.W), y = (float)(pix / a.W);
+        // ---- the pixel's ray from c2w0[b] (pixel_dev.h: raygen_kernel's)
         const float *m = a.c2w0 + (int64_t)b * 12;
-        const float cam0 = (x - cx + 0.5f) / a.focal;
-        const float cam1 = (y - cy + 0.5f) / a.focal * -1.0f;
-        const float cam2 = -1.0f;
-        const float dx = (cam0 * m[0] + cam1 * m[1]) + cam2 * m[2];
-        const float dy = (cam0 * m[4] + cam1 * m[5]) + cam2 * m[6];
-        const float dz = (cam0 * m[8] + cam1 * m[9]) + cam2 * m[10];
-        const float nrm = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-        const float d0 = dx / nrm, d1 = dy / nrm, d2 = dz / nrm;
+        float cam0, cam1, d[3];
+        pixel_ray(pix % a.W, pix / a.W, a.W, a.H, a.focal, m, cam0, cam1, d);
+        normalize_ray(d);
+        const float d0 = d[0], d1 = d[1], d2 = d[2];
         // ---- the correction: R in float64 from the float64 xi, rounded once; d' = R d; o' = c + trans (the rotation about the common origin drops out)
         const double *k = a.xi + (int64_t)b * 6;
         double Rd[9];
@@ -110,38 +96,19 @@ __global__ void __launch_bounds__(256) pose_rays_kernel(const PoseRaysArgs a) {
 #pragma unroll
             for (int j = 0; j < 9; ++j) a.rot_out[(int64_t)b * 9 + j] = R[j];
         }
-        // ---- the targets of gather_pixels_kernel (march.hip), image image_ids[b]
+        // ---- the pixel's targets (pixel_dev.h: gather_pixels_kernel's), image image_ids[b]
         int64_t img = a.image_ids[b];
         img = img < 0 ? 0 : (img >= a.n_images ? a.n_images - 1 : img);
         const int64_t p = img * pixels + pix;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a.t_rgb[3 * i + c] = (float)a.images[3 * p + c] / 255.0f;
-        a.t_dep[i] = a.depth_f16 ? (float)reinterpret_cast<const _Float16 *>(a.depths)[p] : reinterpret_cast<const float *>(a.depths)[p];
-        a.t_lab[i] = a.sem_u8 ? (int64_t)reinterpret_cast<const uint8_t *>(a.sems)[p] : reinterpret_cast<const int64_t *>(a.sems)[p];
+        for (int c = 0; c < 3; ++c) a.t_rgb[3 * i + c] = unit_u8(a.images[3 * p + c]);
+        a.t_dep[i] = load_depth(a.depths, a.depth_f16, p);
+        a.t_lab[i] = load_label(a.sems, a.sem_u8, p);
     }
 }
 
-__device__ __forceinline__ void smooth_l1(float x, float &val, float &grad) {      // beta = 1: loss_kernel's (trainstep.hip)
-    const float ax = fabsf(x);
-    val = ax < 1.0f ? 0.5f * x * x : ax - 0.5f;
-    grad = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);
-}
-
-// a workgroup's float64 sum in a fixed order: the lane's own partial, the xor butterfly of its wave, the waves in order.  Every thread calls it.
-template <int WAVES>
-__device__ __forceinline__ double block_sum(double v, double *s_wave) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();      // (s_wave may still be read from the previous sum)
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) t += s_wave[w];
-    return t;
-}
-
-// One workgroup per view.  Pass 1: any label of the view outside [0, C)?  Pass 2: loss terms and plane gradients of its n rays (zero gradients for a flagged view).
+// One workgroup per view.  Pass 1: any label of the view outside [0, C)?  Pass 2: loss terms and plane gradients of its n rays (pixel_dev.h's two halves; zero
+// gradients for a flagged view), the terms summed in float64 (block_sum, reduce_dev.h).
 __global__ void __launch_bounds__(kLossThreads) pose_loss_kernel(int32_t n, int32_t C, const float *__restrict__ rgb, const float *__restrict__ depth,
                                                                  const float *__restrict__ sem, const float *__restrict__ t_rgb, const float *__restrict__ t_dep,
                                                                  const int64_t *__restrict__ t_lab, float w_rgb, float w_dep, float w_sem,
@@ -158,27 +125,8 @@ __global__ void __launch_bounds__(kLossThreads) pose_loss_kernel(int32_t n, int3
     double l_rgb = 0.0, l_dep = 0.0, l_sem = 0.0;
     for (int32_t r = threadIdx.x; r < n; r += kLossThreads) {
         const int64_t i = base + r;
-        float v, g;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            smooth_l1(rgb[3 * i + k] - t_rgb[3 * i + k], v, g);
-            l_rgb += (double)v;
-            g_rgb[3 * i + k] = bad ? 0.0f : g * (w_rgb / 3.0f) * inv_n;
-        }
-        smooth_l1(depth[i] - t_dep[i], v, g);
-        l_dep += (double)v;
-        g_dep[i] = bad ? 0.0f : g * w_dep * inv_n;
-        if (C > 0) {
-            const float *lg = sem + i * C;
-            float mx = -INFINITY;
-            for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
-            float den = 0.f;
-            for (int k = 0; k < C; ++k) den += expf(lg[k] - mx);
-            const int64_t lab = t_lab[i];
-            const bool lab_ok = lab >= 0 && lab < C;      // (a ray with a label outside the classes contributes nothing and reads nothing past its row)
-            l_sem += lab_ok ? (double)(logf(den) - (lg[lab] - mx)) : 0.0;
-            for (int k = 0; k < C; ++k) g_sem[i * C + k] = bad ? 0.0f : (expf(lg[k] - mx) / den - (k == lab ? 1.0f : 0.0f)) * w_sem * inv_n;
-        }
+        l_dep += (double)ray_loss_planes(i, rgb, depth, t_rgb, t_dep, w_rgb / 3.0f, w_dep, inv_n, bad, g_rgb, g_dep, l_rgb);
+        if (C > 0) l_sem += (double)ray_loss_sem(i, C, sem, t_lab, w_sem, inv_n, bad, g_sem, [] {});      // (the first pass has flagged a bad label)
     }
     const double s_rgb = block_sum<kLossThreads / 64>(l_rgb, s_wave), s_dep = block_sum<kLossThreads / 64>(l_dep, s_wave),
                  s_sem = block_sum<kLossThreads / 64>(l_sem, s_wave);
@@ -235,7 +183,7 @@ __global__ void __launch_bounds__(kUpdateThreads) pose_update_kernel(const PoseU
     for (int j = 0; j < 3; ++j) { g[j] = (s[3 + j] - cb * kx[j]) + cc * kkx[j]; g[3 + j] = s[j]; }
     bool finite = true;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) finite = finite && (g[j] - g[j] == 0.0);
+    for (int j = 0; j < 6; ++j) finite = finite && finite_d(g[j]);
     if (a.grad_out)
         for (int j = 0; j < 6; ++j) a.grad_out[(int64_t)b * 6 + j] = g[j];
     const bool stall = !kept || !finite || (a.view_status && a.view_status[b] != 0) || (a.skip && *a.skip > 0);
@@ -270,7 +218,7 @@ int check_rays_args(const char *who, const uint8_t *images, const void *depths, 
     MNF_REQUIRE(W > 0 && H > 0 && W <= 32768 && H <= 32768 && focal > 0.f && focal <= 3.4e38f, "%s: bad image size or focal (%d x %d, %g)", who, W, H, (double)focal);
     MNF_REQUIRE(n_images > 0, "%s: n_images must be positive", who);
     MNF_REQUIRE(images && depths && semantics && image_ids && c2w0 && xi, "%s: a null input pointer", who);
-    MNF_REQUIRE(aligned8(image_ids) && aligned8(xi) && (reinterpret_cast<uintptr_t>(c2w0) & 3) == 0, "%s: image_ids and xi must be 8-byte aligned, c2w0 4-byte", who);
+    MNF_REQUIRE(aligned8(image_ids) && aligned8(xi) && aligned4(c2w0), "%s: image_ids and xi must be 8-byte aligned, c2w0 4-byte", who);
     return MNF_OK;
 }
 

@@ -23,6 +23,7 @@
 // loop with the running base in a register.
 #pragma once
 #include "common.h"
+#include "reduce_dev.h"
 
 namespace mnf {
 

@@ -2,6 +2,7 @@
 // pinhole ray generator.  Build with -ffp-contract=off (see march_dev.h).
 #include "common.h"
 #include "march_dev.h"
+#include "pixel_dev.h"
 
 namespace mnf {
 
@@ -382,26 +383,21 @@ __global__ void __launch_bounds__(256) accumulate_bwd_kernel(const float *__rest
 }
 
 // ------------------------------------------------------------------ ray generation
-// habitat_to_data.py:274-301; arithmetic order pinned by tests/golden/raygen.npz (oracle/render.py).
+// habitat_to_data.py:274-301; arithmetic order (pixel_dev.h) pinned by tests/golden/raygen.npz (oracle/render.py).
 __global__ void __launch_bounds__(256) raygen_kernel(const float *__restrict__ c2w, int32_t n_views, int32_t width, int32_t height,
                                                      float focal, const int64_t *__restrict__ pix_idx, int64_t n_pix,
                                                      float *__restrict__ origins, float *__restrict__ viewdirs) {
     const int64_t total = (int64_t)n_views * n_pix;
-    const float cx = (float)width * 0.5f, cy = (float)height * 0.5f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)blockDim.x * gridDim.x) {
         const int64_t v = i / n_pix, p = i % n_pix;
         const int64_t pix = pix_idx ? pix_idx[p] : p;
-        const float x = (float)(pix % width), y = (float)(pix / width);
+        const int64_t x = pix % width, y = pix / width;
         const float *m = c2w + v * 12;
-        const float cam0 = (x - cx + 0.5f) / focal;
-        const float cam1 = (y - cy + 0.5f) / focal * -1.0f;
-        const float cam2 = -1.0f;
-        const float dx = (cam0 * m[0] + cam1 * m[1]) + cam2 * m[2];
-        const float dy = (cam0 * m[4] + cam1 * m[5]) + cam2 * m[6];
-        const float dz = (cam0 * m[8] + cam1 * m[9]) + cam2 * m[10];
-        const float n = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        float cam0, cam1, d[3];
+        pixel_ray(x, y, width, height, focal, m, cam0, cam1, d);
+        normalize_ray(d);
         origins[3 * i] = m[3]; origins[3 * i + 1] = m[7]; origins[3 * i + 2] = m[11];
-        viewdirs[3 * i] = dx / n; viewdirs[3 * i + 1] = dy / n; viewdirs[3 * i + 2] = dz / n;
+        viewdirs[3 * i] = d[0]; viewdirs[3 * i + 1] = d[1]; viewdirs[3 * i + 2] = d[2];
     }
 }
 
@@ -416,9 +412,9 @@ __global__ void __launch_bounds__(256) gather_pixels_kernel(const uint8_t *__res
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x) {
         const int64_t p = base + pix[i];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) rgb[3 * i + k] = (float)images[3 * p + k] / 255.0f;
-        dep[i] = depth_f16 ? (float)reinterpret_cast<const _Float16 *>(depths)[p] : reinterpret_cast<const float *>(depths)[p];
-        sem[i] = sem_u8 ? (int64_t)reinterpret_cast<const uint8_t *>(sems)[p] : reinterpret_cast<const int64_t *>(sems)[p];
+        for (int k = 0; k < 3; ++k) rgb[3 * i + k] = unit_u8(images[3 * p + k]);
+        dep[i] = load_depth(depths, depth_f16, p);
+        sem[i] = load_label(sems, sem_u8, p);
     }
 }
 

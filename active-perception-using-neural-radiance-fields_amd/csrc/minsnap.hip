@@ -460,14 +460,14 @@ extern "C" int mnf_minsnap_solve(const double *points, const int32_t *cells, con
     MNF_REQUIRE(n_traj >= 0 && n_traj < ((int64_t)1 << 31), "minsnap_solve: n_traj outside [0, 2^31) (%lld)", (long long)n_traj);
     MNF_REQUIRE(n_waypoints >= 0 && n_waypoints < ((int64_t)1 << 31), "minsnap_solve: n_waypoints outside [0, 2^31) (%lld)", (long long)n_waypoints);
     MNF_REQUIRE((points != nullptr) != (cells != nullptr) || n_waypoints == 0, "minsnap_solve: give points or cells, one of the two");
-    MNF_REQUIRE(yaw0 - yaw0 == 0.0 && yaw1 - yaw1 == 0.0 && v_avg - v_avg == 0.0, "minsnap_solve: yaw0, yaw1 and v_avg must be finite");
+    MNF_REQUIRE(finite_d(yaw0) && finite_d(yaw1) && finite_d(v_avg), "minsnap_solve: yaw0, yaw1 and v_avg must be finite");
     double o[3] = {0.0, 0.0, 0.0};
     if (cells) {
         MNF_REQUIRE(origin_host, "minsnap_solve: origin_host is null");
         MNF_REQUIRE(resolution > 0.0 && resolution <= 1.79e308, "minsnap_solve: resolution must be positive and finite (got %g)", resolution);
-        MNF_REQUIRE(height - height == 0.0, "minsnap_solve: height is not finite");
+        MNF_REQUIRE(finite_d(height), "minsnap_solve: height is not finite");
         for (int k = 0; k < 3; ++k) {
-            MNF_REQUIRE(origin_host[k] - origin_host[k] == 0.0, "minsnap_solve: origin_host[%d] is not finite", k);
+            MNF_REQUIRE(finite_d(origin_host[k]), "minsnap_solve: origin_host[%d] is not finite", k);
             o[k] = origin_host[k];
         }
     }

@@ -88,8 +88,7 @@ __global__ void __launch_bounds__(256) object_map_count_kernel(const unsigned in
     const int64_t words = (g.n_vox + 31) >> 5;
     int64_t n = 0;
     for (int64_t w = tid; w < words; w += 256) n += __popc(bits[c * g.wpp + w] & valid_bits(w, g.n_vox));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+    n = wave_sum(n);
     if ((tid & 63) == 0) red[tid >> 6] = n;
     __syncthreads();
     if (tid == 0) counts[c] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -308,8 +307,7 @@ __global__ void __launch_bounds__(64) match_kernel(const double *__restrict__ cl
         lo += k < c ? 1 : 0;
         cnt += k == c ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { lo += __shfl_xor(lo, off, 64); cnt += __shfl_xor(cnt, off, 64); }
+    wave_sum_all_each(lo, cnt);
     int found = 0;
     for (int64_t r = lo; r < lo + cnt; ++r) {
         const double cx = clusters[r * 5 + 2], cy = clusters[r * 5 + 3], cz = clusters[r * 5 + 4];

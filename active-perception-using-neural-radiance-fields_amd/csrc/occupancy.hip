@@ -12,7 +12,7 @@
 //            stage in LDS.
 //
 // Shapes are static (no boolean-mask compaction, hence no host sync): the sample list has a fixed capacity and unused
-// slots carry cell index -1.  Random draws come from Philox4x32-10 (documented below) or, for tests against the
+// slots carry cell index -1.  Random draws come from Philox4x32-10 (philox_dev.h; the stream is documented below) or, for tests against the
 // reference's recorded draws, from caller-provided arrays.  Duplicate cells in one update resolve as "the last list
 // element wins" (what torch's index assignment does on the CPU; on CUDA the reference's order is undefined).
 //
@@ -21,29 +21,15 @@
 #include <cstring>
 
 #include "field.h"
+#include "philox_dev.h"
 #include "workspace.h"
 
 namespace mnf {
 namespace {
 
-// ------------------------------------------------------------------ Philox4x32-10 (Salmon et al., SC'11)
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * ctr.x, p1 = (uint64_t)0xCD9E8D57u * ctr.z;
-        ctr = {(uint32_t)(p1 >> 32) ^ ctr.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ ctr.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return ctr;
-}
-
-// Draw stream of one update: counter = (element, 0, kind, step), key = (seed low, seed high);
+// Draw stream of one update (philox_dev.h): counter = (element low, element high, kind, step), key = (seed low, seed high);
 // kind 0 = uniform half, 1 = occupied half, 2 = warm-up.  Word 0 picks the cell (uniform: floor(w0 * cells / 2^32);
-// occupied: floor(w0 * n_occupied / 2^32)), words 1..3 are the in-cell offsets (w & 0xFFFFFF) * 2^-24 in [0, 1).
-__device__ __forceinline__ float unit_float(uint32_t w) { return (float)(w & 0xFFFFFFu) * 5.9604644775390625e-08f; }
-
+// occupied: floor(w0 * n_occupied / 2^32)), words 1..3 are the in-cell offsets unit_float(w) in [0, 1).
 struct SampleArgs {
     const float *occs;         // [cells] of this level
     const uint32_t *bits;      // bit-packed binaries of this level (occupied half)

@@ -121,8 +121,7 @@ __global__ void __launch_bounds__(kFieldThreads) path_field_kernel(const int32_t
         if (v >= kNoEntry) v = kUnreached; else ++mine;
         out[i] = v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    mine = wave_sum(mine);
     if ((tid & 63) == 0 && mine) atomicAdd(&reached, mine);
     __syncthreads();
     if (tid == 0) { info[2 * b] = fixpoint ? (int64_t)reached : -1; info[2 * b + 1] = sweeps; }

@@ -211,8 +211,7 @@ extern "C" int mnf_scan_map_update(void *state, int32_t nx, int32_t nz, const fl
     MNF_REQUIRE(loc || n_views == 0, "scan_map_update: loc is null");
     MNF_REQUIRE(centre || n_views == 0, "scan_map_update: centre is null");
     MNF_REQUIRE(aligned8(info) && aligned8(align) && aligned8(yaw) && aligned8(loc), "scan_map_update: info, align, yaw and loc must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(state) & 3) == 0 && (reinterpret_cast<uintptr_t>(centre) & 3) == 0 &&
-                (reinterpret_cast<uintptr_t>(depth) & 3) == 0, "scan_map_update: state, centre and depth must be 4-byte aligned");
+    MNF_REQUIRE(aligned4(state) && aligned4(centre) && aligned4(depth), "scan_map_update: state, centre and depth must be 4-byte aligned");
     if (n_views == 0) return MNF_OK;
     const int cells = nx * nz;
     int32_t *cost = static_cast<int32_t *>(state), *visits = cost + cells;

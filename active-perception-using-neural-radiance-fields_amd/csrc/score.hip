@@ -5,22 +5,12 @@
 #include <vector>
 
 #include "field.h"
+#include "reduce_dev.h"
 #include "workspace.h"
 
 namespace mnf {
 
-// ------------------------------------------------------------------ scorer (pipeline.py:727-781), one block per view
-__device__ __forceinline__ double block_sum(double v, double *s_buf) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_buf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_buf[w];
-    return t;
-}
-
+// ------------------------------------------------------------------ scorer (pipeline.py:727-781), one block of kScoreThreads per view
 constexpr int kScoreMaxM = 4;             // ensemble sizes the array-free form of the semantic term is unrolled for (the reference's ensemble has two members)
 constexpr int kScoreThreads = 1024;      // 16 waves per view: the 4096 pixels of a view are ~220 double-precision exp / log each; four waves per view left three of four issue slots to their latencies (1.07 ms per 256 views)
 template <bool SMALL_M>      // SMALL_M: M <= kScoreMaxM (checked by the host)
@@ -116,7 +106,9 @@ __global__ void __launch_bounds__(kScoreThreads) score_kernel(const float *__res
             s_occ += -(a_ens + 1e-4) * log(a_ens + 1e-4) - (1.0 - a_ens + 1e-4) * log(1.0 - a_ens + 1e-4) - mean_ce / M;
         }
     }
-    const double t0 = block_sum(s_rgb, s_buf), t1 = block_sum(s_dep, s_buf), t2 = block_sum(s_sem, s_buf), t3 = block_sum(s_occ, s_buf);
+    constexpr int kWaves = kScoreThreads / 64;      // (both launches below use kScoreThreads)
+    const double t0 = block_sum<kWaves>(s_rgb, s_buf), t1 = block_sum<kWaves>(s_dep, s_buf), t2 = block_sum<kWaves>(s_sem, s_buf),
+                 t3 = block_sum<kWaves>(s_occ, s_buf);
     if (threadIdx.x == 0) {
         terms[4 * v + 0] = t0 / (3.0 * P);
         terms[4 * v + 1] = t1 / P;

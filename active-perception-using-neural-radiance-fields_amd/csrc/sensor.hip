@@ -19,6 +19,7 @@
 // of a wave's rgba and depth stores is one aligned 64-byte run (a pixel's four bytes are one 32-bit store) and its class bytes a 16-byte
 // one.  The counts of info are summed per wave by ballot and added with one atomic per wave: integer sums, the same whatever the schedule.
 #include "map_dev.h"
+#include "pixel_dev.h"
 
 namespace mnf {
 namespace {
@@ -191,16 +192,9 @@ __global__ void __launch_bounds__(kThreads) views_kernel(Scene sc, const uint32_
     bool bad = false;
     if (live) {
         const double *m = c2w + v * 12;
-        const double cx = (double)W * 0.5, cy = (double)H * 0.5;
-        const double cam0 = ((double)x - cx + 0.5) / focal;
-        const double cam1 = ((double)y - cy + 0.5) / focal * -1.0;
-        const double cam2 = -1.0;
-        double o[3], d[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            d[i] = (cam0 * m[4 * i] + cam1 * m[4 * i + 1]) + cam2 * m[4 * i + 2];
-            o[i] = m[4 * i + 3];
-        }
+        double cam0, cam1, d[3];
+        pixel_ray(x, y, W, H, focal, m, cam0, cam1, d);
+        const double o[3] = {m[3], m[7], m[11]};
         uint32_t word = 0;
         double t = 0.0;
         int fc = kFaceNear;
@@ -232,13 +226,13 @@ int scene_arguments(const char *who, const uint32_t *voxels, int32_t X, int32_t 
     MNF_REQUIRE(bg.wpp <= kMaskWords, "%s: the brick mask of %d x %d x %d voxels takes %lld words, more than the %d (64 KiB of LDS) a workgroup stages", who, X,
                 Y, Z, (long long)bg.wpp, kMaskWords);
     MNF_REQUIRE(lo_host, "%s: lo_host is null", who);
-    for (int k = 0; k < 3; ++k) MNF_REQUIRE(lo_host[k] - lo_host[k] == 0.0, "%s: lo_host[%d] is not finite", who, k);
+    for (int k = 0; k < 3; ++k) MNF_REQUIRE(finite_d(lo_host[k]), "%s: lo_host[%d] is not finite", who, k);
     MNF_REQUIRE(s > 0.0 && s <= 1.79e308, "%s: the voxel size must be positive and finite (got %g)", who, s);
     MNF_REQUIRE(near >= 0.0 && far >= near && far <= 1.79e308, "%s: need 0 <= near <= far, far finite (got %g, %g)", who, near, far);
     MNF_REQUIRE(info, "%s: info is null", who);
     MNF_REQUIRE(aligned8(info), "%s: info must be 8-byte aligned", who);
     MNF_REQUIRE(voxels && bricks, "%s: a null scene pointer", who);
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(voxels) & 3) == 0 && (reinterpret_cast<uintptr_t>(bricks) & 3) == 0, "%s: voxels and bricks must be 4-byte aligned", who);
+    MNF_REQUIRE(aligned4(voxels) && aligned4(bricks), "%s: voxels and bricks must be 4-byte aligned", who);
     *sc = {voxels, X, Y, Z, bg.Y, bg.Z, (int)bg.wpp, {lo_host[0], lo_host[1], lo_host[2]}, s};
     return MNF_OK;
 }
@@ -261,7 +255,7 @@ extern "C" int mnf_sensor_build_bricks(const uint32_t *voxels, int32_t X, int32_
     MNF_REQUIRE(bg.wpp <= kMaskWords, "sensor_build_bricks: the brick mask of %d x %d x %d voxels takes %lld words, more than %d (64 KiB of LDS)", X, Y, Z,
                 (long long)bg.wpp, kMaskWords);
     MNF_REQUIRE(voxels && bricks, "sensor_build_bricks: a null pointer");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(voxels) & 3) == 0 && (reinterpret_cast<uintptr_t>(bricks) & 3) == 0,
+    MNF_REQUIRE(aligned4(voxels) && aligned4(bricks),
                 "sensor_build_bricks: voxels and bricks must be 4-byte aligned");
     hipStream_t s = as_stream(stream);
     ProfScope prof("sensor_build_bricks", s);
@@ -280,7 +274,7 @@ extern "C" int mnf_sensor_cast_rays(const uint32_t *voxels, int32_t X, int32_t Y
     MNF_REQUIRE(n >= 0 && n <= (int64_t)0x7fffffff * kThreads, "sensor_cast_rays: n outside what one launch holds (%lld)", (long long)n);
     MNF_REQUIRE((origins && dirs && t_hit && hit && face) || n == 0, "sensor_cast_rays: a null ray or output array");
     MNF_REQUIRE(aligned8(origins) && aligned8(dirs) && aligned8(t_hit), "sensor_cast_rays: origins, dirs and t_hit must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(hit) & 3) == 0, "sensor_cast_rays: hit must be 4-byte aligned");
+    MNF_REQUIRE(aligned4(hit), "sensor_cast_rays: hit must be 4-byte aligned");
     if (n == 0) return MNF_OK;
     hipStream_t s = as_stream(stream);
     ProfScope prof("sensor_cast_rays", s);
@@ -306,7 +300,7 @@ extern "C" int mnf_sensor_views(const uint32_t *voxels, int32_t X, int32_t Y, in
     MNF_REQUIRE(blocks <= 0x7fffffff, "sensor_views: %d views of %d x %d are more than one launch holds", n_views, width, height);
     MNF_REQUIRE((c2w && rgba && depth && sem) || n_views == 0, "sensor_views: a null pose or output array");
     MNF_REQUIRE(aligned8(c2w), "sensor_views: c2w must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(rgba) & 3) == 0 && (reinterpret_cast<uintptr_t>(depth) & 3) == 0 && (reinterpret_cast<uintptr_t>(hit) & 3) == 0,
+    MNF_REQUIRE(aligned4(rgba) && aligned4(depth) && aligned4(hit),
                 "sensor_views: rgba, depth and hit must be 4-byte aligned");
     if (n_views == 0) return MNF_OK;
     Shade shade;

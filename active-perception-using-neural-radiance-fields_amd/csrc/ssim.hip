@@ -18,7 +18,7 @@
 //   stage    the (th + 10) x (tw + 10) x K patch of both images goes to LDS as floats, de-interleaved into K planes of row stride 42.  A patch
 //            row is one contiguous piece of the image: one wave per row takes it as stage_rows takes a tile (scalar loads up to the first
 //            16-byte boundary of the ADDRESS, 16-byte loads, scalar tail), so nothing outside the planes is read.  A u8 target is converted
-//            here with gather_pixels_kernel's expression (float)u8 / 255.0f.
+//            here with unit_u8 (pixel_dev.h).
 //   row pass per channel: lane j of 18 x 32 jobs filters 11 consecutive floats of one patch row of x and of y (stride-1 ds_read_b32 across
 //            the 32 lanes of a group: conflict-free) into the five doubles of planes[5][18][32].
 //   column pass per channel: lane t adds 11 rows of each plane; the 32 lanes of a ds_read_b64 group read 32 consecutive doubles = 256
@@ -32,6 +32,7 @@
 // double operations and 2.25 * 22 + 55 LDS reads: the double arithmetic and the LDS, not the memory, bound the kernel.
 #include <cmath>
 
+#include "pixel_dev.h"
 #include "view_dev.h"
 
 namespace mnf {
@@ -68,23 +69,23 @@ __device__ __forceinline__ void stage_patch_row(float *__restrict__ dst, const f
     if (e < n) dst[(e % K) * (kPatchH * kPatchW) + e / K] = src[e];
 }
 
-// the same for a row of u8 storage (K == 3): 16 bytes per vector load, (float)u8 / 255.0f as gather_pixels_kernel forms it
+// the same for a row of u8 storage (K == 3): 16 bytes per vector load, a byte converted by unit_u8 (pixel_dev.h)
 __device__ __forceinline__ void stage_patch_row_u8(float *__restrict__ dst, const uint8_t *__restrict__ src, int n, int lane) {
     const int head = min(n, (int)((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15));
     const int nvec = (n - head) >> 4;                           // <= 7
-    if (lane < head) dst[(lane % 3) * (kPatchH * kPatchW) + lane / 3] = (float)src[lane] / 255.0f;
+    if (lane < head) dst[(lane % 3) * (kPatchH * kPatchW) + lane / 3] = unit_u8(src[lane]);
     if (lane < nvec) {
         const uint4 x = *reinterpret_cast<const uint4 *>(src + head + 16 * lane);
         const uint32_t w[4] = {x.x, x.y, x.z, x.w};
         int e = head + 16 * lane, p = e / 3, c = e - p * 3;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            dst[c * (kPatchH * kPatchW) + p] = (float)((w[k >> 2] >> (8 * (k & 3))) & 255u) / 255.0f;
+            dst[c * (kPatchH * kPatchW) + p] = unit_u8((uint8_t)(w[k >> 2] >> (8 * (k & 3))));
             if (++c == 3) { c = 0; ++p; }
         }
     }
     const int e = head + 16 * nvec + lane;                      // tail: at most 15 bytes
-    if (e < n) dst[(e % 3) * (kPatchH * kPatchW) + e / 3] = (float)src[e] / 255.0f;
+    if (e < n) dst[(e % 3) * (kPatchH * kPatchW) + e / 3] = unit_u8(src[e]);
 }
 
 template <int K>
@@ -217,13 +218,13 @@ extern "C" int mnf_ssim_views(const float *pred, const float *target_f32, const 
     }
     MNF_REQUIRE(pred, "ssim_views: pred is null");
     MNF_REQUIRE(!target_u8 || image_ids, "ssim_views: the u8 target needs image_ids");
-    MNF_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target_f32)) & 3) == 0, "ssim_views: the fp32 planes must be 4-byte aligned");
+    MNF_REQUIRE(aligned4(pred) && aligned4(target_f32), "ssim_views: the fp32 planes must be 4-byte aligned");
     MNF_REQUIRE(ssim, "ssim_views: ssim is null");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(ssim) & 7) == 0, "ssim_views: ssim must be 8-byte aligned");
-    MNF_REQUIRE((reinterpret_cast<uintptr_t>(map) & 7) == 0, "ssim_views: map must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(ssim), "ssim_views: ssim must be 8-byte aligned");
+    MNF_REQUIRE(aligned8(map), "ssim_views: map must be 8-byte aligned");
     const SsimPlan pl = ssim_plan(height, width);
     const int64_t need = view_partials_bytes(n_views, pl.vp.nb, 1);
-    MNF_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "ssim_views: needs an 8-byte aligned workspace");
+    MNF_REQUIRE(workspace && aligned8(workspace), "ssim_views: needs an 8-byte aligned workspace");
     MNF_REQUIRE(workspace_bytes >= need, "ssim_views: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     SsimParams prm;
     double gsum = 0.0;

@@ -23,6 +23,7 @@
 // values from HBM and 4 B of words written in the count pass, 4 B of words read in the emit pass; everything else is per vertex or per
 // triangle.  The case table (which edges make the triangles of a tetrahedron, already oriented) is built at compile time from the
 // rule of the header and sits in constant memory.
+#include "reduce_dev.h"
 #include "workspace.h"
 
 namespace mnf {
@@ -320,8 +321,7 @@ __global__ void __launch_bounds__(kThreads) surface_measure_kernel(const float *
         const double c0 = b[1] * c[2] - b[2] * c[1], c1 = b[2] * c[0] - b[0] * c[2], c2 = b[0] * c[1] - b[1] * c[0];
         vol += ((a[0] * c0 + a[1] * c1) + a[2] * c2) / 6.0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { area += __shfl_down(area, off, 64); vol += __shfl_down(vol, off, 64); }
+    wave_sum_each(area, vol);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = area; red[threadIdx.x >> 6][1] = vol; }
     __syncthreads();
     if (threadIdx.x < 2) {

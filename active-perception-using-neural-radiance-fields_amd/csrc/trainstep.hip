@@ -22,6 +22,9 @@
 #include <cstddef>
 
 #include "field.h"
+#include "philox_dev.h"
+#include "pixel_dev.h"
+#include "reduce_dev.h"
 #include "workspace.h"
 
 // mnf_train_presample's handle: what was marched, for which rays / options, and the two events that order it
@@ -47,17 +50,6 @@ int composite_train_backward_impl(const int64_t *chunk_starts, const int64_t *ch
                                   const float *trans, const float *out_acc, const float *out_depth, const float *g_rgb, const float *g_acc, const float *g_depth,
                                   const float *g_sem, float *d_sigmas, float *d_rgbs, float *d_sems, mnf_stream_t stream);
 namespace {
-
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * ctr.x, p1 = (uint64_t)0xCD9E8D57u * ctr.z;
-        ctr = {(uint32_t)(p1 >> 32) ^ ctr.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ ctr.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return ctr;
-}
 
 // occ_grid.py:181-189: near / far planes, stratified jitter near += U[0,1) * step (Philox counter (ray, 0, 7, 0), key = seed)
 // Also the step's small zero-fills (loss terms, counters, skip flag, the two small gradient vectors): five separate memsets were five launches of ~5 us.
@@ -92,7 +84,7 @@ __global__ void __launch_bounds__(256) planes_kernel(int32_t n, float near_plane
     }
     if (r >= n || !nearp) return;
     float v = near_plane;
-    if (stratified) v += ((float)(philox4x32_10({(uint32_t)r, 0u, 7u, 0u}, s0, s1).x & 0xFFFFFFu) * 5.9604644775390625e-08f) * step;
+    if (stratified) v += unit_float(philox4x32_10({(uint32_t)r, 0u, 7u, 0u}, s0, s1).x) * step;
     nearp[r] = v; farp[r] = far_plane;
 }
 
@@ -110,8 +102,7 @@ __global__ void __launch_bounds__(256) mean_partial_kernel(const float *__restri
 __global__ void __launch_bounds__(64) mean_final_kernel(const double *__restrict__ part, int n_part, int64_t n, float alpha_thre, float *__restrict__ out) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < n_part; i += 64) acc += part[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    acc = wave_sum_all(acc);
     if (threadIdx.x == 0) out[0] = fminf(alpha_thre, (float)(acc / (double)n));
 }
 
@@ -169,13 +160,8 @@ __global__ void __launch_bounds__(64) visibility_kernel(int32_t n_rays, const in
 }
 
 // pipeline.py:506-511: 10 * smooth_l1(rgb, pixels) + smooth_l1(depth, dep[:, None]) / 5 + cross_entropy(sem, labels) / 2 (all
-// "mean" reductions) and its gradient with respect to the rendered rgb / depth / semantic logits.  One lane per ray.
-__device__ __forceinline__ void smooth_l1(float x, float &val, float &grad) {      // beta = 1
-    const float ax = fabsf(x);
-    val = ax < 1.0f ? 0.5f * x * x : ax - 0.5f;
-    grad = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);      // torch's branch order: a NaN difference gives a NaN gradient (the guard of pipeline.py:520-529 then drops the step)
-}
-
+// "mean" reductions) and its gradient with respect to the rendered rgb / depth / semantic logits.  One lane per ray, its terms and gradients from
+// pixel_dev.h's two halves.
 __global__ void __launch_bounds__(256) loss_kernel(int32_t n_rays, int32_t C, const float *__restrict__ rgb, const float *__restrict__ depth,
                                                    const float *__restrict__ sem, const float *__restrict__ t_rgb, const float *__restrict__ t_dep,
                                                    const int64_t *__restrict__ t_sem, float *__restrict__ g_rgb, float *__restrict__ g_dep,
@@ -186,32 +172,12 @@ __global__ void __launch_bounds__(256) loss_kernel(int32_t n_rays, int32_t C, co
     float l_rgb = 0.f, l_dep = 0.f, l_sem = 0.f;
     if (r < n_rays) {
         const float inv_r = 1.0f / (float)n_rays;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float v, g;
-            smooth_l1(rgb[3 * r + k] - t_rgb[3 * r + k], v, g);
-            l_rgb += v;
-            g_rgb[3 * r + k] = g * (10.0f / 3.0f) * inv_r;
-        }
-        float v, g;
-        smooth_l1(depth[r] - t_dep[r], v, g);
-        l_dep = v;
-        g_dep[r] = g * 0.2f * inv_r;
-        const float *lg = sem + (int64_t)r * C;
-        float mx = -INFINITY;
-        for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
-        float den = 0.f;
-        for (int k = 0; k < C; ++k) den += expf(lg[k] - mx);
-        const int64_t lab = t_sem[r];
+        l_dep = ray_loss_planes(r, rgb, depth, t_rgb, t_dep, 10.0f / 3.0f, 0.2f, inv_r, false, g_rgb, g_dep, l_rgb);
         // F.cross_entropy raises a device assert for a class id outside [0, C); here the step is flagged (status bit 8, skip
         // raised: no optimizer update) and the ray contributes nothing, instead of reading past the logits row
-        const bool lab_ok = lab >= 0 && lab < C;
-        if (!lab_ok) { atomicOr(reinterpret_cast<unsigned long long *>(status), 8ull); atomicAdd(skip, 1); }
-        l_sem = lab_ok ? logf(den) - (lg[lab] - mx) : 0.0f;
-        for (int k = 0; k < C; ++k) g_sem[(int64_t)r * C + k] = lab_ok ? (expf(lg[k] - mx) / den - (k == lab ? 1.0f : 0.0f)) * 0.5f * inv_r : 0.0f;
+        l_sem = ray_loss_sem(r, C, sem, t_sem, 0.5f, inv_r, false, g_sem, [&] { atomicOr(reinterpret_cast<unsigned long long *>(status), 8ull); atomicAdd(skip, 1); });
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { l_rgb += __shfl_xor(l_rgb, d, 64); l_dep += __shfl_xor(l_dep, d, 64); l_sem += __shfl_xor(l_sem, d, 64); }
+    wave_sum_all_each(l_rgb, l_dep, l_sem);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { s_acc[0][wave] = l_rgb; s_acc[1][wave] = l_dep; s_acc[2][wave] = l_sem; }
     __syncthreads();

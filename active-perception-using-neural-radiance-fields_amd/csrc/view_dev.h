@@ -11,6 +11,7 @@
 // (sum_partials).  No floating-point atomic anywhere: the same inputs give the same bits.
 #pragma once
 #include "common.h"
+#include "reduce_dev.h"
 
 namespace mnf {
 
@@ -38,8 +39,6 @@ inline int stage_tile_pixels(int32_t C, int entry_bytes = 4, int budget = kStage
 
 // bytes of the caller's workspace: one row of K doubles per workgroup
 inline int64_t view_partials_bytes(int32_t n_views, int nb, int K) { return (int64_t)n_views * nb * K * (int64_t)sizeof(double); }
-
-inline bool finite_d(double x) { return x - x == 0.0; }
 
 // Copy the n = np * C contiguous floats at `src` (4-byte aligned) into `stage` as np rows of stride Cs = C | 1: 16-byte loads per lane between
 // the first and the last 16-byte boundary of the ADDRESS, scalar loads before and after, so a base that is only 4-byte aligned is read wide
@@ -97,13 +96,7 @@ __device__ __forceinline__ uint8_t sat8(double y) {
     return (uint8_t)(int)rint(y);
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
-// The workgroup's row of `partials` from every lane's part[K]: shuffle tree per wave, then the four waves in order.  Every lane of workgroup
+// The workgroup's row of `partials` from every lane's part[K]: wave_sum (reduce_dev.h) per wave, then the four waves in order.  Every lane of workgroup
 // b of view v calls it, once; it holds ONE workgroup barrier, after every lane's last use of `part`'s inputs (eval_views_kernel counts on it).
 template <int K>
 __device__ __forceinline__ void store_partials(const double (&part)[K], double *__restrict__ partials, int v, int nb, int b, int tid) {

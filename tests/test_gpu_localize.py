@@ -4,7 +4,7 @@ INTEGRATION.md §A's second loop.  Scene: `make_scene(log2_hashmap_size=15)`, sh
 
 Bars (each figure is printed before it is asserted):
   rays        2^-22 relative to the ray's norm against the restatement; R within 1 fp32 ulp (device and host sin / cos may differ in the last place of a
-              double, and R is rounded once); targets and drawn pixel ids exact
+              double, and R is rounded once); targets and drawn pixel ids exact; with xi = 0 the bytes of `mnf_generate_rays` and `mnf_gather_pixels`
   loss        n 2^-24 sum|terms|: fp32 rounding of an n-term mean, the terms being what a value is formed from (for the cross-entropy log(den) and the
               shifted logit, for a gradient element the operands of its difference)
   update      2^-22 sum|terms| on the 6-vector gradient (the inputs are fp32-rounded), identical bytes on a second run, xi after Adam to 1e-12
@@ -117,6 +117,46 @@ def test_rays_and_targets(packed):
     pix = torch.from_numpy(np.random.default_rng(0).integers(0, WI * HI, (3, n))).to(DEV)
     fixed = _refiner(shape, ids, ds, rays_per_view=n, pix_idx=pix)
     assert torch.equal(fixed.formed(0)["pix"], pix) and torch.equal(fixed.formed(5)["pix"], pix)
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["reference-layout", "packed"])
+def test_pose_rays_equal_raygen_and_gather(packed):
+    """With xi = 0, `mnf_pose_rays` gives the bytes of `mnf_generate_rays` and `mnf_gather_pixels`, called per view with the same pixels: 7 x 5 images (both
+    centres are half-integers), 3 of them, views of images [2, 0], 70 caller's pixels per view (more than a wave, no multiple of 64; pixels 0 and 34 among
+    them), float32 poses with a general rotation (no direction component is zero)."""
+    from apnrf_amd.localize import rodrigues
+    W, Hh, n_img, B, n, C = 7, 5, 3, 2, 70, 11
+    rng = np.random.default_rng(12)
+    images = torch.from_numpy(rng.integers(0, 256, (n_img, Hh, W, 3), dtype=np.uint8)).to(DEV)
+    depths = torch.from_numpy(rng.uniform(0.2, 6.0, (n_img, Hh, W)).astype(np.float16 if packed else np.float32)).to(DEV)
+    sems = torch.from_numpy(rng.integers(0, C, (n_img, Hh, W)).astype(np.uint8 if packed else np.int64)).to(DEV)
+    ids = torch.tensor([2, 0], dtype=torch.int64, device=DEV)
+    pix_np = rng.integers(0, W * Hh, (B, n))
+    pix_np[0, 0], pix_np[0, 69], pix_np[1, 64], pix_np[1, 3] = 0, W * Hh - 1, 0, W * Hh - 1
+    pix = torch.from_numpy(pix_np).to(DEV)
+    c2w_np = np.zeros((B, 3, 4))
+    c2w_np[0, :, :3], c2w_np[1, :, :3] = rodrigues(np.array([0.4, -0.7, 0.55])), rodrigues(np.array([-1.1, 0.3, 0.8]))
+    c2w_np[:, :, 3] = [[0.3, 1.1, -0.7], [-1.4, 0.9, 2.2]]
+    c2w = torch.from_numpy(c2w_np.astype(np.float32)).to(DEV)
+    focal = float(np.float32(4.3))
+    xi = torch.zeros(B, 6, dtype=torch.float64, device=DEV)
+    lib = L.load_library()
+    o, d = torch.empty(B, n, 3, device=DEV), torch.empty(B, n, 3, device=DEV)
+    pix_out, rot = torch.empty(B, n, dtype=torch.int64, device=DEV), torch.empty(B, 3, 3, device=DEV)
+    rgb, dep, lab = torch.empty(B, n, 3, device=DEV), torch.empty(B, n, device=DEV), torch.empty(B, n, dtype=torch.int64, device=DEV)
+    L.launch(lib.mnf_pose_rays, L.ptr(images), L.ptr(depths), int(packed), L.ptr(sems), int(packed), n_img, L.ptr(ids), L.ptr(c2w), focal, W, Hh, L.ptr(pix), L.ptr(xi),
+             B, n, 0, 0, L.ptr(o), L.ptr(d), L.ptr(pix_out), L.ptr(rot), L.ptr(rgb), L.ptr(dep), L.ptr(lab))
+    assert torch.equal(pix_out, pix)
+    for b in range(B):
+        o1, d1 = torch.empty(1, n, 3, device=DEV), torch.empty(1, n, 3, device=DEV)
+        rgb1, dep1, lab1 = torch.empty(n, 3, device=DEV), torch.empty(n, device=DEV), torch.empty(n, dtype=torch.int64, device=DEV)
+        view_pix = pix[b].contiguous()
+        L.launch(lib.mnf_generate_rays, L.ptr(c2w[b:b + 1].contiguous()), 1, W, Hh, focal, L.ptr(view_pix), n, L.ptr(o1), L.ptr(d1))
+        L.launch(lib.mnf_gather_pixels, L.ptr(images), L.ptr(depths), int(packed), L.ptr(sems), int(packed), W * Hh, L.ptr(ids[b:b + 1].contiguous()), L.ptr(view_pix),
+                 n, L.ptr(rgb1), L.ptr(dep1), L.ptr(lab1))
+        assert (d1 != 0).all(), "a general rotation: no direction component is zero"
+        for name, got, want in (("origins", o[b], o1[0]), ("directions", d[b], d1[0]), ("rgb", rgb[b], rgb1), ("depth", dep[b], dep1), ("labels", lab[b], lab1)):
+            assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes(), f"view {b}: {name} differ"
 
 
 # ------------------------------------------------------------------ loss

@@ -266,6 +266,14 @@ SIGNATURES = {
     "mnf_pose_refine": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                   c_int64, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                   POINTER(TrainOpts), POINTER(PoseOpts), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "mnf_tsdf_integrate": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_double), c_double, c_double, c_int32, c_double,
+                                     c_double, c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32,
+                                     c_void_p, c_void_p]),
+    "mnf_tsdf_lattice": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mnf_tsdf_vertex_attrs": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_double), c_double, c_void_p, c_int64, c_void_p, c_int32,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnf_surface_extract_observed": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), c_int64, c_int64, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -54,6 +54,7 @@ SOURCES = {
     "minsnap.hip": ["-ffp-contract=off"],   # the time allocation and the sample times are chains of separately rounded float64 operations (numpy restates them)
     "sensor.hip": ["-ffp-contract=off"],    # a pixel's ray and every step of the walk are chains of separately rounded float64 operations (numpy restates them)
     "localize.hip": ["-ffp-contract=off"],  # a corrected ray is a chain of separately rounded float32 operations (numpy restates them)
+    "tsdf.hip": ["-ffp-contract=off"],      # a point's projection and update are chains of separately rounded float64 operations (numpy restates them)
     "field.hip@bf16": ["-DMNF_BF16", "-fno-slp-vectorize"],
     "train.hip@bf16": ["-DMNF_BF16"],
     "inputgrad.hip@bf16": ["-DMNF_BF16"],

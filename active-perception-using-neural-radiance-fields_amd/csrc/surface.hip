@@ -1,6 +1,7 @@
 // The semantic surface mesh of a trained field on the device (gfx950): the iso-surface of a scalar lattice by marching tetrahedra on the Kuhn
 // split, the lattice points of a trained field that are worth a density query, and the colours and classes of the vertices.
 //   mnf_surface_extract         <- what the `extract_mesh` of the reference's nerfacc benchmarks does with skimage / mcubes on the host
+//   mnf_surface_extract_observed   the same kernels with kObserved: a NaN point is unobserved, and neither its edges nor its tetrahedra emit
 //   mnf_surface_lattice_points  <- estimator.binaries (visualization/vis_voxel.py reads the same grid), refined
 //   mnf_surface_vertex_attrs    <- the colours and semantic labels of simulator/build_point_cloud_from_mesh.py, from the field's own outputs
 // include/mi355nerf.h ("surface mesh") has the definition; every output byte of this unit is fixed by it.  Built with -ffp-contract=off: a
@@ -21,7 +22,10 @@
 // The values are not staged in LDS: neighbouring lanes hold neighbouring z, so each of the 8 loads of the count pass is one coalesced row
 // segment, and the rows of y + 1 and x + 1 are read again by the workgroups that own them (L2 hits).  Traffic per lattice point: 4 B of
 // values from HBM and 4 B of words written in the count pass, 4 B of words read in the emit pass; everything else is per vertex or per
-// triangle.  The case table (which edges make the triangles of a tetrahedron, already oriented) is built at compile time from the
+// triangle.  With kObserved the count pass adds bit 19 "this point is NaN" and bits 20..26 "the other end of edge type t is NaN" to the
+// word (the prefix takes 11 bits, 8..18), an edge with a NaN end carries no vertex, and the emit pass drops the tetrahedra that hold a
+// NaN corner; every tetrahedron holds corners 0 and 7, so a cell whose own point is NaN emits nothing and the other corners' signs still
+// follow from the word.  The case table (which edges make the triangles of a tetrahedron, already oriented) is built at compile time from the
 // rule of the header and sits in constant memory.
 #include "reduce_dev.h"
 #include "workspace.h"
@@ -177,7 +181,38 @@ __device__ __forceinline__ unsigned triangles_of(unsigned cb) {
     return n;
 }
 
+// kObserved: the NaN bits of the 8 corners of the cell at a point, from the point's word (bit 19: this point; bits 20..26: the other ends)
+constexpr int kPrefixBits = 11;                      // a workgroup's earlier points own at most 255 * 7 vertices
+constexpr unsigned kPrefixMask = (1u << kPrefixBits) - 1u;
+constexpr int kNanShift = 8 + kPrefixBits;
+
+__device__ __forceinline__ unsigned cube_nan_bits(unsigned word) {
+    unsigned nb = (word >> kNanShift) & 1u;
+#pragma unroll
+    for (int c = 1; c < 8; ++c) nb |= ((word >> (kNanShift + 1 + kCornerType[c])) & 1u) << c;
+    return nb;
+}
+
+// a tetrahedron with a NaN corner emits nothing: its case becomes 0
+__device__ __forceinline__ bool tet_observed(unsigned nb, int k) {
+    const int c1 = 1 << kPerm[k][0], c2 = c1 | (1 << kPerm[k][1]);
+    return ((nb & 1u) | ((nb >> c1) & 1u) | ((nb >> c2) & 1u) | ((nb >> 7) & 1u)) == 0u;
+}
+
+__device__ __forceinline__ unsigned triangles_of_observed(unsigned cb, unsigned nb) {
+    if (nb & 0x81u) return 0;                          // corners 0 and 7 belong to all six
+    unsigned n = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!tet_observed(nb, k)) continue;
+        const int c = __popc(tet_case(cb, k));
+        n += (c == 0 || c == 4) ? 0u : c == 2 ? 2u : 1u;
+    }
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- count
+template <bool kObserved>
 __global__ void __launch_bounds__(kThreads) surface_count_kernel(const float *__restrict__ values, Lattice L, float iso, unsigned *__restrict__ words,
                                                                  int64_t *__restrict__ vblock, int64_t *__restrict__ tblock) {
     const int64_t lin64 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -186,22 +221,36 @@ __global__ void __launch_bounds__(kThreads) surface_count_kernel(const float *__
         const int lin = (int)lin64;
         int x, y, z;
         point_of(L, lin, x, y, z);
-        const bool in = values[lin] > iso;
+        const float a = values[lin];
+        const bool in = a > iso, a_nan = kObserved && a != a;
         const bool hx = x + 1 < L.NX, hy = y + 1 < L.NY, hz = z + 1 < L.NZ;
+        unsigned nans = a_nan ? 1u : 0u, diff = 0;                                    // diff: the ends differ, NaN or not (the corners' signs)
 #pragma unroll
         for (int t = 0; t < 7; ++t) {
             const int c = kTypeCorner[t], dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
             if ((dx && !hx) || (dy && !hy) || (dz && !hz)) continue;                  // the other end is not a lattice point: no such edge
-            const bool other = values[lin + dx * L.sx + dy * L.sy + dz] > iso;
-            bits |= (other != in ? 1u : 0u) << t;
+            const float b = values[lin + dx * L.sx + dy * L.sy + dz];
+            const bool other = b > iso;
+            diff |= (other != in ? 1u : 0u) << t;
+            if (kObserved) nans |= (b != b ? 1u : 0u) << (t + 1);
         }
-        nv = __popc(bits);
-        bits |= (in ? 1u : 0u) << 7;
-        if (nv && hx && hy && hz) nt = triangles_of(cube_bits(bits));                 // no edge of the point is cut: its cell has one sign
+        if (kObserved) {
+            bits = a_nan ? 0u : diff & ~(nans >> 1);                                   // an edge with a NaN end carries no vertex
+            nv = __popc(bits);
+            // a NaN end is outside, as `diff` has it; where it was masked out of `bits` the emit pass reads the corner's sign as this point's,
+            // which only tetrahedra with a NaN corner see
+            if (!a_nan && hx && hy && hz) nt = triangles_of_observed(cube_bits(diff | ((in ? 1u : 0u) << 7)), cube_nan_bits(nans << kNanShift));
+            bits |= ((in ? 1u : 0u) << 7) | (nans << kNanShift);
+        } else {
+            bits = diff;
+            nv = __popc(bits);
+            bits |= (in ? 1u : 0u) << 7;
+            if (nv && hx && hy && hz) nt = triangles_of(cube_bits(bits));             // no edge of the point is cut: its cell has one sign
+        }
     }
     unsigned all;
     const unsigned before = block_exclusive(nv | (nt << 16), &all);                    // <= 1792 and <= 3072 per workgroup: no carry between the halves
-    if (lin64 < L.n) words[lin64] = ((before & 0xffffu) << 8) | bits;
+    if (lin64 < L.n) words[lin64] = ((before & kPrefixMask) << 8) | bits;
     if (threadIdx.x == 0) { vblock[blockIdx.x] = all & 0xffffu; tblock[blockIdx.x] = all >> 16; }
 }
 
@@ -216,11 +265,12 @@ __device__ __forceinline__ float lattice_difference(const float *__restrict__ v,
 
 __device__ __forceinline__ int64_t vertex_index(const unsigned *__restrict__ words, const int64_t *__restrict__ vbase, int lin, int type) {
     const unsigned w = words[lin];
-    return vbase[lin >> kBlockShift] + (int64_t)(w >> 8) + __popc(w & ((1u << type) - 1u));
+    return vbase[lin >> kBlockShift] + (int64_t)((w >> 8) & kPrefixMask) + __popc(w & ((1u << type) - 1u));
 }
 
 struct Frame { float o[3], s[3]; };
 
+template <bool kObserved>
 __global__ void __launch_bounds__(kThreads) surface_emit_kernel(const float *__restrict__ values, Lattice L, float iso, Frame F, const unsigned *__restrict__ words,
                                                                 const int64_t *__restrict__ vbase, const int64_t *__restrict__ tbase,
                                                                 const int64_t *__restrict__ totals, int64_t max_v, int64_t max_t,
@@ -231,20 +281,24 @@ __global__ void __launch_bounds__(kThreads) surface_emit_kernel(const float *__r
         const int64_t V = totals[0], T = totals[1];
         info[0] = V; info[1] = T; info[2] = V > max_v ? V - max_v : 0; info[3] = T > max_t ? T - max_t : 0;
     }
-    unsigned word = 0, nt = 0, cb = 0;
+    unsigned word = 0, nt = 0, cb = 0, nb = 0;
     int lin = 0, x = 0, y = 0, z = 0;
     if (lin64 < L.n) {
         lin = (int)lin64;
         word = words[lin];
         point_of(L, lin, x, y, z);
-        if ((word & 0x7fu) && x + 1 < L.NX && y + 1 < L.NY && z + 1 < L.NZ) { cb = cube_bits(word); nt = triangles_of(cb); }
+        if ((word & 0x7fu) && x + 1 < L.NX && y + 1 < L.NY && z + 1 < L.NZ) {
+            cb = cube_bits(word);                                                     // kObserved: right for every corner of a tetrahedron that emits
+            if (kObserved) { nb = cube_nan_bits(word); nt = triangles_of_observed(cb, nb); }
+            else nt = triangles_of(cb);
+        }
     }
     unsigned all;
     const unsigned tri_before = block_exclusive(nt, &all);
     // the vertices this point owns
     const unsigned mask = word & 0x7fu;
     if (mask) {
-        const int64_t first = vbase[blockIdx.x] + (int64_t)(word >> 8);
+        const int64_t first = vbase[blockIdx.x] + (int64_t)((word >> 8) & kPrefixMask);
         const float a = values[lin];
         float ga[3];
         ga[0] = lattice_difference(values, lin, x, L.NX, L.sx);
@@ -285,6 +339,7 @@ __global__ void __launch_bounds__(kThreads) surface_emit_kernel(const float *__r
         int64_t r = tbase[blockIdx.x] + (int64_t)tri_before;
 #pragma unroll 1
         for (int k = 0; k < 6; ++k) {
+            if (kObserved && !tet_observed(nb, k)) continue;
             uint64_t e = kCases.e[k][tet_case(cb, k)];
             const int n = (int)(e & 3u);
             e >>= 2;
@@ -490,9 +545,10 @@ extern "C" int64_t mnf_surface_extract_workspace_bytes(int32_t cells_x, int32_t 
     return carve_extract(nullptr, L.n, blocks_for(L.n)).bytes;
 }
 
-extern "C" int mnf_surface_extract(const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
-                                   const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals,
-                                   int32_t *triangles, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+// both entries: `observed` picks the kernels' rule for NaN
+static int surface_extract(bool observed, const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
+                           const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals, int32_t *triangles,
+                           int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
     Lattice L;
     MNF_REQUIRE(make_lattice(cells_x, cells_y, cells_z, &L), "surface_extract: cells per axis must lie in 1 .. %d (got %d x %d x %d)", kMaxCells, cells_x,
                 cells_y, cells_z);
@@ -517,17 +573,36 @@ extern "C" int mnf_surface_extract(const float *values, int32_t cells_x, int32_t
     Frame F;
     for (int k = 0; k < 3; ++k) { F.o[k] = origin_host[k]; F.s[k] = step_host[k]; }
     hipStream_t s = as_stream(stream);
-    ProfScope prof("surface_extract", s);
-    hipLaunchKernelGGL(surface_count_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, w.words, w.vblock, w.tblock);
+    ProfScope prof(observed ? "surface_extract_observed" : "surface_extract", s);
+    if (observed) hipLaunchKernelGGL(surface_count_kernel<true>, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, w.words, w.vblock, w.tblock);
+    else hipLaunchKernelGGL(surface_count_kernel<false>, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, w.words, w.vblock, w.tblock);
     int rc = launch_status("surface_count_kernel");
     if (rc) return rc;
     rc = mnf_exclusive_scan_i64(w.vblock, nb, w.vbase, w.totals, w.scan, scan_bytes(nb), stream);
     if (rc) return rc;
     rc = mnf_exclusive_scan_i64(w.tblock, nb, w.tbase, w.totals + 1, w.scan, scan_bytes(nb), stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(surface_emit_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, F, w.words, w.vbase, w.tbase, w.totals, max_vertices,
-                       max_triangles, positions, normals, triangles, info);
+    if (observed)
+        hipLaunchKernelGGL(surface_emit_kernel<true>, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, F, w.words, w.vbase, w.tbase, w.totals,
+                           max_vertices, max_triangles, positions, normals, triangles, info);
+    else
+        hipLaunchKernelGGL(surface_emit_kernel<false>, dim3((unsigned)nb), dim3(kThreads), 0, s, values, L, iso, F, w.words, w.vbase, w.tbase, w.totals,
+                           max_vertices, max_triangles, positions, normals, triangles, info);
     return launch_status("surface_emit_kernel");
+}
+
+extern "C" int mnf_surface_extract(const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
+                                   const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals,
+                                   int32_t *triangles, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    return surface_extract(false, values, cells_x, cells_y, cells_z, iso, origin_host, step_host, max_vertices, max_triangles, positions, normals, triangles,
+                           info, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mnf_surface_extract_observed(const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
+                                            const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals,
+                                            int32_t *triangles, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream) {
+    return surface_extract(true, values, cells_x, cells_y, cells_z, iso, origin_host, step_host, max_vertices, max_triangles, positions, normals, triangles,
+                           info, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mnf_surface_measure(const float *positions, const int32_t *triangles, const int64_t *info, int64_t max_vertices, int64_t max_triangles,

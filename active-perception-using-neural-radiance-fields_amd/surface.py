@@ -114,7 +114,7 @@ def load_ply(path):
             "colour": np.stack([v["red"], v["green"], v["blue"]], axis=1), "label": v["label"].copy(), "triangles": f["v"].copy()}
 
 
-def _extract_call(values, cells, iso, origin, step, max_v, max_t):
+def _extract_call(values, cells, iso, origin, step, max_v, max_t, observed=False):
     lib = L.load_library()
     dev = values.device
     nbytes = int(lib.mnf_surface_extract_workspace_bytes(*cells))
@@ -128,17 +128,19 @@ def _extract_call(values, cells, iso, origin, step, max_v, max_t):
         # a plain temporary, not the per-stream workspace cache: it is lattice-sized (4.1 B per point: 557 MB for 513^3) and a one-off mesh
         # export must not pin that through later training or rendering; torch's allocator takes it back when the call's tensors go
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        L.launch(lib.mnf_surface_extract, L.ptr(values), *cells, float(iso), origin, step, max_v, max_t, L.ptr(pos) if max_v else None,
+        L.launch(lib.mnf_surface_extract_observed if observed else lib.mnf_surface_extract, L.ptr(values), *cells, float(iso), origin, step, max_v, max_t, L.ptr(pos) if max_v else None,
                  L.ptr(nrm) if max_v else None, L.ptr(tri) if max_t else None, L.ptr(info), L.ptr(ws), nbytes)
     return pos, nrm, tri, info
 
 
 @torch.no_grad()
-def extract_lattice_surface(values, iso, origin, step, max_vertices=None, max_triangles=None):
+def extract_lattice_surface(values, iso, origin, step, max_vertices=None, max_triangles=None, observed=False):
     """The iso-surface of a float32 device lattice `values` [X+1, Y+1, Z+1] (x slowest) by marching tetrahedra: a point is inside where
     value > iso; vertex positions are (index + t) * step + origin.  -> SurfaceMesh of device tensors cut to the counts.  With no
     capacity given, a counting pass sizes the outputs (one small host copy); a given capacity that overflows raises an MnfError that
-    names the count and the capacity.  The mesh is open where matter touches the lattice boundary."""
+    names the count and the capacity.  The mesh is open where matter touches the lattice boundary.  `observed=True` takes a NaN point as
+    UNOBSERVED instead of outside (`mnf_surface_extract_observed`, what a TSDF lattice needs): no edge with a NaN end carries a vertex and
+    no tetrahedron with a NaN corner a triangle, so the mesh is open where nothing was observed; a vertex no triangle uses may remain."""
     L.require_gpu(values)
     if values.dim() != 3:
         raise ValueError(f"values is [X+1, Y+1, Z+1] (got {tuple(values.shape)})")
@@ -147,11 +149,11 @@ def extract_lattice_surface(values, iso, origin, step, max_vertices=None, max_tr
     o, _ = _f3(origin)
     s, _ = _f3(step)
     if max_vertices is None or max_triangles is None:
-        counts = _extract_call(v, cells, iso, o, s, 0, 0)[3].cpu().numpy()
+        counts = _extract_call(v, cells, iso, o, s, 0, 0, observed)[3].cpu().numpy()
         max_vertices = int(counts[0]) if max_vertices is None else int(max_vertices)
         max_triangles = int(counts[1]) if max_triangles is None else int(max_triangles)
     max_vertices, max_triangles = int(max_vertices), int(max_triangles)
-    pos, nrm, tri, info = _extract_call(v, cells, iso, o, s, max_vertices, max_triangles)
+    pos, nrm, tri, info = _extract_call(v, cells, iso, o, s, max_vertices, max_triangles, observed)
     host = info.cpu().numpy()
     if host[2] or host[3]:
         raise L.MnfError(f"the surface has {int(host[0])} vertices and {int(host[1])} triangles: more than max_vertices = {max_vertices} / "

@@ -1479,6 +1479,91 @@ int mnf_pose_refine(mnf_field_t f, const uint8_t *binaries, const uint32_t *bitg
                     const mnf_train_opts *opts, const mnf_pose_opts *pose, double *loss_trace, int32_t *stalled, int64_t *counts_dev, int64_t max_marched,
                     int64_t max_kept, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
 
+/* ---------------------------------------------------------------- TSDF fusion of captures (csrc/tsdf.hip)
+ *
+ * The classical map any robotics stack builds from the same captures the field is trained on: a truncated signed distance volume fused
+ * from depth, colour and class images (Curless & Levoy 1996; KinectFusion), its lattice for mnf_surface_extract_observed, and the colour
+ * and class of mesh vertices.  This comment is the definition: every output byte follows from it (tests/tsdf_ref.py restates it).
+ *
+ * Volume.  Lattice points [X+1][Y+1][Z+1] with X = cells_x etc. (1 .. 1024 each), lin(p) = (x (Y+1) + y)(Z+1) + z, exactly the lattice of
+ * mnf_surface_extract; point i of an axis is at w = lo + (double)i * voxel (lo_host three host doubles, voxel a host double).  The state is
+ * four device arrays of one element per point, 16 bytes per point:
+ *   tsdf   f32    the running mean of min(1, sdf / trunc); 1 for a point never observed (the caller's initial value)
+ *   weight int32  observations so far, capped at max_weight; initially 0
+ *   word   uint32 r | g << 8 | b << 16 | class << 24 of one observation (the sensor's voxel word); initially anything
+ *   best   f32    the |sdf| of the observation that wrote `word`; -1 for none
+ *
+ * mnf_tsdf_integrate applies views 0 .. n_views - 1 in ascending order to every lattice point.  A view is c2w [3][4] float64 (rotation
+ * columns and position c, as mnf_sensor_views takes it) of a pinhole camera looking along -z with a double `focal` and width x height
+ * pixels; depth [n_views][height][width] is f32 (MNF_TSDF_DEPTH_F32) or f16 (MNF_TSDF_DEPTH_F16); colour uint8
+ * [n_views][height][width][colour_stride], colour_stride 3 or 4 (bytes 0..2 are r, g, b); classes uint8 (MNF_TSDF_CLASS_U8) or int64
+ * (MNF_TSDF_CLASS_I64) [n_views][height][width].  depth_mode is MNF_SENSOR_DEPTH_PLANAR (the depth is the distance along the camera's axis)
+ * or MNF_SENSOR_DEPTH_RAY (the length of the pixel's ray).  For a point and a view, in float64, every operation rounded separately (the
+ * unit is built without FMA contraction):
+ *    1. q_k = w_k - c_k.
+ *    2. xc = (q_0 R_00 + q_1 R_10) + q_2 R_20;  yc = (q_0 R_01 + q_1 R_11) + q_2 R_21;  zc = (q_0 R_02 + q_1 R_12) + q_2 R_22.
+ *    3. zd = -zc.  The view is SKIPPED unless zd > min_depth.
+ *    4. u = floor((xc / zd) * focal + (double)width * 0.5),  v = floor(((-yc) / zd) * focal + (double)height * 0.5): the inverse of the sensor's
+ *       pixel-centre convention.  Skipped unless 0 <= u < width and 0 <= v < height (a NaN fails); px = (int)u, py = (int)v.
+ *    5. d = the stored depth of pixel (py, px), widened exactly.  Skipped and counted (info[2]) when d is not finite, d <= 0 or d > max_depth.
+ *    6. along = zd (planar) or sqrt((q_0 q_0 + q_1 q_1) + q_2 q_2) (ray).
+ *    7. sdf = d - along.  Skipped and counted (info[3]) when sdf < -trunc.
+ *    8. s = min(1, sdf / trunc).
+ *    9. tsdf = (float)(((double)tsdf * (double)weight + s) / (double)(weight + 1)), with the weight BEFORE the update; info[0] counts the
+ *       observation, info[1] too when that weight was 0.
+ *   10. weight = min(weight + 1, max_weight).
+ *   11. With a = |sdf|: when a <= trunc and (best < 0 or (float)a < best): best = (float)a and word = the pixel's r, g, b and class.
+ *   12. A class outside [0, 255] (int64 layout) stores 255 and is counted (info[4]) each time such a word is stored.
+ * Nearest pixel, no interpolation; one truncation for the whole volume; colour and class are those of the observation closest to the
+ * surface, not an average.
+ * info [5] int64 += {observations applied, points observed for the first time, invalid depths, observations behind the surface, labels out
+ * of range}: the caller clears it.  Only these are counted: none depends on how a kernel culls (a kernel may skip only work that changes
+ * nothing: a view that misses the volume leaves every byte and every counter as it was; there is no cull on max_depth, because a far point
+ * that projects onto a pixel still counts as behind the surface or as an invalid depth).  No atomics touch the state: the same inputs give
+ * the same bytes, and n_views views in one call give the bytes of n_views calls of one view each, in order.  The state arrays must not
+ * overlap the images.
+ *
+ * mnf_tsdf_lattice.  values [X+1][Y+1][Z+1] f32: -tsdf where weight >= min_weight (>= 1), else NaN: inside (value > 0) is behind a surface,
+ * the iso-surface at 0 is the fused surface, NaN is UNOBSERVED (mnf_surface_extract_observed).  counts [3] int64 (overwritten) = {points with
+ * weight >= min_weight, those of them with tsdf < 0, points with best >= 0}.
+ *
+ * mnf_tsdf_vertex_attrs.  positions [n][3] f32 -> colour [n][3] uint8, label [n] int32 and, with a palette [n_palette][3] uint8,
+ * sem_colour [n][3] uint8 (any output may be NULL).  The cell of a vertex is c_k = floor(((double)pos_k - lo_k) / voxel) per axis in
+ * float64, clamped into 0 .. cells_k - 1 (a NaN gives 0).  Of the cell's 8 corners the one with best >= 0 and the smallest best gives its
+ * word (ties go to the lowest lin): colour = its r, g, b, label = its class byte, sem_colour = palette[label], or (0,0,0) where label >=
+ * n_palette.  With no such corner: colour 0, label -1, sem_colour 0.
+ *
+ * mnf_surface_extract_observed (csrc/surface.hip): mnf_surface_extract with ONE rule changed.  A NaN lattice point is UNOBSERVED rather
+ * than outside: an edge carries a vertex only when its ends differ in inside-ness AND neither end is NaN; a tetrahedron emits its triangles
+ * only when none of its four vertices is NaN.  Order, arithmetic, normals, capacities, workspace and info are those of mnf_surface_extract,
+ * and on a lattice without NaN the outputs are the same bytes.  A vertex that no triangle uses may remain (an edge between two observed
+ * points all of whose tetrahedra hold an unobserved one).  The mesh is open where nothing was observed.  The unchanged entry would wrap
+ * every observed region of a TSDF lattice in a shell of midpoint vertices.
+ *
+ * Argument errors (a null required pointer, cells outside 1 .. 1024, a lo, voxel, trunc or focal that is not finite or (the last three) not
+ * positive, min_depth negative or not finite, max_depth not above min_depth or not finite, max_weight or min_weight outside 1 .. 2^31 - 1,
+ * more than 65535 views or fewer than 0, an image wider or higher than 16384, a colour_stride other than 3 or 4, an unknown depth_type,
+ * class_type or depth_mode, a misaligned array, n outside [0, 2^31)) return MNF_ERR_INVALID before any HIP call.  n_views == 0 and n == 0
+ * return MNF_OK and do nothing.  Profile labels: "tsdf_integrate", "tsdf_lattice", "tsdf_vertex_attrs", "surface_extract_observed".  Every
+ * call enqueues on `stream` and none synchronises.  There is no CPU fallback. */
+#define MNF_TSDF_DEPTH_F32 0
+#define MNF_TSDF_DEPTH_F16 1
+#define MNF_TSDF_CLASS_U8 0
+#define MNF_TSDF_CLASS_I64 1
+#define MNF_TSDF_MAX_VIEWS 65535
+int mnf_tsdf_integrate(float *tsdf, int32_t *weight, uint32_t *word, float *best, int32_t cells_x, int32_t cells_y, int32_t cells_z,
+                       const double *lo_host, double voxel, double trunc, int32_t max_weight, double min_depth, double max_depth, const double *c2w,
+                       int32_t n_views, int32_t width, int32_t height, double focal, const void *depth, int32_t depth_type, const uint8_t *colour,
+                       int32_t colour_stride, const void *classes, int32_t class_type, int32_t depth_mode, int64_t *info, mnf_stream_t stream);
+int mnf_tsdf_lattice(const float *tsdf, const int32_t *weight, const float *best, int32_t cells_x, int32_t cells_y, int32_t cells_z,
+                     int32_t min_weight, float *values, int64_t *counts, mnf_stream_t stream);
+int mnf_tsdf_vertex_attrs(const uint32_t *word, const float *best, int32_t cells_x, int32_t cells_y, int32_t cells_z, const double *lo_host,
+                          double voxel, const float *positions, int64_t n, const uint8_t *palette, int32_t n_palette, uint8_t *colour, int32_t *label,
+                          uint8_t *sem_colour, mnf_stream_t stream);
+int mnf_surface_extract_observed(const float *values, int32_t cells_x, int32_t cells_y, int32_t cells_z, float iso, const float *origin_host,
+                                 const float *step_host, int64_t max_vertices, int64_t max_triangles, float *positions, float *normals,
+                                 int32_t *triangles, int64_t *info, void *workspace, int64_t workspace_bytes, mnf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

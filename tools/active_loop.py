@@ -11,11 +11,16 @@ With `--pose-noise DEG,CM` every capture of a planning step arrives with a drift
 along a random direction) and is relocalised against the current field before it is trained on (`localize.PoseRefiner`, all views of the step in one batch);
 the step's line then carries the mean pose error before and after.  The initial sweep keeps its poses: there is no map to relocalise against yet.
 
+With `--tsdf` every batch of captures is also fused into a `tsdf.TsdfVolume` at the world's 10 cm (from the dataset's own storage and poses), and each
+step's line gains the observed fraction of its lattice, the triangle count of its mesh, and the accuracy and completion of the field's mesh
+(`extract_surface` at iso = occ_thre / render_step_size) against points sampled from the TSDF mesh every 5 cm.  Without the flag every line stays as it is.
+
 One line per planning step.  The whole run is one child process under `timeout`; the driver starts no GPU work itself.  Nothing here is a
 measurement of speed and nothing is asserted: it shows the stages joined end to end on the device.
 
     python tools/active_loop.py [--steps 3] [--out profiles/active_loop.txt]
     python tools/active_loop.py --pose-noise 1,3 --out profiles/active_loop_pose_noise.txt
+    python tools/active_loop.py --tsdf --out profiles/active_loop_tsdf.txt
 """
 import argparse
 import os
@@ -42,7 +47,7 @@ def pose_errors(c2w, truth):
     return float(ang.mean()), float(100.0 * np.linalg.norm(c2w[:, :3, 3] - truth[:, :3, 3], axis=1).mean())
 
 
-def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40):
+def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40, tsdf=False):
     import torch
     from apnrf_amd import localize as LZ
     from apnrf_amd import clearance as CL
@@ -68,6 +73,24 @@ def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40):
     opt = FusedAdam(field.parameters(), lr=2e-3, eps=1e-15).bind_field(field)
     data = Dataset(training=True, save_fp="", num_rays=1024, device=DEV)
     cost = PL.ScanCostMap(AABB, CELL, device=DEV)
+    fused = None
+    if tsdf:
+        from apnrf_amd import cloud as CD
+        from apnrf_amd import surface as SF
+        from apnrf_amd.tsdf import TsdfVolume
+        fused = TsdfVolume(AABB, world.voxel_size, device=DEV)
+
+    def tsdf_report():
+        """The classical map beside the neural one: the field's mesh against points on the TSDF mesh."""
+        counts = fused.counts()
+        classical = fused.extract_mesh()
+        text = f"; tsdf {100.0 * counts['observed_fraction']:.1f} % observed, {classical.n_triangles} triangles"
+        neural = SF.extract_surface(field.eval(), est.eval(), 1e-2 / KW["render_step_size"])
+        if classical.n_triangles == 0 or neural.n_triangles == 0:
+            return text + f", field mesh {neural.n_triangles} triangles: nothing to compare"
+        points = CD.sample_mesh_points(classical, resolution=0.05)[0]
+        q = CD.mesh_quality(neural, points, resolution=0.05, threshold=0.1, r_max=0.5)
+        return text + f", field mesh {neural.n_triangles} triangles: accuracy {q['accuracy']:.3f} m, completion {q['completion']:.3f} m against the tsdf mesh"
     c2w_of = lambda poses: torch.from_numpy(np.stack([RD.pose_to_c2w(p) for p in np.asarray(poses, np.float64).reshape(-1, 7)])).to(DEV)
 
     noise_rng = np.random.default_rng(seed + 1)      # (its own stream: the loop's draws are the same with and without the leg)
@@ -95,6 +118,8 @@ def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40):
             report = pose_errors(noisy, truth) + pose_errors(out["c2w"], truth) + (int(out["stalled"].max()), out["status"])
         else:
             data.update_data(rgba[..., :3], depth_ray, sem, c2w)
+        if fused is not None:
+            fused.integrate_dataset(data, list(range(len(data) - int(c2w.shape[0]), len(data))), depth_along="ray")
         cost.update(planar, c2w)
         return report
 
@@ -154,7 +179,7 @@ def run(steps, train_steps, n_goals, seed, pose_noise=None, refine_iters=40):
               f"{min(scores):.3f} .. {max(scores):.3f}, flew curve {cand['kept'][best]} of {len(traj)} poses to ({current[0]:.2f}, {current[1]:.2f}, {current[2]:.2f}); "
               f"{len(data)} views, {done[0]} train steps: held-out PSNR {ev['psnr']:.2f}, depth MSE {ev['depth_mse']:.4f}; sensor misses {int(sim.info[0])}"
               + ("" if report is None else f"; pose error of the {len(views)} captures {report[0]:.2f} deg, {report[1]:.2f} cm -> {report[2]:.2f} deg, {report[3]:.2f} cm after "
-                 f"{refine_iters} iterations (stalled at most {report[4]}, status {report[5]})"), flush=True)
+                 f"{refine_iters} iterations (stalled at most {report[4]}, status {report[5]})") + (tsdf_report() if fused is not None else ""), flush=True)
 
 
 def main():
@@ -164,6 +189,7 @@ def main():
     ap.add_argument("--goals", type=int, default=6)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--pose-noise", default=None, metavar="DEG,CM", help="perturb the pose of every capture of a planning step and refine it against the field first")
+    ap.add_argument("--tsdf", action="store_true", help="fuse every batch of captures into a TSDF volume too and compare the field's mesh with its mesh")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help="(internal) run the loop in this process")
     a = ap.parse_args()
@@ -172,14 +198,15 @@ def main():
         if not torch.cuda.is_available():
             raise SystemExit("active_loop needs a GPU")
         import apnrf_amd  # noqa: F401
-        run(a.steps, a.train_steps, a.goals, a.seed, tuple(float(x) for x in a.pose_noise.split(",")) if a.pose_noise else None)
+        run(a.steps, a.train_steps, a.goals, a.seed, tuple(float(x) for x in a.pose_noise.split(",")) if a.pose_noise else None, tsdf=a.tsdf)
         return
     r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--child", "--steps", str(a.steps), "--train-steps", str(a.train_steps),
-                        "--goals", str(a.goals), "--seed", str(a.seed)] + (["--pose-noise", a.pose_noise] if a.pose_noise else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                        "--goals", str(a.goals), "--seed", str(a.seed)] + (["--pose-noise", a.pose_noise] if a.pose_noise else []) + (["--tsdf"] if a.tsdf else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     body = [ln for ln in r.stdout.splitlines() if ln.strip() and "amdgpu.ids" not in ln]
     head = (f"# the active-mapping loop at small sizes: a closed {AABB[3] - AABB[0]:.0f} x {AABB[4] - AABB[1]:.1f} x {AABB[5] - AABB[2]:.0f} m procedural world at 10 cm voxels, "
             f"{SIDE} x {SIDE} captures, one 128 x 2 field with a 2^14 table; {a.steps} planning steps, seed {a.seed}"
-            + (f"; captures arrive with {a.pose_noise} (deg, cm) of pose noise and are relocalised first" if a.pose_noise else ""))
+            + (f"; captures arrive with {a.pose_noise} (deg, cm) of pose noise and are relocalised first" if a.pose_noise else "")
+            + ("; every batch of captures is also fused into a TSDF volume at 10 cm (trunc 40 cm, nearest pixel)" if a.tsdf else ""))
     text = "\n".join([head] + (body if r.returncode == 0 else body[-25:] + [f"# the loop ended with status {r.returncode}"]))
     print(text)
     if a.out:

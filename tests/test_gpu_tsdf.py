@@ -10,7 +10,12 @@ holds planted NaN, inf, 0 and over-range depths, and the int64 layout a class of
 In planar mode everything is `array_equal` to the restatement: both sides round every float64 operation separately and in the same order,
 and IEEE division is correctly rounded on both.  In ray mode `along` is a float64 square root; the device's is assumed correctly rounded,
 not bit-equal to numpy's (as tests/test_gpu_sensor.py assumes of the sensor's), so `tsdf` and `best` are held to one float32 ulp there and
-weight, word and info to the byte; the test prints whether the bytes were equal after all (on one MI355X they were, in both layouts)."""
+weight, word and info to the byte; the test prints whether the bytes were equal after all (on one MI355X they were, in both layouts).
+
+The second group leaves the yaw poses: 24 general poses (no rotation entry is 0 or 1, so every index of the point chain and of the block
+cull matters), the same under a skew (the cull's bound needs the column norms), min_depth and max_depth that bind, three degenerate poses,
+and a list of 600 views (more than one wave of survivors per block, a second and a third chunk, a block first reached in the second chunk
+and one never reached, views that tie in |sdf| across waves).  tests/test_tsdf_cpu.py shows that these inputs reach those cases."""
 import ctypes
 
 import numpy as np
@@ -77,8 +82,9 @@ def fresh(max_weight=64):
     return T.Volume(CELLS, T.ROOM_LO, S, TRUNC, max_weight=max_weight)
 
 
-def gpu_integrate(vol, c2w, depth, colour, classes, mode, one_by_one=False):
-    """mnf_tsdf_integrate on a copy of `vol`'s state -> a Volume holding what the device left.  Twice; the same bytes both times."""
+def gpu_integrate(vol, c2w, depth, colour, classes, mode, one_by_one=False, calls=None):
+    """mnf_tsdf_integrate on a copy of `vol`'s state -> a Volume holding what the device left.  Twice; the same bytes both times.  `calls`
+    is a list of view counts, one call each, in order (all views in one call when None)."""
     L, lib = _lib()
     n = int(np.prod(vol.shape))
     V, H, W = depth.shape
@@ -89,7 +95,9 @@ def gpu_integrate(vol, c2w, depth, colour, classes, mode, one_by_one=False):
         for (whole, part), init in zip(bufs, (vol.tsdf, vol.weight, vol.word.view(np.int32), vol.best, vol.info)):
             part.copy_(_dev(init.reshape(-1)))
         t, w, wd, b, info = (p for _, p in bufs)
-        for lo_v, hi_v in ([(v, v + 1) for v in range(V)] if one_by_one else [(0, V)]):
+        ends = np.cumsum([1] * V if one_by_one else [V] if calls is None else calls).tolist()
+        assert ends[-1:] == [V] or V == 0
+        for lo_v, hi_v in zip([0] + ends[:-1], ends):
             L.launch(lib.mnf_tsdf_integrate, L.ptr(t), L.ptr(w), L.ptr(wd), L.ptr(b), *vol.cells, _c3(vol.lo), float(vol.voxel), float(vol.trunc), vol.max_weight,
                      float(vol.min_depth), float(vol.max_depth), L.ptr(d_m[lo_v:hi_v]), hi_v - lo_v, W, H, T.FOCAL, L.ptr(d_d[lo_v:hi_v]),
                      1 if depth.dtype == np.float16 else 0, L.ptr(d_c[lo_v:hi_v]), colour.shape[-1], L.ptr(d_k[lo_v:hi_v]), 1 if classes.dtype == np.int64 else 0,
@@ -154,6 +162,123 @@ def test_a_view_that_misses_changes_nothing():
         assert getattr(after, k).tobytes() == getattr(before, k).tobytes(), k
     none = gpu_integrate(before, c2w[:0], depth[:0], colour[:0], classes[:0], T.PLANAR)                  # n_views == 0
     assert none.tsdf.tobytes() == before.tsdf.tobytes() and none.info.tolist() == before.info.tolist()
+
+
+# ------------------------------------------------------------------ general poses, skewed poses, the near plane, view lists beyond one wave
+STATE = ("tsdf", "weight", "word", "best", "info")
+
+
+def _assert_equals_restatement(got, want, mode, what):
+    """The file's rule: planar mode to the byte; ray mode tsdf and best within one float32 ulp, the rest to the byte."""
+    np.testing.assert_array_equal(got.weight, want.weight, err_msg=what)
+    np.testing.assert_array_equal(got.word, want.word, err_msg=what)
+    np.testing.assert_array_equal(got.info, want.info, err_msg=what)
+    if mode == T.PLANAR:
+        assert _same_bits(got.tsdf, want.tsdf) and _same_bits(got.best, want.best), what
+    else:
+        print(f"ray mode, {what}: tsdf bytes equal {_same_bits(got.tsdf, want.tsdf)}, best bytes equal {_same_bits(got.best, want.best)}")
+        assert _within_one_ulp(got.tsdf, want.tsdf) and _within_one_ulp(got.best, want.best), what
+
+
+def _assert_same_state(a, b, what):
+    for k in STATE:
+        assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), (what, k)
+
+
+def general(mode, layout):
+    """`tsdf_ref.general_captures` in storage layout "wide" (RGBA / f32 / i64 with a patch of class 300) or "packed" (RGB / f16 / u8)."""
+    c2w, depth, rgba, sem = T.general_captures(mode)
+    if layout == "wide":
+        sem = sem.astype(np.int64)
+        sem[3, 4:12, 6:18] = 300
+        return c2w, depth, rgba, sem
+    return c2w, depth.astype(np.float16), np.ascontiguousarray(rgba[..., :3]), sem
+
+
+def worded(max_weight=3, **kw):
+    """A fresh volume whose words are not 0: the header leaves the initial word to the caller, and a point nothing reaches keeps it."""
+    vol = T.volume(max_weight, **kw)
+    vol.word = (np.arange(vol.word.size, dtype=np.uint32) * np.uint32(2654435761) | np.uint32(1)).reshape(vol.shape)
+    return vol
+
+
+@pytest.mark.parametrize("layout", ["wide", "packed"])
+@pytest.mark.parametrize("mode", [T.PLANAR, T.RAY])
+def test_general_poses_equal_the_restatement(mode, layout):
+    """24 poses none of whose rotation entries is below 0.05 in magnitude: every index of the point chain and of the cull matters."""
+    c2w, depth, colour, classes = general(mode, layout)
+    want = T.integrate(worded(), c2w, T.FOCAL, depth, colour, classes, mode)
+    got = gpu_integrate(worded(), c2w, depth, colour, classes, mode)
+    assert want.info[0] > 3000 and want.info[3] > 0 and (want.weight == 3).any() and want.info[0] > want.weight.sum() and (want.info[4] > 0) == (layout == "wide")
+    _assert_equals_restatement(got, want, mode, f"general poses, {layout}")
+
+
+@pytest.mark.parametrize("mode", [T.PLANAR, T.RAY])
+def test_skewed_poses_equal_the_restatement(mode):
+    """The same captures under poses whose columns have norms 0.6, 1.04 and 1.9 and a shear: a cull that left the norms out of its bound
+    drops points the header admits (tests/test_tsdf_cpu.py counts them).  The images mean nothing under such a pose; the bytes are held."""
+    c2w, depth, colour, classes = general(mode, "wide")
+    c2w = T.skewed(c2w)
+    want = T.integrate(worded(), c2w, T.FOCAL, depth, colour, classes, mode)
+    got = gpu_integrate(worded(), c2w, depth, colour, classes, mode)
+    assert want.info[0] > 1000
+    _assert_equals_restatement(got, want, mode, "skewed poses")
+
+
+def test_min_depth_equals_the_restatement():
+    """min_depth = 0.4 (step 3, and the cull's near plane) and max_depth = 0.6, below some stored depths (step 5)."""
+    for mode in (T.PLANAR, T.RAY):
+        c2w, depth, colour, classes = general(mode, "packed")
+        assert (depth.astype(np.float32) > 0.6).any()
+        want = T.integrate(worded(min_depth=0.4, max_depth=0.6), c2w, T.FOCAL, depth, colour, classes, mode)
+        loose = T.integrate(worded(), c2w, T.FOCAL, depth, colour, classes, mode)
+        assert 0 < want.info[0] < loose.info[0] and want.info[2] > loose.info[2]
+        got = gpu_integrate(worded(min_depth=0.4, max_depth=0.6), c2w, depth, colour, classes, mode)
+        _assert_equals_restatement(got, want, mode, "min_depth 0.4")
+
+
+@pytest.mark.parametrize("mode", [T.PLANAR, T.RAY])
+def test_six_hundred_views_equal_the_restatement(mode):
+    """Two full chunks of 256 views and one of 88 (tests/test_tsdf_cpu.py says what they reach: blocks with more than 64 survivors from
+    all four waves, a block first reached in the second chunk, a block never reached, tied views in different waves).  One call, 600
+    calls and calls of 256 + 256 + 88 views give the same bytes, which are the restatement's."""
+    c2w, depth, colour, classes = T.view_list(600, mode)
+    want = T.integrate(worded(), c2w, T.FOCAL, depth, colour, classes, mode)
+    one = gpu_integrate(worded(), c2w, depth, colour, classes, mode)
+    if mode == T.PLANAR:
+        _assert_equals_restatement(one, want, mode, "600 views in one call")
+    else:                                                                        # a square root one ulp off numpy's may compound over 600 views: the three device runs are held to each other
+        print("ray mode, 600 views: bytes equal the restatement's: " + ", ".join(f"{k} {_same_bits(getattr(one, k), getattr(want, k))}" for k in STATE))
+    _assert_same_state(gpu_integrate(worded(), c2w, depth, colour, classes, mode, one_by_one=True), one, "600 calls")
+    _assert_same_state(gpu_integrate(worded(), c2w, depth, colour, classes, mode, calls=[256, 256, 88]), one, "256 + 256 + 88")
+    index, _ = T.block_table(one)
+    never, start = index == T.B_NEVER, worded()
+    assert never.sum() == 4 * 4 * 6 and (one.weight[index == T.B_LATE] > 0).any()
+    for k in STATE[:4]:
+        assert getattr(one, k)[never].tobytes() == getattr(start, k)[never].tobytes(), f"{k} of a block no view reaches"
+
+
+def test_degenerate_poses_change_nothing_and_stop_nothing():
+    """A pose holding a NaN, a camera infinitely far away and a camera exactly on a lattice point (q = 0 there: zd is 0 and xc / zd a NaN),
+    in the middle of the general set.  The header defines all three: a NaN fails steps 3-4."""
+    c2w, depth, colour, classes = general(T.PLANAR, "wide")
+    nan_pose, far_pose, on_point = c2w[5].copy(), c2w[6].copy(), c2w[7].copy()
+    nan_pose[1, 1] = np.nan
+    far_pose[0, 3] = np.inf
+    on_point[:, 3] = T.volume().points()[9, 4, 12]
+    at = [0, 1, 2]
+    put = lambda a, extra: np.concatenate([a[:12], extra, a[12:]])
+    m = put(c2w, np.stack([nan_pose, far_pose, on_point]))
+    d, c, k = (put(a, a[at]) for a in (depth, colour, classes))
+    want = T.integrate(worded(), m, T.FOCAL, d, c, k, T.PLANAR)
+    assert not T.project(T.volume(), on_point, T.W, T.H, T.FOCAL)[0][9, 4, 12] and T.project(T.volume(), on_point, T.W, T.H, T.FOCAL)[0].any()
+    got = gpu_integrate(worded(), m, d, c, k, T.PLANAR)
+    _assert_equals_restatement(got, want, T.PLANAR, "degenerate poses")
+    keep = np.r_[0:12, 14:27]
+    without = gpu_integrate(worded(), m[keep], d[keep], c[keep], k[keep], T.PLANAR)
+    _assert_same_state(got, without, "the NaN and the infinite pose removed")
+    alone = gpu_integrate(worded(), m[12:14], d[12:14], c[12:14], k[12:14], T.PLANAR)
+    _assert_same_state(alone, worded(), "the NaN and the infinite pose alone")
 
 
 # ------------------------------------------------------------------ lattice, mesh, attributes
@@ -403,6 +528,38 @@ def test_volume_end_to_end(tmp_path):
     assert vol.info()["applied"] == 0 and vol.counts()["observed"] == 0 and vol.extract_mesh().n_triangles == 0
     with pytest.raises(L_error()):
         TsdfVolume(aabb, S, device="cpu")
+
+
+def test_volume_takes_six_hundred_float32_poses(tmp_path):
+    """`TsdfVolume.integrate` with the 600 views' poses as a float32 [V,4,4] device tensor is the C ABI on the float32-rounded poses, and
+    `integrate_dataset` with an id list of three runs (one longer than a chunk, out of order) is `integrate` on the gathered views."""
+    from apnrf_amd.dataset import Dataset
+    from apnrf_amd.tsdf import TsdfVolume
+    c2w, depth, rgba, sem = T.view_list(600, T.PLANAR)
+    c2w32 = c2w.astype(np.float32)
+    m44 = np.concatenate([c2w32, np.broadcast_to(np.array([0, 0, 0, 1], np.float32), (600, 1, 4))], axis=1)
+    aabb = np.concatenate([T.ROOM_LO, T.ROOM_LO + np.asarray(CELLS) * S])
+    vol = TsdfVolume(aabb, S, max_weight=3, device=DEV)
+    vol.integrate(_dev(depth), _dev(rgba), _dev(sem), _dev(m44), T.FOCAL, depth_along="z")
+    want = gpu_integrate(fresh(3), c2w32.astype(np.float64), depth, rgba, sem, T.PLANAR)
+    assert want.info[0] > 100000 and (c2w32.astype(np.float64) != c2w).any()
+    assert list(vol.info().values()) == want.info.tolist()
+    for k in ("tsdf", "weight", "best"):
+        assert getattr(vol, k).cpu().numpy().tobytes() == getattr(want, k).tobytes(), k
+    assert vol.word.cpu().numpy().view(np.uint32).tobytes() == want.word.tobytes()
+    ids = list(range(280, 600)) + list(range(0, 260)) + list(range(270, 280))
+    order = torch.tensor(ids, device=DEV)
+    for packed in (False, True):
+        ds = Dataset(training=False, save_fp=str(tmp_path / f"d{int(packed)}"), device=DEV, packed=packed)
+        ds.update_data(_dev(np.ascontiguousarray(rgba[..., :3])), _dev(depth), _dev(sem), _dev(c2w32))
+        assert float(ds.K[0, 0]) == T.FOCAL
+        a = TsdfVolume(aabb, S, max_weight=3, device=DEV)
+        a.integrate_dataset(ds, ids)
+        b = TsdfVolume(aabb, S, max_weight=3, device=DEV)
+        b.integrate(ds.depths[order], ds.images[order], ds.semantics[order], ds.camtoworlds[order], T.FOCAL)
+        for k in ("tsdf", "weight", "word", "best", "info_device"):
+            assert torch.equal(getattr(a, k), getattr(b, k)), (packed, k)
+        assert a.info()["applied"] > 100000 and not torch.equal(a.tsdf, vol.tsdf), "the order of the runs is the order of fusion"
 
 
 def L_error():

@@ -1,6 +1,9 @@
 """tests/tsdf_ref.py, the numpy restatement of TSDF fusion (include/mi355nerf.h "TSDF fusion of captures"), held to things it shares no code
 with: the closed form of a wall seen head on, the geometry of a closed room (every point the volume calls inside lies near matter), the
-rules of the observed-only extraction, and a vectorised search for the vertex attributes.  No GPU."""
+rules of the observed-only extraction, and a vectorised search for the vertex attributes; under general rotations, to the sensor's own
+pixel rays and to the closed form of a tilted plane.  The last group shows that the inputs of tests/test_gpu_tsdf.py discriminate: what
+the 600-view list reaches in a kernel that culls views per block 256 at a time, that skewed poses need the column norms, that min_depth
+binds.  No GPU."""
 import functools
 
 import numpy as np
@@ -190,6 +193,256 @@ def test_vertex_attrs_against_a_vectorised_search():
     colour = np.where(none[:, None], 0, np.stack([word & 0xFF, (word >> 8) & 0xFF, (word >> 16) & 0xFF], axis=1)).astype(np.uint8)
     assert np.array_equal(got["label"], label) and np.array_equal(got["colour"], colour) and none.any() and (~none).sum() > 100
     assert np.array_equal(got["sem_colour"], np.where((label >= 0)[:, None], palette[np.maximum(label, 0)], 0).astype(np.uint8))
+
+
+# ------------------------------------------------------------------ general poses: the restatement, and what the device tests' inputs reach
+def _integrate_before_project(vol, c2w, focal, depth, colour, classes, depth_mode):
+    """`tsdf_ref.integrate` as it stood before steps 1-4 moved into `tsdf_ref.project`, kept here word for word."""
+    F32, F64 = np.float32, np.float64
+    m = np.asarray(c2w, F64).reshape(-1, 3, 4)
+    V, H, W = depth.shape
+    f = F64(focal)
+    w = vol.points()
+    with np.errstate(all="ignore"):
+        for v in range(V):
+            R, c = m[v, :, :3], m[v, :, 3]
+            q = w - c
+            q0, q1, q2 = q[..., 0], q[..., 1], q[..., 2]
+            xc = (q0 * R[0, 0] + q1 * R[1, 0]) + q2 * R[2, 0]
+            yc = (q0 * R[0, 1] + q1 * R[1, 1]) + q2 * R[2, 1]
+            zc = (q0 * R[0, 2] + q1 * R[1, 2]) + q2 * R[2, 2]
+            zd = -zc
+            ok = zd > vol.min_depth
+            u = np.floor((xc / zd) * f + F64(W) * 0.5)
+            vv = np.floor(((-yc) / zd) * f + F64(H) * 0.5)
+            ok &= (u >= 0) & (u < W) & (vv >= 0) & (vv < H)
+            px, py = np.where(ok, u, 0).astype(np.int64), np.where(ok, vv, 0).astype(np.int64)
+            d = depth[v][py, px].astype(F64)
+            invalid = ok & ~(np.isfinite(d) & (d > 0) & (d <= vol.max_depth))
+            vol.info[2] += int(invalid.sum())
+            ok &= ~invalid
+            along = np.sqrt((q0 * q0 + q1 * q1) + q2 * q2) if depth_mode == T.RAY else zd
+            sdf = d - along
+            behind = ok & (sdf < -vol.trunc)
+            vol.info[3] += int(behind.sum())
+            ok &= ~behind
+            s = np.minimum(1.0, sdf / vol.trunc)
+            wt = vol.weight.astype(F64)
+            new = ((vol.tsdf.astype(F64) * wt + s) / (wt + 1.0)).astype(F32)
+            vol.tsdf = np.where(ok, new, vol.tsdf)
+            vol.info[0] += int(ok.sum())
+            vol.info[1] += int((ok & (vol.weight == 0)).sum())
+            vol.weight = np.where(ok, np.minimum(vol.weight.astype(np.int64) + 1, vol.max_weight), vol.weight).astype(np.int32)
+            a = np.abs(sdf)
+            a32 = a.astype(F32)
+            take = ok & (a <= vol.trunc) & ((vol.best < 0) | (a32 < vol.best))
+            cls = classes[v][py, px].astype(np.int64)
+            out = (cls < 0) | (cls > 255)
+            vol.info[4] += int((take & out).sum())
+            cls = np.where(out, 255, cls)
+            col = colour[v][py, px]
+            word = SR.pack(col[..., 0], col[..., 1], col[..., 2], cls)
+            vol.best = np.where(take, a32, vol.best)
+            vol.word = np.where(take, word, vol.word).astype(np.uint32)
+    return vol
+
+
+STATE = ("tsdf", "weight", "word", "best", "info")
+
+
+def _same_state(a, b):
+    return all(getattr(a, k).tobytes() == getattr(b, k).tobytes() for k in STATE)
+
+
+def test_project_left_the_restatement_as_it_was():
+    """Factoring steps 1-4 out changed no byte: the earlier body, kept above, run beside `integrate` on the room's captures (yaw poses,
+    planted depths, an int64 class out of range, the cap) and on the general ones."""
+    for mode in (T.PLANAR, T.RAY):
+        c2w, depth, rgba, sem = T.room_captures(mode, repeats=2)
+        sem64 = sem.astype(np.int64)
+        sem64[0, 4:12, 6:18] = 300
+        for args in ((c2w, T.FOCAL, depth, rgba, sem64), (c2w, T.FOCAL, depth.astype(np.float16), rgba[..., :3], sem)):
+            a = T.integrate(T.volume(3), *args, mode)
+            b = _integrate_before_project(T.volume(3), *args, mode)
+            assert _same_state(a, b) and a.info[0] > 3000
+        g = T.general_captures(mode)
+        assert _same_state(T.integrate(T.volume(3), g[0], T.FOCAL, *g[1:], mode), _integrate_before_project(T.volume(3), g[0], T.FOCAL, *g[1:], mode))
+
+
+def test_general_poses_are_general():
+    c2w = T.general_poses()
+    R = c2w[:, :, :3]
+    assert c2w.shape == (24, 3, 4) and np.abs(R).min() >= T.MIN_ENTRY and np.abs(R).max() < 1
+    assert np.abs(np.einsum("vij,vik->vjk", R, R) - np.eye(3)).max() < 1e-14 and (np.linalg.det(R) > 0).all()
+    idx = np.floor((c2w[:, :, 3] - T.ROOM_LO) / S).astype(int)
+    centre = np.asarray(T.ROOM_SHAPE) // 2
+    outside = (np.abs(idx - centre) > np.array([2, 1, 2])).any(axis=1)
+    depth = T.general_captures(T.PLANAR)[1]
+    print(f"general poses: smallest rotation entry {np.abs(R).min():.4f}, {int(outside.sum())} of 24 cameras outside the free pocket, nearest hit "
+          f"{depth[depth > 0].min():.4f} m, {int((depth.reshape(24, -1).min(axis=1) < T.TRUNC).sum())} views hold a hit nearer than trunc")
+    assert outside.sum() >= 8 and (~outside).sum() >= 1 and (depth.reshape(24, -1).min(axis=1) < T.TRUNC).sum() >= 8
+    K = T.skewed(c2w)[:, :, :3]
+    n = np.linalg.norm(K, axis=1)
+    assert np.allclose(n, [0.6, np.sqrt(1.09), 1.9]) and np.abs(np.einsum("vi,vi->v", K[:, :, 0], K[:, :, 1])).min() > 0.1, "norms on both sides of 1, and a shear"
+    assert np.array_equal(T.skewed(c2w)[:, :, 3], c2w[:, :, 3])
+
+
+def test_project_inverts_the_sensor_under_general_poses():
+    """Points c + t dir(px, py) on the sensor's own pixel-centre rays (`sensor_ref.view_rays`) project into exactly (px, py): the ideal
+    image coordinate is px + 0.5, half a pixel from either floor boundary, and the float64 chain moves it by some 1e-14."""
+    c2w = T.general_poses()
+    o, d, _, _ = SR.view_rays(c2w, T.W, T.H, T.FOCAL)
+    vol = T.volume()
+    py, px = np.meshgrid(np.arange(T.H), np.arange(T.W), indexing="ij")
+    for v in range(len(c2w)):
+        for t in (0.05, 0.37, 1.0, 7.5):
+            ok, gx, gy, zd, _ = T.project(vol, c2w[v], T.W, T.H, T.FOCAL, o[v] + t * d[v])
+            assert ok.all() and np.array_equal(gx, px) and np.array_equal(gy, py), (v, t)
+            assert np.abs(zd - t).max() < 1e-13, "the camera's z component of dir is -1: planar depth is t"
+            behind = T.project(vol, c2w[v], T.W, T.H, T.FOCAL, o[v] - t * d[v])[0]
+            assert not behind.any()
+
+
+def test_tilted_plane_matches_the_closed_form():
+    """`test_wall_matches_the_closed_form` under general rotations.  A plane n . x = h tilted against the camera's axis by about 20
+    degrees (n is the view direction plus 0.3 of the camera's x axis and 0.2 of its y axis), 0.35 m ahead; pixel (px, py) looks along
+    dir = R k, k = (cam0, cam1, -1) from `sensor_ref.view_rays`, and meets the plane at t = (h - n . c) / (n . dir), which IS its planar
+    depth (k_z = -1); its ray depth is t |k|.  The image is that, in float64, stored as float32.  One view is fused, and every observed
+    point p holds tsdf = (float)min(1, (d(pixel(p)) - along(p)) / trunc), with pixel(p) and along(p) from k(p) = R^T (p - c) as a matrix
+    product, which shares no expression with `project`.
+
+    THE BOUND.  As for the wall.  t has a handful of float64 roundings (two dot products of three terms, a difference, a quotient, and
+    |k| for ray depth) on numbers below 2, and along(p), the difference and the quotient by trunc a handful more: below 32 * 2^-53 * 2 m
+    < 1e-14 m in all.  The depth is stored as float32: |d32 - d| <= 2^-24 d <= 2^-24 d_max.  The tsdf is stored as float32: 2^-24 |s|
+    <= 2^-24.  So
+        |tsdf - closed form| <= (2^-24 d_max + 1e-14) / trunc + 2^-24.
+    A point whose image coordinate lies within 1e-9 of a pixel boundary may be assigned to either pixel by either chain and is left out
+    (none is, with these poses); which points are observed is held too, away from the three thresholds by 1e-9."""
+    vol0 = T.volume()
+    pts = vol0.points()
+    trunc = float(vol0.trunc)
+    worst = {T.PLANAR: 0.0, T.RAY: 0.0}
+    seen = inside = 0
+    for m in T.general_poses()[:8]:
+        R, c = m[:, :3], m[:, 3]
+        n = R @ np.array([0.3, 0.2, -1.0])
+        n /= np.linalg.norm(n)
+        h = n @ (c + 0.35 * -R[:, 2])
+        _, _, cam0, cam1 = SR.view_rays(m[None], T.W, T.H, T.FOCAL)
+        k = np.stack([np.broadcast_to(cam0[None, :], (T.H, T.W)), np.broadcast_to(cam1[:, None], (T.H, T.W)), np.full((T.H, T.W), -1.0)], axis=-1)
+        t = (h - n @ c) / (k @ R.T @ n)
+        assert (t > 0).all() and t.max() < 2, "every pixel's ray meets the plane in front of the camera"
+        kp = (pts - c) @ R                                                      # R^T (p - c), per point
+        zd = -kp[..., 2]
+        with np.errstate(all="ignore"):
+            uf, vf = kp[..., 0] / zd * T.FOCAL + T.W / 2, -kp[..., 1] / zd * T.FOCAL + T.H / 2
+        u, v = np.floor(uf), np.floor(vf)
+        in_image = (zd > 0) & (u >= 0) & (u < T.W) & (v >= 0) & (v < T.H)
+        edge = (np.abs(uf - np.round(uf)) < 1e-9) | (np.abs(vf - np.round(vf)) < 1e-9) | (np.abs(zd) < 1e-9)
+        ui, vi = np.where(in_image, u, 0).astype(int), np.where(in_image, v, 0).astype(int)
+        for mode in (T.PLANAR, T.RAY):
+            d64 = t * np.linalg.norm(k, axis=-1) if mode == T.RAY else t
+            depth = d64.astype(np.float32)[None]
+            vol = T.integrate(T.volume(), m[None], T.FOCAL, depth, np.zeros((1, T.H, T.W, 3), np.uint8), np.zeros((1, T.H, T.W), np.uint8), mode)
+            along = np.linalg.norm(pts - c, axis=-1) if mode == T.RAY else zd
+            sdf = d64[vi, ui] - along
+            want_obs = in_image & (sdf >= -trunc)
+            sure = ~edge & (np.abs(sdf + trunc) > 1e-9)
+            obs = vol.weight > 0
+            assert (obs == want_obs)[sure].all() and int(edge.sum()) == 0
+            sel = obs & sure
+            err = np.abs(vol.tsdf.astype(np.float64) - np.minimum(1.0, sdf / trunc))[sel].max()
+            bound = (2.0 ** -24 * d64.max() + 1e-14) / trunc + 2.0 ** -24
+            print(f"tilted plane, mode {mode}: {int(sel.sum())} observed points, {int((vol.tsdf[sel] < 1).sum())} inside the truncation, tsdf error {err:.3e}, bound {bound:.3e}")
+            assert sel.any() and (vol.tsdf[sel] < 0).any() and (vol.tsdf[sel] == 1).any(), "both sides of the plane and the clamp, for every pose"
+            assert err <= bound
+            worst[mode] = max(worst[mode], err)
+            seen, inside = seen + int(sel.sum()), inside + int((vol.tsdf[sel] < 1).sum())
+    print(f"tilted plane: {seen} observations over 8 poses and 2 modes, {inside} inside the truncation, worst error planar {worst[T.PLANAR]:.3e}, ray {worst[T.RAY]:.3e}")
+    assert seen > 2000 and inside > 1000
+
+
+def _reach_figures(reach):
+    """Per chunk of 256 views: the most views that reach one block, the blocks reached from all four 64-view quarters, the blocks not reached."""
+    out = []
+    for lo in range(0, reach.shape[0], 256):
+        chunk = reach[lo:lo + 256]
+        quarters = np.stack([chunk[q:q + 64].any(axis=0) for q in range(0, 256, 64)])
+        out.append((int(chunk.sum(axis=0).max()), int(quarters.all(axis=0).sum()), int((~chunk.any(axis=0)).sum())))
+    return out
+
+
+def test_view_list_reaches_every_branch_of_the_chunked_cull():
+    """What the 600 views of `tsdf_ref.view_list` make a kernel do that takes views 256 at a time, a wave of 64 lanes testing 64 of them,
+    for blocks of the product's 4 x 4 x 16 points; the same figures are printed for the two other shapes the unit can be built with."""
+    c2w, depth, rgba, sem = T.view_list()
+    assert c2w.shape[0] == 600 and np.abs(c2w[:, :, :3]).min() >= T.MIN_ENTRY
+    vol = T.volume(3)
+    for block in T.BLOCKS[1:]:
+        print(f"blocks of {block}: (most survivors, blocks reached from all four quarters, blocks not reached) per chunk {_reach_figures(T.block_reach(vol, c2w, block))}")
+    reach = T.block_reach(vol, c2w)
+    figures = _reach_figures(reach)
+    print(f"blocks of {T.BLOCKS[0]}: (most survivors, blocks reached from all four quarters, blocks not reached) per chunk {figures}")
+    assert reach.shape == (600, 36)
+    # (a) more than one wave's worth of survivors, from every wave
+    chunk = reach[256:512]
+    quarters = np.stack([chunk[q:q + 64].sum(axis=0) for q in range(0, 256, 64)])
+    busy = (chunk.sum(axis=0) > 64) & (quarters > 0).all(axis=0)
+    assert busy.any() and figures[0][0] > 64 and figures[1][0] > 64
+    # (b) a block no view of the first chunk can reach, reached in the second and in the third
+    late = [T.sphere_clear(vol, m, T.B_LATE, T.MARGIN) for m in c2w[:256]]
+    n_late = [int(reach[lo:lo + 256, T.B_LATE].sum()) for lo in (0, 256, 512)]
+    print(f"block {T.B_LATE}: clear of all {sum(late)} views of chunk 0 at margin {T.MARGIN}; reached by {n_late[1]} views of chunk 1 and {n_late[2]} of chunk 2")
+    assert all(late) and n_late[0] == 0 and n_late[1] >= 1 and n_late[2] >= 1
+    # (c) a block no view can reach, beside blocks that are written
+    never = [T.sphere_clear(vol, m, T.B_NEVER, T.MARGIN) for m in c2w]
+    neighbours = [T.B_NEVER - 1, T.B_NEVER + 2, T.B_NEVER + 6]                   # one block along z, y and x: 36 blocks are 6 x 3 x 2, z fastest
+    print(f"block {T.B_NEVER}: clear of all {sum(never)} views at margin {T.MARGIN}; its neighbours {neighbours} are reached by {reach[:, neighbours].sum(axis=0).tolist()} views")
+    assert all(never) and not reach[:, T.B_NEVER].any() and reach[:, neighbours].any(axis=0).all()
+    # (d) order matters
+    want = T.integrate(T.volume(3), c2w, T.FOCAL, depth, rgba, sem, T.PLANAR)
+    back = T.integrate(T.volume(3), c2w[::-1], T.FOCAL, depth[::-1], rgba[::-1], sem[::-1], T.PLANAR)
+    n_tsdf, n_word = int((want.tsdf.view(np.uint32) != back.tsdf.view(np.uint32)).sum()), int((want.word != back.word).sum())
+    print(f"600 views reversed: {n_tsdf} tsdf values and {n_word} words differ; info {want.info.tolist()}, {int((want.weight == 3).sum())} points at the cap")
+    assert n_tsdf > 100 and n_word > 20 and np.array_equal(want.weight, back.weight)
+    # (e) every counter the images can move, and the cap
+    assert want.info[0] > 0 and want.info[1] > 0 and want.info[3] > 0 and (want.weight == 3).any() and want.info[0] > want.weight.sum()
+    index, _ = T.block_table(vol)
+    assert (want.weight[index == T.B_NEVER] == 0).all() and (want.weight[index == T.B_LATE] > 0).any()
+    # no two views are interchangeable
+    assert len({(c2w[v].tobytes(), depth[v].tobytes(), rgba[v].tobytes()) for v in range(600)}) == 600 and len({depth[v].tobytes() for v in range(0, 312, 24)}) == 13
+
+
+def test_skewed_poses_need_the_column_norms():
+    """A cull that took the pose for orthonormal (norms 1, 1, 1) would drop (view, block) pairs that hold points steps 3-4 admit: for the
+    skewed general poses `sphere_clear` with the norms forced to 1 rejects such pairs even at a margin of 0.1, and with the true norms it
+    rejects none at margin 0.  The device test on these poses therefore fails for such a cull."""
+    c2w = T.skewed(T.general_poses())
+    vol = T.volume()
+    n = T.block_reach(vol, c2w, counts=True)
+    pairs = points = 0
+    for v, b in zip(*np.nonzero(n)):
+        assert not T.sphere_clear(vol, c2w[v], b, 0.0), "the bound with the true norms never rejects a reached pair"
+        if T.sphere_clear(vol, c2w[v], b, T.MARGIN, norms=(1.0, 1.0, 1.0)):
+            pairs, points = pairs + 1, points + int(n[v, b])
+    print(f"skewed poses: {int((n > 0).sum())} reached (view, block) pairs; with the norms forced to 1 {pairs} of them, holding {points} points, are called clear")
+    assert pairs > 0 and points > 0
+    plain = T.general_poses()
+    for v, b in zip(*np.nonzero(T.block_reach(vol, plain))):
+        assert not T.sphere_clear(vol, plain[v], b, 0.0)
+
+
+def test_min_depth_binds_on_the_general_captures():
+    c2w, depth, rgba, sem = T.general_captures(T.PLANAR)
+    near = T.integrate(T.volume(3, min_depth=0.4), c2w, T.FOCAL, depth, rgba, sem, T.PLANAR)
+    zero = T.integrate(T.volume(3), c2w, T.FOCAL, depth, rgba, sem, T.PLANAR)
+    assert 0 < near.info[0] < zero.info[0] and near.tsdf.tobytes() != zero.tsdf.tobytes() and near.word.tobytes() != zero.word.tobytes()
+    only = [(v, b) for v in range(len(c2w)) for b in range(36)
+            if T.sphere_planes(T.volume(min_depth=0.4), c2w[v], b, T.MARGIN)[0] and not T.sphere_clear(T.volume(), c2w[v], b, 0.0)]
+    print(f"min_depth 0.4: {int(zero.info[0] - near.info[0])} observations fewer; {len(only)} (view, block) pairs are clear at the near plane only because of it")
+    assert len(only) > 0
+    reach = T.block_reach(T.volume(), c2w)
+    assert any(reach[v, b] for v, b in only), "and some of those blocks hold points that min_depth = 0 admits"
 
 
 # ------------------------------------------------------------------ the library's boundary, without a GPU

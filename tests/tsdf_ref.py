@@ -37,27 +37,37 @@ class Volume:
         return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1)
 
 
+def project(vol, m, W, H, focal, w=None):
+    """Steps 1-4 of the header for one view m [3,4] and the points w [..., 3] (the lattice's own when None) -> (ok bool: zd > min_depth and
+    the pixel lies in the image, px, py int64 (0 where not ok), zd, (q0, q1, q2))."""
+    m = np.asarray(m, F64).reshape(3, 4)
+    f = F64(focal)
+    w = vol.points() if w is None else np.asarray(w, F64)
+    with np.errstate(all="ignore"):
+        R, c = m[:, :3], m[:, 3]
+        q = w - c
+        q0, q1, q2 = q[..., 0], q[..., 1], q[..., 2]
+        xc = (q0 * R[0, 0] + q1 * R[1, 0]) + q2 * R[2, 0]
+        yc = (q0 * R[0, 1] + q1 * R[1, 1]) + q2 * R[2, 1]
+        zc = (q0 * R[0, 2] + q1 * R[1, 2]) + q2 * R[2, 2]
+        zd = -zc
+        ok = zd > vol.min_depth
+        u = np.floor((xc / zd) * f + F64(W) * 0.5)
+        vv = np.floor(((-yc) / zd) * f + F64(H) * 0.5)
+        ok &= (u >= 0) & (u < W) & (vv >= 0) & (vv < H)
+        px, py = np.where(ok, u, 0).astype(np.int64), np.where(ok, vv, 0).astype(np.int64)
+    return ok, px, py, zd, (q0, q1, q2)
+
+
 def integrate(vol, c2w, focal, depth, colour, classes, depth_mode=PLANAR):
     """Views in ascending order; depth [V,H,W] float32 or float16, colour [V,H,W,3 or 4] uint8, classes [V,H,W] uint8 or int64."""
     m = np.asarray(c2w, F64).reshape(-1, 3, 4)
     V, H, W = depth.shape
     assert m.shape[0] == V
-    f = F64(focal)
     w = vol.points()
     with np.errstate(all="ignore"):
         for v in range(V):
-            R, c = m[v, :, :3], m[v, :, 3]
-            q = w - c
-            q0, q1, q2 = q[..., 0], q[..., 1], q[..., 2]
-            xc = (q0 * R[0, 0] + q1 * R[1, 0]) + q2 * R[2, 0]
-            yc = (q0 * R[0, 1] + q1 * R[1, 1]) + q2 * R[2, 1]
-            zc = (q0 * R[0, 2] + q1 * R[1, 2]) + q2 * R[2, 2]
-            zd = -zc
-            ok = zd > vol.min_depth
-            u = np.floor((xc / zd) * f + F64(W) * 0.5)
-            vv = np.floor(((-yc) / zd) * f + F64(H) * 0.5)
-            ok &= (u >= 0) & (u < W) & (vv >= 0) & (vv < H)
-            px, py = np.where(ok, u, 0).astype(np.int64), np.where(ok, vv, 0).astype(np.int64)
+            ok, px, py, zd, (q0, q1, q2) = project(vol, m[v], W, H, focal, w)
             d = depth[v][py, px].astype(F64)
             invalid = ok & ~(np.isfinite(d) & (d > 0) & (d <= vol.max_depth))
             vol.info[2] += int(invalid.sum())
@@ -238,3 +248,151 @@ def room_captures(depth_mode, repeats=0):
     depth = out["depth"].copy()
     depth[1, 3, 4], depth[1, 9, 12], depth[1, 10, 5], depth[1, 15, 20] = np.nan, np.inf, 0.0, 50.0
     return c2w, depth, out["rgba"], out["sem"]
+
+
+# ------------------------------------------------------------------ general poses, long view lists and what a cull may assume of them
+CELLS = (20, 9, 21)                                                          # the lattice the device tests fuse into: the room's, one cell wider in x
+TRUNC = 4 * S
+BLOCKS = ((4, 4, 16), (1, 4, 64), (2, 8, 16))                                # the shapes csrc/tsdf.hip can be built with; the first is the product's
+MIN_ENTRY = 0.05
+
+
+def volume(max_weight=64, min_depth=0.0, max_depth=10.0):
+    return Volume(CELLS, ROOM_LO, S, TRUNC, max_weight=max_weight, min_depth=min_depth, max_depth=max_depth)
+
+
+def general_pose(position, yaw, pitch, roll):
+    """c2w [3,4] of Ry(yaw) Rx(pitch) Rz(roll), degrees: for generic angles none of the nine rotation entries is 0 or 1."""
+    a, b, g = np.deg2rad([yaw, pitch, roll])
+    Ry = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    Rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
+    Rz = np.array([[np.cos(g), -np.sin(g), 0], [np.sin(g), np.cos(g), 0], [0, 0, 1]])
+    return np.concatenate([Ry @ Rx @ Rz, np.asarray(position, F64).reshape(3, 1)], axis=1)
+
+
+def pose_pool(n, seed, spread=(0.3, 0.12, 0.35)):
+    """n general poses around the room centre: any yaw, pitch and roll within 60 degrees, positions within `spread` metres of the centre per
+    axis (the free pocket is 0.125 x 0.075 x 0.125 m, so most cameras sit among the clutter and see near hits).  A draw is repeated until
+    every rotation entry has magnitude >= MIN_ENTRY: a naive draw leaves entries of 1e-4."""
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < n:
+        m = general_pose(room_centre() + rng.uniform(-1, 1, 3) * np.asarray(spread), rng.uniform(-180, 180), rng.uniform(-60, 60), rng.uniform(-60, 60))
+        if np.abs(m[:, :3]).min() >= MIN_ENTRY:
+            out.append(m)
+    return np.stack(out)
+
+
+def general_poses(n=24):
+    return pose_pool(n, 29)
+
+
+_GENERAL = {}
+
+
+def general_captures(depth_mode):
+    """-> (c2w [24,3,4], depth float32, rgba uint8, sem uint8) of `general_poses()` from sensor_ref.views, read-only."""
+    if depth_mode not in _GENERAL:
+        c2w = general_poses()
+        out = SR.views(room(), ROOM_LO, S, c2w, W, H, FOCAL, 0.0, 100.0, ray_depth=depth_mode == RAY)
+        got = (c2w, out["depth"], out["rgba"], out["sem"])
+        for a in got:
+            a.setflags(write=False)
+        _GENERAL[depth_mode] = got
+    return _GENERAL[depth_mode]
+
+
+SKEW = np.array([[0.6, 0.3, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.9]])
+
+
+def skewed(m):
+    """The rotation block right-multiplied by SKEW: columns of norm 0.6, sqrt(1.09) and 1.9, the second sheared towards the first."""
+    m = np.asarray(m, F64).reshape(-1, 3, 4).copy()
+    m[:, :, :3] = m[:, :, :3] @ SKEW
+    return m
+
+
+def block_table(vol, block=BLOCKS[0]):
+    """-> (index int64 [NX,NY,NZ] of the block each point lies in, z fastest as the kernel numbers its workgroups, blocks per axis)."""
+    n = tuple(-(-vol.shape[k] // block[k]) for k in range(3))
+    i = [np.arange(vol.shape[k]) // block[k] for k in range(3)]
+    return (i[0][:, None, None] * n[1] + i[1][None, :, None]) * n[2] + i[2][None, None, :], n
+
+
+def block_reach(vol, c2w, block=BLOCKS[0], counts=False):
+    """bool [V, blocks]: some point of the block passes steps 3-4 for the view (with `counts`, how many do).  From `project` alone."""
+    m = np.asarray(c2w, F64).reshape(-1, 3, 4)
+    index, n = block_table(vol, block)
+    w = vol.points()
+    out = np.zeros((m.shape[0], int(np.prod(n))), np.int64)
+    for v in range(m.shape[0]):
+        out[v] = np.bincount(index[project(vol, m[v], W, H, FOCAL, w)[0]], minlength=out.shape[1])
+    return out if counts else out > 0
+
+
+def block_sphere(vol, block_index, block=BLOCKS[0]):
+    """-> (centre [3], radius) of the smallest sphere about the box of the block's existing points."""
+    index, n = block_table(vol, block)
+    b = np.unravel_index(block_index, n)
+    first = np.array([b[k] * block[k] for k in range(3)])
+    last = np.minimum(first + np.asarray(block), np.asarray(vol.shape)) - 1
+    return vol.lo + 0.5 * (first + last) * vol.voxel, 0.5 * float(vol.voxel) * float(np.linalg.norm(last - first))
+
+
+def sphere_planes(vol, m, block_index, margin, block=BLOCKS[0], norms=None):
+    """Plain float64 geometry, independent of `project`: is the block's bounding sphere, grown to (1 + margin) radius, wholly on the
+    rejected side of (the near plane zd = min_depth, u = 0, u = W, v = 0, v = H)?  -> bool [5].
+
+    In camera coordinates k = R^T q the admitted set of steps 3-4 is zd > min_depth with -zd W/2 <= xc focal < zd W/2 and the same for -yc
+    and H: five half-spaces, each a linear form a . k >= b.  Over a ball of radius r in q the form R a . q varies by r |R a|, and
+    |R a| <= sum |a_j| |column j of R| is the bound a cull can afford per view; `norms` replaces the three column norms (what a cull that
+    assumed an orthonormal pose would use: (1, 1, 1))."""
+    m = np.asarray(m, F64).reshape(3, 4)
+    R = m[:, :3]
+    centre, radius = block_sphere(vol, block_index, block)
+    k = R.T @ (centre - m[:, 3])
+    n = np.linalg.norm(R, axis=0) if norms is None else np.asarray(norms, F64)
+    r = (1.0 + margin) * radius
+    hw, hh, f = 0.5 * W, 0.5 * H, FOCAL
+    forms = [(np.array([0.0, 0.0, -1.0]), float(vol.min_depth)),                 # zd >= min_depth
+             (np.array([f, 0.0, -hw]), 0.0), (np.array([-f, 0.0, -hw]), 0.0),     # xc f + zd hw >= 0;  zd hw - xc f >= 0
+             (np.array([0.0, -f, -hh]), 0.0), (np.array([0.0, f, -hh]), 0.0)]     # -yc f + zd hh >= 0;  zd hh + yc f >= 0
+    return np.array([a @ k + r * (np.abs(a) @ n) < b for a, b in forms])
+
+
+def sphere_clear(vol, m, block_index, margin, block=BLOCKS[0], norms=None):
+    return bool(sphere_planes(vol, m, block_index, margin, block, norms).any())
+
+
+B_NEVER, B_LATE, MARGIN = 1, 35, 0.1                                         # of the product's 36 blocks: two corners of the far z end, x and y apart
+_VIEW_LISTS = {}
+
+
+def view_list(V=600, depth_mode=PLANAR):
+    """-> (c2w [V,3,4], depth float32 [V,H,W], rgba, sem): two full chunks of 256 views and a partial one, for the lattice of `volume()`.
+
+    Poses come from a seeded pool of 3000 general poses.  Every view is `sphere_clear` of block B_NEVER at MARGIN, views 0 .. 255 of block
+    B_LATE too, and the later ones are the pool's remaining ones in order (many reach B_LATE: tests/test_tsdf_cpu.py counts them).  The
+    images are those of `general_captures`, view v taking capture v mod 24 with (1 + v mod 13) 2^-10 m added to every hit's depth: poses and
+    images do not belong together, which the fusion cannot know.  Every ninth view from 330 on repeats the pose and the depth image of the
+    view 70 before it, a view of another wave of the same chunk, under its own colours and classes: the two tie in |sdf|, and step 11's
+    strict < gives the word to whichever comes first.  So no two views are interchangeable."""
+    if (V, depth_mode) not in _VIEW_LISTS:
+        pool, vol = pose_pool(3000, 31), volume()
+        never = np.array([sphere_clear(vol, m, B_NEVER, MARGIN) for m in pool])
+        late = np.array([sphere_clear(vol, m, B_LATE, MARGIN) for m in pool])
+        head = np.nonzero(never & late)[0][:min(V, 256)]
+        rest = np.setdiff1d(np.nonzero(never)[0], head)[:V - len(head)]
+        c2w = pool[np.concatenate([head, rest])]
+        assert c2w.shape[0] == V, "the pool is too small for this many views"
+        _, depth, rgba, sem = general_captures(depth_mode)
+        pick = np.arange(V) % depth.shape[0]
+        offset = ((1 + np.arange(V) % 13) * 2.0 ** -10).astype(F32)
+        depth = np.where(depth[pick] > 0, depth[pick] + offset[:, None, None], depth[pick]).astype(F32)
+        for b in range(330, V, 9):
+            c2w[b], depth[b] = c2w[b - 70], depth[b - 70]
+        got = (c2w, depth, rgba[pick], sem[pick])
+        for a in got:
+            a.setflags(write=False)
+        _VIEW_LISTS[(V, depth_mode)] = got
+    return _VIEW_LISTS[(V, depth_mode)]
